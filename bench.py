@@ -4,26 +4,30 @@ path (temporal sampling -> mailbox consume + GRU -> temporal attention -> memory
 write-back), BASELINE.json configs[1]: JODIE-Wikipedia-shaped stream, d=172, batch=1024,
 msg_src=left upd_src=left, on 1 (or N) MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one batch of B events through tg_stream_step.  The whole synthetic stream is
 resident in HBM before the timed region.  Order of a run: PREROLL untimed batches bring the
 memories / mailbox to steady state (independent of --warmup: the number of involved nodes per
 batch keeps growing for ~100 batches), W untimed warm-up steps, then the timed region replays
 a captured hipGraph of one step K times (the step reads its batch at a device-side offset and
-advances it).  Per-stage HIP-event times are then taken on the NEXT unseen batches of the
-stream (the state keeps moving forward: no batch is replayed).
-Rank 0 prints ONE JSON line (see the task contract) including
+advances it).  --dump-outputs DIR then writes what the last timed step produced (dump_outputs).
+A plain run stops there and prints the headline line (metric, value, unit, ms_per_step, ...).
+With --full, per-stage HIP-event times are then taken on the NEXT unseen batches of the
+stream (the state keeps moving forward: no batch is replayed), and rank 0's ONE JSON line also
+holds the repeats of the timed region, the replay self-check and
   roofline               - the dominant kernel of the step, timed live with HIP events, priced with the
                            algorithmic flops / bytes of SURVEY.md s8(d) and the measured U / O / P of the run;
   roofline_memory_gather - the memory-gather kernel OF THE TIMED STEP (eager direct form: the attention core, which gathers the
                            involved rows itself) against the HBM roofline on its COMPULSORY bytes, the design's and the
                            PMC bytes beside it, plus SURVEY's full bytes_gather over gather + updater;
   roofline_sampler       - the sampler launch on the HBM roofline (SURVEY s8 d bytes_samp) where it has a launch of its own;
-  c5s_leg                - (default C2 run only) a short run of the HBM-roofline configuration (10 M nodes,
+  c5s_leg                - (--full C2 run only) a short run of the HBM-roofline configuration (10 M nodes,
                            d=256, B=65536): at C2 every table is cache resident, so the HBM claim is made there;
   cpu_baseline           - the CPU oracle (oracle/tiger_oracle.py, "port") on a bounded sample of the same
-                           workload on this host's cores (thread count chosen by a quick sweep).
+                           workload on this host's cores (thread count chosen by a quick sweep);
+  reference_api_loop, partitioned_form_1rank - (--full C2 run only) the evaluation harness and the one-rank
+                           multi-GPU code path.
 With --gpus N > 1 and no torchrun environment the script starts its own N ranks.
 """
 import argparse
@@ -144,7 +148,7 @@ def build_models(stream, d, K, msg_src, upd_src, restarter='static', hist_len=40
     torch.manual_seed(seed)
     with torch.device(dev):  # parameters and the (possibly tens of GB of) state tables are born on the GPU
         fg = NumericalFeature(None if nfeats is None else torch.from_numpy(nfeats).to(dev),
-                              None if efeats is None else torch.from_numpy(efeats).to(dev), dim=d, device=dev)
+                              None if efeats is None else torch.as_tensor(efeats).to(dev), dim=d, device=dev)
         fg.n_nodes, fg.n_edges = n_nodes, len(stream['src'])
         if restarter == 'seq':
             rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=hist_len, n_head=2, dropout=dropout)
@@ -163,6 +167,43 @@ def build_models(stream, d, K, msg_src, upd_src, restarter='static', hist_len=40
         oracle = O.OracleTIGER(params, og, n_nodes=n_nodes, dim=d, nfeats=nfeats, efeats=efeats, n_neighbors=K,
                                msg_src=msg_src, upd_src=upd_src, restarter=restarter, hist_len=hist_len)
     return model, oracle
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20  # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every (name, tensor) as out_dir/<name>.npy, float64 kept, anything else as float32.  While the
+    whole set fits in DUMP_LIMIT_BYTES the arrays are written whole; otherwise each array over its equal share keeps a
+    fixed sample of its rows (np.random.RandomState(0), sorted), the same in every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    over = sum(size(t) for _, t in arrays) > DUMP_LIMIT_BYTES
+    for name, t in arrays:
+        t = t.detach()
+        if over and size(t) > share:
+            keep = max(1, share * t.shape[0] // size(t))
+            rows = np.sort(np.random.RandomState(0).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+
+
+def device_edge_features(E, d, dev, seed=0):
+    """make_stream's edge-feature table (E + 1 rows of N(0, 1), row 0 = 0) drawn on the GPU from a seeded generator: the
+    same values in every run, no host time - a plain bench run's stream grows with --steps"""
+    ef = torch.empty(E + 1, d, dtype=torch.float32, device=dev)
+    ef.normal_(generator=torch.Generator(device=dev).manual_seed(seed))
+    ef[0] = 0
+    return ef
+
+
+def stream_outputs(model, buf):
+    """What the streaming step gives its caller: the embeddings of cat[src, dst, neg] of the batch, and the memories
+    (values, last-update times) it wrote back."""
+    return [('h', buf.h), ('left_memory', model.left_memory.vals), ('left_update_ts', model.left_memory.update_ts),
+            ('right_memory', model.right_memory.vals), ('right_update_ts', model.right_memory.update_ts)]
 
 
 
@@ -400,20 +441,26 @@ def roofline_of(name, ms, work, traffic, overhead=0.0):
     return dict(bound='hbm', kernel=name, achieved=None, peak=HBM_PEAK_GBS, unit='GB/s', frac=None, **extra)
 
 
-def run_stream_leg(cfg, args, preroll, warmup, steps, n_prof, traffic_tag, want_cpu=False):
-    """One single-GPU measurement of the streaming step on workload `cfg`; returns the pieces of the JSON line."""
+def run_stream_leg(cfg, args, preroll, warmup, steps, n_prof, traffic_tag, want_cpu=False, full=True, dump_dir=None):
+    """One single-GPU measurement of the streaming step on workload `cfg`; returns the pieces of the JSON line.
+    full=False: only the timed region and what it needs - the stream holds the batches of the pre-roll, the warm-up and
+    the timed steps (+ 2 spares: a prefetching step reads the next batch), its edge features are drawn on the GPU
+    (device_edge_features: the host would spend seconds per million events on them); dump_dir: dump_outputs of the last
+    timed step."""
     torch.cuda.set_device(0)
     dev = torch.device('cuda', 0)
     B, K, d = cfg['B'], cfg['K'], cfg['d']
     # the timed region is K steps, once (the contract); `reps` further, separately timed repetitions of the same K steps
     # on the following batches give its spread (a K = 20 region is ONE 1.7 ms graph replay)
-    reps = args.repeats if (B <= 8192 and not args.no_graph) else 0
-    n_batches = preroll + warmup + steps * (1 + reps) + n_prof + 8  # + 4 batches for the copy-form gather timing, + 2 for the set sizes of a lean run, + 2 spare
+    reps = args.repeats if (full and B <= 8192 and not args.no_graph) else 0
+    n_batches = preroll + warmup + steps * (1 + reps) + (n_prof + 8 if full else 2)  # --full: + 4 batches for the copy-form gather timing, + 2 for the set sizes of a lean run, + 2 spare
     E = max(cfg['E'], n_batches * B) if not cfg.get('counter_stream') else n_batches * B
     no_feats = bool(cfg.get('no_feats'))
     stream = make_stream(cfg['n_u'], cfg['n_i'], E, cfg['T'] * E / cfg['E'], seed=0, d_e=d,
-                         integer_ts=cfg.get('integer_ts', True), with_efeats=not no_feats,
+                         integer_ts=cfg.get('integer_ts', True), with_efeats=full and not no_feats,
                          counter=bool(cfg.get('counter_stream')))
+    if not full and not no_feats:
+        stream['efeats'] = device_edge_features(E, d, dev)
     model, _ = build_models(stream, d, K, cfg['msg_src'], cfg['upd_src'], restarter='static', device='cuda:0',
                             zero_nfeats=not no_feats)
     resident = tuple(torch.from_numpy(stream[k]).to(dev) for k in ('src', 'dst', 'neg', 'ts', 'eids'))
@@ -466,7 +513,7 @@ def run_stream_leg(cfg, args, preroll, warmup, steps, n_prof, traffic_tag, want_
     n_replay_warm = 0 if (args.no_graph or n_untimed < 6) else (gsteps if gsteps > 1 else min(2, warmup))
     u_trace = []
     for b in range(n_untimed - n_replay_warm):
-        full_form = lean and b in (n_untimed // 2, n_untimed - n_replay_warm - 2)  # two full steps: the involved set's size
+        full_form = full and lean and b in (n_untimed // 2, n_untimed - n_replay_warm - 2)  # two full steps: the involved set's size
         if full_form:
             buf.io.lean = 0
         model.launch_step(buf)
@@ -504,6 +551,17 @@ def run_stream_leg(cfg, args, preroll, warmup, steps, n_prof, traffic_tag, want_
     dt = time.perf_counter() - t0
     assert int(buf.err.item()) == 0, f'invariant word {int(buf.err.item())}'
     assert int(buf.offset.item()) == (preroll + warmup + steps) * B
+    if dump_dir:
+        dump_outputs(dump_dir, stream_outputs(model, buf))
+    if not full:
+        launch = f'hipGraph replay, {gsteps} step{"s" if gsteps > 1 else ""} per captured graph' if graph is not None else 'eager'
+        out = dict(value=steps * B / dt, ms_per_step=dt / steps * 1e3,
+                   config=dict(workload=cfg['name'], batch=B, dim=d, n_neighbors=K, msg_src=cfg['msg_src'],
+                               upd_src=cfg['upd_src'], n_nodes=stream['n_nodes'], events=E,
+                               mode='stream (no_grad) STEP 1-6', launch=launch, state_preroll_batches=preroll))
+        if restart_prob > 0:
+            out['config'].update(restart_prob=restart_prob, restart_triggers_in_timed_region=n_trig)
+        return out
     rep_ms = []
     for _ in range(reps if graph is not None else 0):
         torch.cuda.synchronize()
@@ -982,13 +1040,20 @@ def train_main(args, cfg):
     assert int(tr.buf.sb.offset.item()) == (args.warmup + args.steps) * B
     loss = float(tr.buf.losses[0])
     assert np.isfinite(loss)
+    if args.dump_outputs:  # what the last timed iteration gives its caller: losses, scores, the embeddings of the batch's
+        # sources and destinations (rows [0, 2B) of the step's h), updated weights.
+        # Not bit-reproducible run to run: some gradients are summed with float atomics (e.g. the time encoder's), Adam and
+        # cos(freq * dt) amplify the differences - compare these dumps loosely, the streaming step's exactly
+        dump_outputs(args.dump_outputs, [('losses', tr.buf.losses), ('pos_scores', tr.buf.pos_scores),
+                                         ('neg_scores', tr.buf.neg_scores), ('h_src_dst', tr.buf.sb.h[:2 * B]),
+                                         ('parameters', torch.cat([p.detach().flatten() for p in model.parameters()]))])
     extra = {}
     if lazy is not None:
         r = lazy.pop('restarted')
         if r:
             lazy.update(restarted_nodes_per_iteration_mean=float(np.mean(r)), restarted_nodes_per_iteration_max=int(max(r)))
         extra['lazy_restart_loop'] = lazy
-    if rkind == 'seq' and lazy is None:
+    if rkind == 'seq' and lazy is None and args.full:
         try:
             extra['roofline_restarter'] = restarter_roofline(stream, cfg, args, args.warmup, args.steps, dt / args.steps * 1e3)
         except Exception as e:  # a side object: the line does not depend on it
@@ -1009,17 +1074,25 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: repeats of the timed region, the replay self-check, per-stage / per-kernel '
+                         'timings and rooflines, the CPU baseline and (C2) the c5s, reference API loop and one-rank '
+                         'multi-GPU legs; a plain run times the steps and prints the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, '
+                         f'{DUMP_LIMIT_BYTES >> 20} MB at most in all: a fixed sample of the rows of larger outputs); bit-'
+                         'reproducible for the streaming step, not for --train (float-atomic gradient sums)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--workload', default='c2', choices=sorted(WORKLOADS), help='c2 is the benchmarked configuration')
     ap.add_argument('--preroll', type=int, default=None,
                     help=f'untimed state pre-roll batches before --warmup (default {PREROLL}; 96 for c5s / c5)')
-    ap.add_argument('--no-c5s-leg', action='store_true', help='default C2 run: skip the short HBM-roofline leg')
+    ap.add_argument('--no-c5s-leg', action='store_true', help='--full C2 run: skip the short HBM-roofline leg')
     ap.add_argument('--no-api-loop', action='store_true',
-                    help='default C2 run: skip the reference_api_loop leg (eval_edge_prediction on the drop-in API)')
+                    help='--full C2 run: skip the reference_api_loop leg (eval_edge_prediction on the drop-in API)')
     ap.add_argument('--no-dist-leg', action='store_true',
-                    help='default C2 run: skip the one-rank leg of the multi-GPU code path (partitioned_form_1rank)')
+                    help='--full C2 run: skip the one-rank leg of the multi-GPU code path (partitioned_form_1rank)')
     ap.add_argument('--repeats', type=int, default=4,
-                    help='further, separately timed repetitions of the K-step region (spread; not part of `value`)')
+                    help='--full: further, separately timed repetitions of the K-step region (spread; not part of `value`)')
     ap.add_argument('--graph-steps', type=int, default=0,
                     help='steps per captured hipGraph (default: the largest divisor of --steps up to 25)')
     ap.add_argument('--no-prefetch', action='store_true',
@@ -1028,7 +1101,7 @@ def main():
                     help='form the involved / outdated sets in every step even where nothing reads them')
     ap.add_argument('--no-graph', action='store_true', help='launch steps eagerly instead of replaying a hipGraph')
     ap.add_argument('--no-self-check', action='store_true',
-                    help='skip the untimed comparison of the replayed region with a second, eagerly launched model')
+                    help='--full: skip the untimed comparison of the replayed region with a second, eagerly launched model')
     ap.add_argument('--force-dist', action='store_true', help='run the multi-GPU code path even with one rank')
     ap.add_argument('--dist-graphs', action='store_true',
                     help='multi-GPU: replay captured hipGraphs around the exchange (experimental; default eager)')
@@ -1060,6 +1133,9 @@ def main():
                          'iteration (the reference default is 0.01); 0 = the training step alone')
     ap.add_argument('--hist-len', type=int, default=40, help='--train-restarter seq: history length (reference default 40, init_utils.py:58)')
     args = ap.parse_args()
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full  # (the multi-GPU path reads the flag too)
+    if args.dump_outputs and not args.train and (args.gpus > 1 or args.force_dist):
+        ap.error('--dump-outputs: single-GPU runs only')
     cfg = dict(WORKLOADS[args.workload])
     if args.train:
         return train_main(args, cfg)
@@ -1075,13 +1151,14 @@ def main():
     preroll = args.preroll if args.preroll is not None else (C5S_PREROLL if args.workload in ('c5s', 'c5') else PREROLL)
     n_prof = max(4, min(args.steps, 30 if cfg['B'] <= 8192 else 6))
     leg = run_stream_leg(cfg, args, preroll, args.warmup, args.steps, n_prof, traffic_tag=args.workload,
-                         want_cpu=not args.no_cpu_baseline and args.workload == 'c2')
+                         want_cpu=not args.no_cpu_baseline and args.workload == 'c2', full=args.full,
+                         dump_dir=args.dump_outputs)
     out = dict(metric='processed interaction-events/sec (memory+aggregate+embed), Wikipedia d=172',
                value=leg.pop('value'), unit='events/s', n_gpus=1, steps=args.steps, warmup=args.warmup,
                ms_per_step=leg.pop('ms_per_step'), higher_is_better=True, scaling='weak', vs_baseline=None,
                dtype='f32', data='synthetic')
     out.update(leg)
-    if args.workload == 'c2' and not args.no_c5s_leg:
+    if args.full and args.workload == 'c2' and not args.no_c5s_leg:
         # at C2 every table is cache resident (150 MB): the HBM-roofline claim for the memory-gather kernel is made
         # on the C5-shaped tables (10 M nodes, d=256, B=65536: 70 GB of state), C5S_PREROLL untimed batches and 30 timed steps; the involved set still grows slowly
         # there (its sizes before and after the timed region are in the line)
@@ -1090,12 +1167,12 @@ def main():
                               config=c5['config'], roofline_memory_gather=c5['roofline_memory_gather'],
                               roofline_sampler=c5['roofline_sampler'], roofline_updater=c5['roofline_updater'],
                               roofline_neighbour_gather=c5['roofline_neighbour_gather'], stages_ms=c5['stages_ms'])
-    if args.workload == 'c2' and not args.no_api_loop:
+    if args.full and args.workload == 'c2' and not args.no_api_loop:
         try:
             out['reference_api_loop'] = reference_api_loop(cfg)
         except Exception as e:  # a side leg: the headline line does not depend on it
             out['reference_api_loop'] = dict(error=repr(e))
-    if args.workload == 'c2' and not args.no_dist_leg:
+    if args.full and args.workload == 'c2' and not args.no_dist_leg:
         # the N = 1 point of the multi-GPU code path (partitioned state, hipGraph segments around two RCCL
         # all_to_all_single with one rank) next to the single-GPU graph line, so that a scaling curve whose N > 1 points
         # come from that path has an N = 1 of the same form on record

@@ -14,7 +14,7 @@ below as `scatter_max`; among equal maxima the FIRST position wins, which is the
 torch_scatter CPU behaviour.  Everything downstream of that tie rule is
 therefore "parity unpinned" by the reference itself and pinned by these vectors.
 
-usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [NAME ...]   (no NAME: every file)
 """
 import os
 import sys
@@ -146,11 +146,12 @@ def build_reference_model(cfg, nfeats, efeats, graph, n_edges, dropout=0.1):
     fg.n_nodes = graph.num_node
     fg.n_edges = n_edges
     if cfg['restarter'] == 'seq':
-        rst = SeqRestarter(raw_feat_getter=fg, graph=graph, hist_len=cfg['H'], n_head=2, dropout=dropout)
+        rst = SeqRestarter(raw_feat_getter=fg, graph=graph, hist_len=cfg['H'], n_head=cfg.get('nh', 2),
+                           dropout=dropout)
     else:
         rst = StaticRestarter(raw_feat_getter=fg, graph=graph)
     model = TIGER(raw_feat_getter=fg, graph=graph, restarter=rst, n_neighbors=cfg['K'],
-                  hit_type=cfg.get('hit', 'bin'), n_layers=cfg.get('L', 1), n_head=2, dropout=dropout,
+                  hit_type=cfg.get('hit', 'bin'), n_layers=cfg.get('L', 1), n_head=cfg.get('nh', 2), dropout=dropout,
                   msg_src=cfg['msg_src'], upd_src=cfg['upd_src'],
                   msg_tsfm_type=cfg.get('tsfm', 'id'), mem_update_type=cfg.get('upd_fn', 'gru'),
                   tgn_mode=True, msg_last_only=True)
@@ -547,6 +548,11 @@ TRAIN_SCENARIOS = {
     'train_contrast_ll_d16_L2': dict(d=16, n_u=40, n_i=15, E=320, T=240.0, B=40, n_batches=6, K=6, H=6, L=2, seed=27,
                                      wseed=27, restarter='seq', msg_src='left', upd_src='left', hit='vec',
                                      contrast_only=1, lr=1e-2, mutual_coef=1.0, grad_batches=(1, 4)),
+    # --n_heads 4 with edge features narrower than the memory (the TGN-preprocessed MOOC layout): attention head width
+    # 2d/4 = 16, restarter head width (4d + d_e)/4 = 33 - odd
+    'train_seq_lr_d32_e4_h4': dict(d=32, d_e=4, nh=4, n_u=40, n_i=15, E=240, T=300.0, B=40, n_batches=6, K=5, H=10,
+                                   seed=29, wseed=29, restarter='seq', msg_src='left', upd_src='right', hit='bin',
+                                   restart_at=3, lr=1e-2, mutual_coef=1.0, grad_batches=(4,)),
 }
 
 CKPT_SCENARIOS = {
@@ -584,6 +590,15 @@ SCENARIOS = {
                             restarter='static', msg_src='left', upd_src='right', restart_at=5),
     'seq_ll_d16_L2': dict(d=16, n_u=40, n_i=15, E=300, T=200.0, B=40, n_batches=5, K=5, H=6, L=2, seed=9, wseed=9,
                           nfeat='zero', restarter='seq', msg_src='left', upd_src='left'),
+    # --n_heads 4, edge features narrower than the memory (MOOC-shaped): restarter head width (4d + d_e)/4 = 33 is odd
+    'seq_lr_d32_e4_h4': dict(d=32, d_e=4, nh=4, n_u=40, n_i=15, E=400, T=300.0, B=40, n_batches=8, K=6, H=12, seed=10,
+                             wseed=10, restarter='seq', msg_src='left', upd_src='right', restart_at=5),
+    # --n_heads 1
+    'static_ll_d16_h1': dict(d=16, nh=1, n_u=60, n_i=25, E=640, T=500.0, B=64, n_batches=8, K=10, seed=11, wseed=11,
+                             restarter='static', msg_src='left', upd_src='left', restart_at=5),
+    # --n_heads 1, no node table and edge features wider than the memory (--dim below the edge width)
+    'seq_lr_d8_e20_h1': dict(d=8, d_e=20, nh=1, n_u=40, n_i=15, E=480, T=300.0, B=40, n_batches=10, K=5, H=8, seed=12,
+                             wseed=12, nfeat=None, restarter='seq', msg_src='left', upd_src='right', restart_at=6),
 }
 
 if __name__ == '__main__':

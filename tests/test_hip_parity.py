@@ -34,11 +34,11 @@ def build_hip_model(z, cfg, strategy='recent_edges', dropout=0.1):
                           None if efeats is None else torch.from_numpy(efeats), dim=cfg['d'], device=dev())
     fg.n_nodes, fg.n_edges = n_nodes, len(z['src'])
     if cfg['restarter'] == 'seq':
-        rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=cfg['H'], n_head=2, dropout=dropout)
+        rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=cfg['H'], n_head=cfg.get('nh', 2), dropout=dropout)
     else:
         rst = StaticRestarter(raw_feat_getter=fg, graph=g)
     model = TIGER(raw_feat_getter=fg, graph=g, restarter=rst, n_neighbors=cfg['K'], hit_type=cfg.get('hit', 'bin'),
-                  n_layers=cfg.get('L', 1), n_head=2, dropout=dropout, msg_src=cfg['msg_src'], upd_src=cfg['upd_src'],
+                  n_layers=cfg.get('L', 1), n_head=cfg.get('nh', 2), dropout=dropout, msg_src=cfg['msg_src'], upd_src=cfg['upd_src'],
                   msg_tsfm_type=cfg.get('tsfm', 'id'), mem_update_type=cfg.get('upd_fn', 'gru'))
     params = fixture_params(z, cfg)
     own = dict(model.named_parameters())
@@ -1054,7 +1054,8 @@ def test_time_encode_large_arguments():
     assert np.abs(out - tref).max() < 5e-7
 
 
-@pytest.mark.parametrize('name', ['static_ll_d16', 'seq_lr_d8', 'seq_rr_d8_nofeat', 'static_ll_d172'])
+@pytest.mark.parametrize('name', ['static_ll_d16', 'seq_lr_d8', 'seq_rr_d8_nofeat', 'static_ll_d172',
+                                  'seq_lr_d32_e4_h4', 'static_ll_d16_h1', 'seq_lr_d8_e20_h1'])
 def test_fused_attention_weights_match_reference(name):
     """tg_attn_fuse (q+g and v+out+fc1 products pre-multiplied): embeddings against the reference fixtures
     and against the unfused path, including centres without neighbours (the masked constant)."""

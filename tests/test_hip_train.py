@@ -233,7 +233,7 @@ def test_two_layer_training_step_with_the_recent_nodes_strategy(strategy):
 
 
 @pytest.mark.parametrize('name', ['train_seq_lr_d8', 'train_static_ll_d16', 'train_mlp_merge_d8', 'train_linear_gru_d8',
-                                  'train_static_lr_d8_L2', 'train_seq_lr_d8_zeronf'])
+                                  'train_static_lr_d8_L2', 'train_seq_lr_d8_zeronf', 'train_seq_lr_d32_e4_h4'])
 def test_mutual_gradients_match_oracle(name):
     """contrast + mutual loss (tiger.py:547-592): restarter gradients and both losses."""
     from oracle import tiger_oracle as O
@@ -269,7 +269,7 @@ def test_mutual_gradients_match_oracle(name):
         assert int(tb.flags[2]) == had_grad, b
 
 
-@pytest.mark.parametrize('name', ['train_seq_lr_d8', 'train_static_ll_d16'])
+@pytest.mark.parametrize('name', ['train_seq_lr_d8', 'train_static_ll_d16', 'train_seq_lr_d32_e4_h4'])
 @pytest.mark.parametrize('loop', ['host_sets', 'device'])
 def test_fused_trainer_mutual_trajectory(loop, name):
     """Full reference recipe (seq restarter, mutual learning, lazy restart at batch 6) with no
@@ -585,6 +585,8 @@ def test_training_other_shapes(d, n_head, hit, K, restarter):
         assert worst[0] < 3e-4, (b, worst)
 
 
+# (not train_seq_lr_d32_e4_h4: its stream ends before batch 8; the odd head width with both row classes of the backward is
+#  test_hip_heads_widths.test_training_step_heads_and_widths)
 @pytest.mark.parametrize('name,H', [('train_seq_lr_d8_zeronf', 100), ('train_seq_lr_d8', 72), ('train_seq_lr_d8_zeronf', 33)])
 def test_long_history_restarter_forward_and_gradients(name, H):
     """--hist_len beyond 64 (init_utils.py:58 takes any int; the score kernels' 128-row grids need more dynamic LDS than a
@@ -610,9 +612,9 @@ def test_long_history_restarter_forward_and_gradients(name, H):
     g = Graph.from_arrays(z['src'], z['dst'], z['ts'], z['eids'], strategy='recent_edges', seed=0, device=dev())
     fg = NumericalFeature(None if nfeats is None else torch.from_numpy(nfeats), torch.from_numpy(efeats), dim=cfg['d'], device=dev())
     fg.n_nodes, fg.n_edges = n_nodes, len(z['src'])
-    rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=H, n_head=2, dropout=0.0)
+    rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=H, n_head=cfg.get('nh', 2), dropout=0.0)
     model = TIGER(raw_feat_getter=fg, graph=g, restarter=rst, n_neighbors=cfg['K'], hit_type=cfg.get('hit', 'bin'), n_layers=1,
-                  n_head=2, dropout=0.0, msg_src=cfg['msg_src'], upd_src=cfg['upd_src'])
+                  n_head=cfg.get('nh', 2), dropout=0.0, msg_src=cfg['msg_src'], upd_src=cfg['upd_src'])
     params = {k: golden_param(k, tuple(v.shape), cfg['wseed']) for k, v in model.named_parameters()}
     with torch.no_grad():
         for k, v in model.named_parameters():
@@ -620,7 +622,8 @@ def test_long_history_restarter_forward_and_gradients(name, H):
     model = model.to(dev())
     og = O.OracleGraph(z['src'], z['dst'], z['ts'], z['eids'], strategy='recent_edges', seed=0)
     orc = O.OracleTIGER(params, og, n_nodes=n_nodes, dim=cfg['d'], nfeats=nfeats, efeats=efeats, n_neighbors=cfg['K'],
-                        msg_src=cfg['msg_src'], upd_src=cfg['upd_src'], restarter='seq', hist_len=H, hit_type=cfg.get('hit', 'bin'))
+                        msg_src=cfg['msg_src'], upd_src=cfg['upd_src'], restarter='seq', hist_len=H, hit_type=cfg.get('hit', 'bin'),
+                        n_head=cfg.get('nh', 2))
     # forward at the end of the stream: long histories for the popular nodes, short (padded) ones for the others
     model.eval()
     nids = np.arange(1, n_nodes, dtype=np.int64)
@@ -650,7 +653,8 @@ def test_long_history_restarter_forward_and_gradients(name, H):
             assert grad_err(gv.cpu().numpy(), grads[k].numpy()) < 2e-4, (b, k)
 
 
-@pytest.mark.parametrize('name,H', [('train_seq_lr_d8_zeronf', 1), ('train_seq_lr_d8_zeronf', 2), ('train_seq_lr_d8', 1), ('train_seq_lr_d8', 5)])
+@pytest.mark.parametrize('name,H', [('train_seq_lr_d8_zeronf', 1), ('train_seq_lr_d8_zeronf', 2), ('train_seq_lr_d8', 1), ('train_seq_lr_d8', 5),
+                                    ('train_seq_lr_d32_e4_h4', 2)])  # 4 heads of odd width 33
 def test_restarter_forward_on_empty_and_minimal_histories(name, H):
     """Edge cases of the compact-row restarter (csrc/tg_restart.hip): hist_len 1 (only the shared last row exists), 2 and 5;
     every node restarted at time 0 (no history at all: every slot padded, the last one included), at a mid-stream time and
@@ -671,9 +675,9 @@ def test_restarter_forward_on_empty_and_minimal_histories(name, H):
     g = Graph.from_arrays(z['src'], z['dst'], z['ts'], z['eids'], strategy='recent_edges', seed=0, device=dev())
     fg = NumericalFeature(None if nfeats is None else torch.from_numpy(nfeats), torch.from_numpy(efeats), dim=cfg['d'], device=dev())
     fg.n_nodes, fg.n_edges = n_nodes, len(z['src'])
-    rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=H, n_head=2, dropout=0.0)
+    rst = SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=H, n_head=cfg.get('nh', 2), dropout=0.0)
     model = TIGER(raw_feat_getter=fg, graph=g, restarter=rst, n_neighbors=cfg['K'], hit_type=cfg.get('hit', 'bin'), n_layers=1,
-                  n_head=2, dropout=0.0, msg_src=cfg['msg_src'], upd_src=cfg['upd_src'])
+                  n_head=cfg.get('nh', 2), dropout=0.0, msg_src=cfg['msg_src'], upd_src=cfg['upd_src'])
     params = {k: golden_param(k, tuple(v.shape), cfg['wseed']) for k, v in model.named_parameters()}
     with torch.no_grad():
         for k, v in model.named_parameters():
@@ -681,7 +685,8 @@ def test_restarter_forward_on_empty_and_minimal_histories(name, H):
     model = model.to(dev()).eval()
     og = O.OracleGraph(z['src'], z['dst'], z['ts'], z['eids'], strategy='recent_edges', seed=0)
     orc = O.OracleTIGER(params, og, n_nodes=n_nodes, dim=cfg['d'], nfeats=nfeats, efeats=efeats, n_neighbors=cfg['K'],
-                        msg_src=cfg['msg_src'], upd_src=cfg['upd_src'], restarter='seq', hist_len=H, hit_type=cfg.get('hit', 'bin'))
+                        msg_src=cfg['msg_src'], upd_src=cfg['upd_src'], restarter='seq', hist_len=H, hit_type=cfg.get('hit', 'bin'),
+                        n_head=cfg.get('nh', 2))
     tmax = float(np.float32(z['ts'].max()))
     for nids, t in ((np.arange(n_nodes, dtype=np.int64), 0.0), (np.arange(1, n_nodes, dtype=np.int64), 0.5 * tmax),
                     (np.arange(1, n_nodes, dtype=np.int64), tmax + 1.0), (np.array([int(z['dst'][0])], dtype=np.int64), tmax + 1.0)):

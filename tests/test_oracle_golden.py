@@ -73,7 +73,7 @@ def build_oracle(z, cfg):
     return O.OracleTIGER(fixture_params(z, cfg), g, n_nodes=n_nodes, dim=cfg['d'], nfeats=nfeats, efeats=efeats,
                          n_neighbors=cfg['K'], msg_src=cfg['msg_src'], upd_src=cfg['upd_src'],
                          restarter=cfg['restarter'], hist_len=cfg.get('H'), tsfm=cfg.get('tsfm', 'id'),
-                         upd_fn=cfg.get('upd_fn', 'gru'), hit_type=cfg.get('hit', 'bin'))
+                         upd_fn=cfg.get('upd_fn', 'gru'), hit_type=cfg.get('hit', 'bin'), n_head=cfg.get('nh', 2))
 
 
 def check_state(m, z, tag):
@@ -145,7 +145,7 @@ def test_stream_matches_reference(name):
 
 # --------------------------------------------------------------------------- training tail
 TRAIN_FIXTURES = ['train_seq_lr_d8', 'train_static_ll_d16', 'train_contrast_rr_d8', 'train_mlp_merge_d8',
-                  'train_linear_gru_d8', 'train_seq_lr_d8_zeronf']
+                  'train_linear_gru_d8', 'train_seq_lr_d8_zeronf', 'train_seq_lr_d32_e4_h4']
 TRAIN_FIXTURES_L2 = ['train_static_lr_d8_L2', 'train_contrast_ll_d16_L2']  # --n_layers 2
 
 

@@ -442,6 +442,11 @@ int attn_dims_ok(const tg_model* m) {
   if (!m || m->d <= 0 || (m->d % 4) || m->d_e <= 0 || (m->d_e % 4) || m->n_neighbors <= 0) return 0;
   if (m->n_neighbors > TG_WAVE) return 0;  // one key per lane in k_attn_core
   if (m->n_head <= 0 || (2 * m->d) % m->n_head || ((2 * m->d / m->n_head) % 4)) return 0;
+  // the k_attn_core instances (launch_attn_core): 1, 2 or 4 heads; rows of max(d, d_e) <= 256 floats in one float4 per
+  // lane, up to 512 in two - the latter for 2 heads only.  Refused here, in every workspace query, before any launch.
+  const int wmax = std::max(m->d, m->d_e);
+  if (m->n_head != 1 && m->n_head != 2 && m->n_head != 4) return 0;
+  if (wmax > 2 * 4 * TG_WAVE || (wmax > 4 * TG_WAVE && m->n_head != 2)) return 0;
   return 1;
 }
 

@@ -821,6 +821,41 @@ int tg_adam_step(const tg_adam_seg* segs_dev, int32_t n_segs, int32_t n_groups, 
 int tg_ap_auc(int64_t n, int32_t chunk, const float* pos_pred, const float* neg_pred, double* ap, double* auc,
               int32_t* n_nonfinite, void* stream);
 
+/* sklearn's roc_auc_score(labels, scores) over the whole [n] array, ties included (midrank).  labels: [n] float32,
+ * > 0.5 is the positive class.  *auc: one double on device; NaN when either class has no finite score (sklearn
+ * raises there).  Non-finite scores are left out and counted in *n_nonfinite (nullable, device int32, not reset
+ * here).  ws: tg_roc_auc_workspace_bytes(n) bytes, n < 2^31.  Deterministic (integer counts). */
+size_t tg_roc_auc_workspace_bytes(int64_t n);
+int tg_roc_auc(int64_t n, const float* scores, const float* labels, double* auc, int32_t* n_nonfinite, void* ws,
+               size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Node-classification decoder (tiger/model/basic_modules.py:22-33 MLP):      */
+/* y = fn.6(drop(relu(fn.3(drop(relu(fn.0(x))))))), widths d -> 80 -> 10 -> 1 */
+/* ------------------------------------------------------------------------- */
+#define TG_DECODER_MAX_D 512
+typedef struct tg_decoder {
+  float* w1; /* [80, d]  (fn.0) */
+  float* b1; /* [80] */
+  float* w2; /* [10, 80] (fn.3) */
+  float* b2; /* [10] */
+  float* w3; /* [1, 10]  (fn.6) */
+  float* b3; /* [1] */
+} tg_decoder;
+/* Forward of n rows x [n, d] (d a multiple of 4, at most TG_DECODER_MAX_D) -> logits y [n], one launch.  Dropout
+ * (torch's inverted form, probability dropout_p < 1) after both ReLUs when dropout_p > 0, masks drawn from the
+ * counter-based generator at rng = device {seed, counter} (not advanced here).  z1 [n, 80] / z2 [n, 10] (nullable):
+ * the pre-activations, which the backward needs. */
+int tg_decoder_fwd(int64_t n, const float* x, int32_t d, const tg_decoder* w, float dropout_p, const uint64_t* rng,
+                   float* y, float* z1, float* z2, void* stream);
+/* Its backward from dy [n], the forward's z1 / z2 and the same dropout_p / rng (the masks are regenerated): every
+ * gradient of `grads` is overwritten (not accumulated); dx [n, d] nullable.  Two launches, deterministic (no float
+ * atomics: per-workgroup partials summed in a fixed order). */
+size_t tg_decoder_bwd_workspace_bytes(int64_t n, int32_t d);
+int tg_decoder_bwd(int64_t n, const float* x, int32_t d, const tg_decoder* w, float dropout_p, const uint64_t* rng,
+                   const float* z1, const float* z2, const float* dy, const tg_decoder* grads, float* dx, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */

@@ -135,6 +135,11 @@ class TgTrainIo(C.Structure):
     ]
 
 
+class TgDecoder(C.Structure):
+    """tiger_hip.h: tg_decoder - the node-classification MLP's three layers (weights, or their gradients)"""
+    _fields_ = [('w1', vp), ('b1', vp), ('w2', vp), ('b2', vp), ('w3', vp), ('b3', vp)]
+
+
 class TgAdamSeg(C.Structure):
     _fields_ = [('p', vp), ('g', vp), ('m', vp), ('v', vp), ('n', i64), ('group', i32), ('grad_scale', C.c_float)]
 
@@ -227,6 +232,11 @@ SIGNATURES = {
     'tg_attn_tile_applies': (C.c_int, [P(TgModel)]),
     'tg_attn_gtab_rows': (C.c_int, [P(TgModel), i64, vp, vp, vp, sz, vp]),
     'tg_ap_auc': (C.c_int, [i64, i32, vp, vp, vp, vp, vp, vp]),
+    'tg_roc_auc_workspace_bytes': (sz, [i64]),
+    'tg_roc_auc': (C.c_int, [i64, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_decoder_fwd': (C.c_int, [i64, vp, i32, P(TgDecoder), C.c_float, vp, vp, vp, vp, vp]),
+    'tg_decoder_bwd_workspace_bytes': (sz, [i64, i32]),
+    'tg_decoder_bwd': (C.c_int, [i64, vp, i32, P(TgDecoder), C.c_float, vp, vp, vp, vp, P(TgDecoder), vp, vp, sz, vp]),
     'tg_stream_writeback_workspace_bytes': (sz, [P(TgModel), i64]),
     'tg_stream_writeback': (C.c_int, [P(TgModel), P(TgWritebackIo), vp, sz, vp]),
 }

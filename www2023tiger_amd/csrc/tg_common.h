@@ -229,7 +229,7 @@ struct DropCfg {
   uint32_t thresh;      // p * 2^32
   const uint64_t* rng;  // device: {seed, step counter}
 };
-enum { DROP_ATTN = 1, DROP_SCORE = 2, DROP_SEQ_ATTN = 3, DROP_SEQ_MERGER = 4 };
+enum { DROP_ATTN = 1, DROP_SCORE = 2, DROP_SEQ_ATTN = 3, DROP_SEQ_MERGER = 4, DROP_DEC1 = 5, DROP_DEC2 = 6 };
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du;
   x ^= x >> 15; x *= 0x846ca68bu;

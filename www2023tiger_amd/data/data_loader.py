@@ -351,6 +351,31 @@ def load_jodie_data(name: str, train_seed: int, *, root='.', data_seed=2020, val
             subset(in_val & touches_unseen, 1, True), subset(in_test & touches_unseen, 3, True))
 
 
+def load_jodie_data_for_node_task(name: str, train_seed: int, use_validation: bool = False, *, root='.', data_seed=2020,
+                                  val_p=0.7, test_p=0.85):
+    """data_loader.py:407-461: preprocessed JODIE files -> (nfeats, efeats, full, train, val, test) for node
+    classification.  Chronological split at the val_p / test_p time quantiles, no held-out nodes.  Without
+    `use_validation` training runs up to the test time and the validation split holds the test split's events (as
+    in the reference, with its own negative stream: seed 0 against the test split's 2).  `data_seed` draws nothing
+    here (the reference seeds python `random` and never samples from it); it stays for the signature."""
+    frame, efeats, nfeats = _read_jodie_tables(root, name)
+    src, dst, ts = frame.u.values, frame.i.values, frame.ts.values
+    eids, labels = frame.idx.values, frame.label.values
+    cols = (src, dst, ts, eids, labels)
+    t_val, t_test = (float(q) for q in np.quantile(frame.ts, [val_p, test_p]))
+
+    def subset(mask, seed, eval_mode):
+        return InteractionData(*(c[mask] for c in cols), seed=seed, eval=eval_mode)
+
+    in_test = ts > t_test
+    if use_validation:
+        in_train, in_val = ts <= t_val, (ts > t_val) & (ts <= t_test)
+    else:
+        in_train, in_val = ts <= t_test, in_test
+    return (nfeats, efeats, InteractionData(*cols),
+            subset(in_train, train_seed, False), subset(in_val, 0, True), subset(in_test, 2, True))
+
+
 def compute_delta_std(srcs: np.ndarray, dsts: np.ndarray, ts: np.ndarray) -> float:
     """data_loader.py:464-478: std of the time since each endpoint's previous event (first event: since 0)."""
     last = {}

@@ -1,9 +1,8 @@
-"""Mirror of tiger/eval_utils.py for the link-prediction path: `eval_edge_prediction`
-(eval_utils.py:15-68) and `warmup` (eval_utils.py:102-129).  The model forward is the same
-device path as in training; scores stay on the GPU until the end, where AP / AUC per window of
-`mean_over_n_samples` events come from one kernel (`tg_ap_auc`) instead of sklearn round trips.
-Node classification and trajectory encoding (eval_utils.py:71-99,132-183) are downstream tasks
-outside the scope table."""
+"""Mirror of tiger/eval_utils.py: `eval_edge_prediction` (eval_utils.py:15-68), `eval_node_classification`
+(eval_utils.py:71-99) and `warmup` (eval_utils.py:102-129).  The model forward is the same device path as in
+training; scores stay on the GPU until the end, where AP / AUC per window of `mean_over_n_samples` events come from
+one kernel (`tg_ap_auc`), and the node-classification AUC over the whole split from another (`tg_roc_auc`), instead
+of sklearn round trips.  Trajectory encoding (eval_utils.py:132-183) is a downstream task outside the scope table."""
 import math
 import os
 import warnings
@@ -29,6 +28,28 @@ def ap_auc_windows(pos_pred: torch.Tensor, neg_pred: torch.Tensor, window: int =
     check(lib.tg_ap_auc(n, window, ptr(pos_pred), ptr(neg_pred), ptr(ap), ptr(auc), ptr(bad), stream_ptr(dev)),
           'tg_ap_auc')
     return ap, auc, bad
+
+
+def roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
+    """sklearn's roc_auc_score(labels, scores) over the whole array on the device (tg_roc_auc), one read-back.  Raises
+    ValueError, as sklearn does, when a score is not finite or only one class is present."""
+    dev = scores.device
+    scores = scores.float().contiguous()
+    labels = labels.to(device=dev, dtype=torch.float32).contiguous()
+    n = scores.numel()
+    if labels.numel() != n:
+        raise ValueError(f'{labels.numel()} labels for {n} scores')
+    ws = torch.empty(int(lib.tg_roc_auc_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    out = torch.zeros(16, dtype=torch.uint8, device=dev)  # [auc: double | non-finite count: int32 | pad]
+    check(lib.tg_roc_auc(n, ptr(scores), ptr(labels), ptr(out), ptr(out) + 8, ptr(ws), ws.numel(), stream_ptr(dev)),
+          'tg_roc_auc')
+    host = out.cpu()
+    auc, bad = float(host[:8].view(torch.float64)), int(host[8:12].view(torch.int32))
+    if bad:
+        raise ValueError(f'Input contains {bad} non-finite scores.')
+    if math.isnan(auc):
+        raise ValueError('Only one class present in y_true. ROC AUC score is not defined in that case.')
+    return auc
 
 
 def _lazy_restart(model, comp_graph, ts, uptodate_nodes: set, device):
@@ -64,7 +85,8 @@ def _resident_plan(model, dl, restart_mode: bool):
     return (lo, hi, graph) if hi > lo and dl.batch_size > 0 else None
 
 
-def _eval_resident(model, dl, plan, mean_over_n_samples: int, restart_mode: bool = False, uptodate_nodes: Optional[set] = None):
+def _eval_resident(model, dl, plan, mean_over_n_samples: int, restart_mode: bool = False, uptodate_nodes: Optional[set] = None,
+                   on_batch=None):
     """eval_edge_prediction's loop (eval_utils.py:29-57) over a RESIDENT stream: the loader's event columns and
     negatives are uploaded once, every batch is one `tg_train_step` call without gradient buffers - the very call
     `contrast_learning` makes per batch under no_grad - that reads its rows at a device-side offset and leaves its
@@ -94,7 +116,7 @@ def _eval_resident(model, dl, plan, mean_over_n_samples: int, restart_mode: bool
             if not had[1]:
                 model.fuse_attention(True)
         return _eval_resident_run(model, ds, bs, dev, N, lo, hi, graph, TrainBuffers, lean=stream_form,
-                                  restart_mode=restart_mode, uptodate_nodes=uptodate_nodes)
+                                  restart_mode=restart_mode, uptodate_nodes=uptodate_nodes, on_batch=on_batch)
     finally:
         if stream_form and not all(had):
             if not had[0]:
@@ -395,7 +417,10 @@ class _RestartRun:
         self._keep = (ctx, offsets, host, rows, fwd_ws, run)  # (alive until the caller's read-back has drained the stream)
 
 
-def _eval_resident_run(model, ds, bs, dev, N, lo, hi, graph, TrainBuffers, lean, restart_mode=False, uptodate_nodes=None):
+def _eval_resident_run(model, ds, bs, dev, N, lo, hi, graph, TrainBuffers, lean, restart_mode=False, uptodate_nodes=None,
+                       on_batch=None):
+    """on_batch (nullable): called as on_batch(tb, row) after each step's launch - the step's embeddings are in tb.sb.h,
+    `row` is the batch's first event within the pass (a hook for work that reads them on the same stream)"""
     c = getattr(ds, '_dev', None)
     if c is not None and c['device'] == dev:
         src, dst, ts64, eids = (c[k][lo:hi] for k in ('src', 'dst', 'ts', 'eids'))
@@ -472,6 +497,8 @@ def _eval_resident_run(model, ds, bs, dev, N, lo, hi, graph, TrainBuffers, lean,
             elif restart_mode and not tb._restart_in_step:
                 _restart_listed(model, tb, graph)
             tb.launch(graph=graph)
+            if on_batch is not None:
+                on_batch(tb, first + k * B)
             if k == 0 and count > 8:  # one early read-back: the updater's launches are sized by the counts seen so far
                 cnt = tb.sb.counts.tolist()
                 model.note_rows(cnt[1], cnt[2])
@@ -524,6 +551,53 @@ def eval_edge_prediction(model, dl, device: torch.device, restart_mode: bool, up
     if int(bad.item()):
         warnings.warn(f'Encounter invalid values: {int(bad.item())} non-finite predictions were dropped')
     return float(ap.mean().item()), float(auc.mean().item())
+
+
+def _decode_resident(encoder, decoder, dl, plan):
+    """eval_node_classification's loop over a RESIDENT stream (_eval_resident, the same steps as eval_edge_prediction's
+    pass): after each step a tg_decoder_fwd launch reads the batch's source embeddings (tb.sb.h[:B]) and writes their
+    logits into place in an [N] column; the labels are uploaded once; one tg_roc_auc at the end."""
+    from .model.basic_modules import decoder_forward
+    lo, hi, _ = plan
+    dev = encoder.device
+    logits = torch.empty(hi - lo, dtype=torch.float32, device=dev)
+    params = tuple(t.contiguous() for t in decoder.params())
+
+    def decode(tb, row):
+        decoder_forward(params, tb.sb.h[:tb.B], logits[row:row + tb.B])
+
+    _eval_resident(encoder, dl, plan, 200, False, None, on_batch=decode)
+    labels = torch.from_numpy(np.ascontiguousarray(dl.dataset.labels[lo:hi], dtype=np.float32)).to(dev)
+    return logits, labels
+
+
+def eval_node_classification(encoder, decoder, dl, device: torch.device) -> float:
+    """eval_utils.py:71-99: sklearn's roc_auc_score of sigmoid(decoder(h_src)) against the events' labels over the
+    whole loader.  A BatchLoader that the link-prediction pass would stream resident (_resident_plan) with an MLP decoder
+    on the encoder's device takes that stream with the decoder as a per-batch hook; anything else the literal loop."""
+    from .model.basic_modules import MLP
+    encoder.eval()
+    decoder.eval()
+    plan = _resident_plan(encoder, dl, False)
+    if plan is not None and isinstance(decoder, MLP) and decoder.kernel_takes(encoder.nfeat_dim, encoder.device):
+        with torch.no_grad():
+            encoder._poll_train_errors()
+            logits, labels = _decode_resident(encoder, decoder, dl, plan)
+            return roc_auc(logits.sigmoid_(), labels)
+    preds, trues = [], []
+    with torch.no_grad():
+        for src_ids, dst_ids, neg_dst_ids, ts, eids, labels, comp_graph in BackgroundThreadGenerator(dl):
+            bs = len(src_ids)
+            src_ids, dst_ids, neg_dst_ids = (x.long().to(device) for x in (src_ids, dst_ids, neg_dst_ids))
+            ts, eids = ts.float().to(device), eids.long().to(device)
+            comp_graph.to(device)
+            _, h, *_ = encoder.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
+            preds.append(decoder(h[:bs]).sigmoid())
+            trues.append(torch.as_tensor(labels))
+    encoder._poll_train_errors()
+    if not preds:
+        raise ValueError('eval_node_classification: the loader yielded no batch')
+    return roc_auc(torch.cat([p.reshape(-1).to(device) for p in preds]), torch.cat(trues).to(device))
 
 
 def warmup(model, dl, device: torch.device, uptodate_nodes: Optional[set] = None):

@@ -132,6 +132,58 @@ int tg_hits(int64_t B, int32_t K, const int64_t* center, const int64_t* nbr, flo
 int tg_anonymized_reindex(int64_t n, int32_t H, const int64_t* hist_nids, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Historical / inductive negative sampling (replaces AdversarialEdgeSampler's */
+/* sample_hist / sample_ind, tiger/data/adversarial.py:36-50,72-100)           */
+/* ------------------------------------------------------------------------- */
+/* Pair index over a T-CSR of a TIME-ORDERED stream, aligned with its 2E entries.  For an entry e of node s seen from
+ * the source side (eid bit 31 clear, so s -> d = nbr[e]):
+ *   next_ts[e]  = time of the next entry of the same ordered pair (s, d) in T-CSR order, +inf if there is none;
+ *   first_ts[e] = time of the pair's first entry.
+ * Entries seen from the destination side hold -inf in both.  For t0 <= t1, d is a `hist` candidate of s (the set
+ * {d : s->d at ts <= t0} - {d : s->d at t0 <= ts <= t1}, adversarial.py:41-44,72-77) exactly when some entry e of s
+ * has ts[e] < t0 and next_ts[e] > t1 - at most one entry per pair does; `ind` (adversarial.py:87-92) adds
+ * first_ts[e] > ts_hist_end. */
+typedef struct tg_adv_index {
+  const double* next_ts;  /* [num_entry] */
+  const double* first_ts; /* [num_entry] */
+} tg_adv_index;
+
+/* Host build: g holds HOST pointers; next_ts_host / first_ts_host [g->num_entry]. */
+int tg_adv_index_build_host(const tg_tcsr* g, double* next_ts_host, double* first_ts_host);
+/* Device build (same values, bit for bit): two stable radix sorts of the entries, on the neighbour and then on the
+ * owner, and one pass over the sorted order.  g holds DEVICE pointers; num_entry < 2^32. */
+size_t tg_adv_index_build_device_workspace_bytes(int64_t num_entry, int64_t num_node);
+int tg_adv_index_build_device(const tg_tcsr* g, double* next_ts, double* first_ts, void* ws, size_t ws_bytes,
+                              void* stream);
+
+#define TG_ADV_HIST 0
+#define TG_ADV_IND 1
+/* One negative destination per query (adversarial.py:72-100): query q asks for source srcs[q] in the window
+ * [t0[q], t1[q]].  The candidates are the T-CSR entries e of srcs[q] that pass the predicate above (mode TG_ADV_HIST
+ * or TG_ADV_IND with ts_hist_end), in ascending entry order; with `count` of them
+ *   count > 0:  out_dst[q] = nbr[e_k],  k = mulhi32(tg_adv_hash(seed, counter, q, 7), count)
+ *   count == 0: out_dst[q] = dst_distinct[mulhi32(tg_adv_hash(seed, counter, q, 8), n_dst_distinct)]
+ * where mulhi32(h, c) = (h * c) >> 32 in 64-bit arithmetic and, with mix32 as for dropout (x ^= x >> 16;
+ * x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16; all uint32):
+ *   tg_adv_hash(seed, counter, q, s):  k = seed ^ (counter * 0x9E3779B97F4A7C15)        (uint64)
+ *                                      h = mix32(lo32(q) ^ lo32(k))
+ *                                      h = mix32(h + hi32(q) * 0x9e3779b9 + hi32(k))
+ *                                      return mix32(h ^ (s * 0x85ebca6b))
+ * Ids outside [0, num_node) have no entries (count 0).  out_count (nullable) receives count.  One wavefront per
+ * query.  All arrays are DEVICE pointers; the device entry cannot inspect t0 / t1, so a query with t0 > t1 (or a NaN)
+ * gets out_dst = -1 and count -1 there, while the host twin returns TG_EINVAL.  TG_EINVAL also for a bad mode,
+ * n_dst_distinct outside [1, 2^32) and n < 0. */
+int tg_adv_neg_sample(const tg_tcsr* g, const tg_adv_index* ix, int64_t n, const int64_t* srcs, const double* t0,
+                      const double* t1, int32_t mode, double ts_hist_end, const int64_t* dst_distinct,
+                      int64_t n_dst_distinct, uint64_t seed, uint64_t counter, int64_t* out_dst, int64_t* out_count,
+                      void* stream);
+/* The same on the host (g, ix and every array HOST pointers); identical outputs. */
+int tg_adv_neg_sample_host(const tg_tcsr* g, const tg_adv_index* ix, int64_t n, const int64_t* srcs_host,
+                           const double* t0_host, const double* t1_host, int32_t mode, double ts_hist_end,
+                           const int64_t* dst_distinct_host, int64_t n_dst_distinct, uint64_t seed, uint64_t counter,
+                           int64_t* out_dst_host, int64_t* out_count_host);
+
+/* ------------------------------------------------------------------------- */
 /* Sorted-unique compaction on an n-node bitmap                               */
 /* ------------------------------------------------------------------------- */
 /* number of uint64 words of a bitmap over n_nodes ids */

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TIGER_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libtiger_hip.so')  # override: experiments only
 
 TG_OK, TG_EINVAL, TG_EUNSUPPORTED, TG_EWORKSPACE, TG_EHIP = 0, -1, -2, -3, -4
+TG_ADV_HIST, TG_ADV_IND = 0, 1  # tg_adv_neg_sample modes
 ERR_PAST_MEMORY, ERR_DUPLICATE_IDS, ERR_UNUSED_MESSAGE = 1, 2, 4
 ERR_MSG_BEFORE_MEM, ERR_MSG_TS_MISMATCH, ERR_EVENT_BEFORE_MEM = 8, 16, 32
 
@@ -32,6 +33,11 @@ vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 
 class TgTcsr(C.Structure):
     _fields_ = [('num_node', i64), ('num_entry', i64), ('indptr', vp), ('ts', vp), ('nbr', vp), ('eid', vp)]
+
+
+class TgAdvIndex(C.Structure):
+    """tiger_hip.h: tg_adv_index - the pair index of historical / inductive negative sampling"""
+    _fields_ = [('next_ts', vp), ('first_ts', vp)]
 
 
 class TgLinear(C.Structure):
@@ -157,6 +163,13 @@ SIGNATURES = {
     'tg_sample_recent_edges': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     'tg_sample_recent_nodes': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp]),
     'tg_sample_uniform': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    'tg_adv_index_build_host': (C.c_int, [P(TgTcsr), vp, vp]),
+    'tg_adv_index_build_device_workspace_bytes': (sz, [i64, i64]),
+    'tg_adv_index_build_device': (C.c_int, [P(TgTcsr), vp, vp, vp, sz, vp]),
+    'tg_adv_neg_sample': (C.c_int, [P(TgTcsr), P(TgAdvIndex), i64, vp, vp, vp, i32, C.c_double, vp, i64, C.c_uint64,
+                                    C.c_uint64, vp, vp, vp]),
+    'tg_adv_neg_sample_host': (C.c_int, [P(TgTcsr), P(TgAdvIndex), i64, vp, vp, vp, i32, C.c_double, vp, i64, C.c_uint64,
+                                         C.c_uint64, vp, vp]),
     'tg_hits': (C.c_int, [i64, i32, vp, vp, vp, vp]),
     'tg_anonymized_reindex': (C.c_int, [i64, i32, vp, vp, vp]),
     'tg_bitmap_words': (i64, [i64]),

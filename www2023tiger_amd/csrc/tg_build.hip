@@ -182,6 +182,34 @@ __global__ void k_tcsr_fill(uint32_t P, const uint32_t* __restrict__ order, cons
   }
 }
 
+// Stable LSD radix sort of P (key, value) pairs on the low `bits` bits of the keys (a multiple of 4), with the pass
+// kernels above reading an arbitrary key array.  (k, v) and (k_alt, v_alt) are ping-pong buffers of P entries each;
+// the sorted pairs end in (k, v) when bits / 4 is even, else in (k_alt, v_alt) - the pointers are swapped to say which.
+// Scratch: radix_sort_scratch_bytes(P).  Internal (tg_adv.hip).
+size_t radix_sort_scratch_bytes(uint32_t P) {
+  const size_t nblocks = ((size_t)P + RS_TILE - 1) / RS_TILE;
+  return align16(16 * nblocks * 4) + align16(scan_scratch_elems((int64_t)(16 * nblocks)) * 4);
+}
+int radix_sort_pairs(uint32_t P, int bits, uint32_t*& k, uint32_t*& v, uint32_t*& k_alt, uint32_t*& v_alt, void* scratch,
+                     size_t scratch_bytes, hipStream_t st) {
+  if (P == 0) return TG_OK;
+  const uint32_t nblocks = (P + RS_TILE - 1) / RS_TILE;
+  Carver cv(scratch, scratch_bytes);
+  uint32_t* hist = cv.take<uint32_t>((size_t)16 * nblocks);
+  uint32_t* hscr = cv.take<uint32_t>(scan_scratch_elems((int64_t)16 * nblocks));
+  if (!cv.ok) return TG_EWORKSPACE;
+  for (int shift = 0; shift < bits; shift += 4) {
+    hipLaunchKernelGGL(k_rs_count<false>, dim3(nblocks), dim3(RS_THREADS), 0, st, P, k, nullptr, nullptr, shift, hist,
+                       nblocks);
+    exclusive_scan<uint32_t>(hist, (int64_t)16 * nblocks, hscr, st);
+    hipLaunchKernelGGL(k_rs_scatter<false>, dim3(nblocks), dim3(RS_THREADS), 0, st, P, k, v, nullptr, nullptr, shift,
+                       hist, nblocks, k_alt, v_alt);
+    std::swap(k, k_alt);
+    std::swap(v, v_alt);
+  }
+  return check_launch("radix_sort_pairs");
+}
+
 }  // namespace tg
 
 using namespace tg;

@@ -269,6 +269,11 @@ __device__ __forceinline__ uint64_t orderable(float x) {
 
 
 // ---- internal launchers shared between translation units (not part of the C ABI) ----
+// stable LSD radix sort of (key, value) pairs on the low `bits` key bits (tg_build.hip; the sorted pairs are left in
+// whichever pair of buffers (k, v) points at on return)
+size_t radix_sort_scratch_bytes(uint32_t P);
+int radix_sort_pairs(uint32_t P, int bits, uint32_t*& k, uint32_t*& v, uint32_t*& k_alt, uint32_t*& v_alt, void* scratch,
+                     size_t scratch_bytes, hipStream_t st);
 // sampler with the batch -> query expansion fused in (data_loader.py:79-81,92,128)
 struct CentresRider;
 int sample_batch_launch(const tg_tcsr* g, int64_t B, const int64_t* src, const int64_t* dst, const int64_t* neg,

@@ -491,7 +491,7 @@ int attn_tile_applies(const tg_model* m) {
   // against 76; C5 shape 3.98 ms against 2.97) - a 16-centre tile needs 32 B/clk of weights per CU at full matrix rate
   // and a CU pulls 13-16 B/clk of L2-resident lines here, while the 64-row tiles of the separate products need a quarter
   // of that and their G / S round trip costs less than it saves (profiles/r03_attn_tile_phase_trace.txt)
-  static const int knob = getenv("TG_ATTN_TILE") ? atoi(getenv("TG_ATTN_TILE")) : 0;
+  static const int knob = env_int("TG_ATTN_TILE", 0);
   return (knob != 0 && tile_waves(m) != 0 && !m->row_of) ? 1 : 0;
 }
 
@@ -507,11 +507,11 @@ int attn_tile_launch(const tg_model* m, int64_t Q, const float* cc, const float*
   a.pos = pos ? *pos : PosArgs{};
   a.zeros = zero_line();
   if (!a.zeros) return TG_EHIP;
-  static const int dbg_knob = getenv("TG_TILE_DBG") ? atoi(getenv("TG_TILE_DBG")) : 0;
+  static const int dbg_knob = env_int("TG_TILE_DBG", 0);
   a.dbg = dbg_knob;
   // tiles of 12 centres (12 wavefronts) while they need no more rounds of 256 workgroups than tiles of 16 would: the
   // matrix work of a workgroup is that of a 16-row tile either way, so below that point more CUs share the centres
-  static const int mc_knob = getenv("TG_ATTN_TILE_MC") ? atoi(getenv("TG_ATTN_TILE_MC")) : 0;
+  static const int mc_knob = env_int("TG_ATTN_TILE_MC", 0);
   const bool twelve = mc_knob ? mc_knob == 12 : cdiv(cdiv(Q, 12), 256) <= cdiv(cdiv(Q, 16), 256);
   const size_t lds = tile_lds_bytes(a.t, twelve ? 12 : 8);
   const int W = std::max(a.t.d, a.t.de) <= 128 ? 2 : 4;  // narrow rows: two columns per lane fill more lanes (as k_attn_core)

@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
 #include "tiger_hip.h"
 
 #define TG_WAVE 64
@@ -22,6 +24,14 @@ inline int check_launch(const char* what) {
 }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Integer environment knob (TG_...; the list: tools/README.md).  Call sites keep the value in a function-local static, so a
+// knob is read once per process, at first use.  (static: the cold call sites do not inline it, and the out-of-line copy of
+// a plain inline function would be one more exported symbol of the library)
+static inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // ---- kernel-bound timing (tg_profiler, eager launches only) ----------------------------------------------------------
 // A HIP-event pair AROUND a launch measures the launch plus the two event records (~4.5 us on this stack); an event pair

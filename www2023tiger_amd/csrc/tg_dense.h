@@ -155,9 +155,9 @@ struct GruArgs {
   int x_skip_at, x_skip_n;
 };
 
-int gru_launch(const GruArgs& g, hipStream_t st);
+int gru_launch(const GruArgs& g, hipStream_t st);  // (tg_gru.hip)
 
-// Weight-gradient GEMM: out[n, k] (+)= alpha * sum_m Y[m, n] * X[m, k], X = [x0 | x1] with optional
+// Weight-gradient GEMM (tg_gemm_tn.hip): out[n, k] (+)= alpha * sum_m Y[m, n] * X[m, k], X = [x0 | x1] with optional
 // row gathers, m < *m_dev (<= m_cap).  The M extent is split over blocks; partial tiles go to
 // `part` ([splits, nbatch, N, K] floats, plain stores) and a second launch reduces them in a
 // fixed order (deterministic, no float atomics).

@@ -451,7 +451,7 @@ int attn_dims_ok(const tg_model* m) {
 }
 
 static int gru_split_knob() {
-  static const int k = getenv("TG_GRU_SPLIT") ? atoi(getenv("TG_GRU_SPLIT")) : 0;  // tuning knob (0 = off, the default)
+  static const int k = env_int("TG_GRU_SPLIT", 0);  // tuning knob (0 = off, the default)
   return k;
 }
 static bool carve_attn(const tg_model* m, int64_t Q, Carver& cv, AttnWs& w) {
@@ -514,13 +514,13 @@ void launch_attn_core(const tg_model* m, int64_t Q, const float* ts, const int64
   const int wmax = std::max(d, d_e);
   int W = 4, nv = (int)cdiv(cdiv(wmax, 4), TG_WAVE);
   {
-    static const int w_knob = getenv("TG_ATTN_W") ? atoi(getenv("TG_ATTN_W")) : 0;  // tuning knob: 4 forces float4 lanes
+    static const int w_knob = env_int("TG_ATTN_W", 0);  // tuning knob: 4 forces float4 lanes
     // narrow rows (d <= 128, e.g. LastFM's --dim 100): two columns per lane instead of four fill 50 lanes instead of 25;
     // the kernel is bound by per-key VALU work and latency there, not by bytes (8-byte accesses stay sector aligned)
     if (wmax <= 128 && w_knob != 4) { W = 2; nv = 1; }
   }
   const unsigned cgrid = flat_grid(Q, 4);
-  static const int core_dbg = getenv("TG_CORE_DBG") ? atoi(getenv("TG_CORE_DBG")) : 0;  // diagnostic: s_memtime stamps (tools/trace_core.py)
+  static const int core_dbg = env_int("TG_CORE_DBG", 0);  // diagnostic: s_memtime stamps (tools/trace_core.py)
   if (core_dbg) direct |= 256;
   const float* zl = zero_line();
   if (!zl) { *rc_out = TG_EHIP; return; }
@@ -568,8 +568,7 @@ struct SideLane {
   bool ok = false;
 };
 static SideLane* side_lane(hipStream_t st) {
-  const char* knob = getenv("TG_SIDE_STREAM");  // tuning knob (read per call; default off, see above)
-  if (!knob || atoi(knob) == 0) return nullptr;
+  if (env_int("TG_SIDE_STREAM", 0) == 0) return nullptr;  // tuning knob (read per call; default off, see above)
   static SideLane lanes[16];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
@@ -1392,7 +1391,7 @@ static StepForm step_form(const tg_model* m, const tg_step_io* io, bool eager, b
   const tg_lazy_restart* lz = (io->lazy && !io->embed_only) ? io->lazy : nullptr;
   // eager updates, direct form (default; TG_EAGER_DIRECT=0 keeps the compact copy): centres and neighbour rows are read
   // from pending / right themselves, so there is no gather launch and no reprs buffer
-  static const int direct_knob = getenv("TG_EAGER_DIRECT") ? atoi(getenv("TG_EAGER_DIRECT")) : 1;
+  static const int direct_knob = env_int("TG_EAGER_DIRECT", 1);
   f.direct = eager && direct_knob != 0 && !io->eager_copy && !io->collate_only;
   // the one-launch write-back needs the snapshot; the restarter targets (h_prev_*) are read between STEP 4 and STEP 6,
   // so a step that outputs them keeps the two-phase write-back
@@ -1449,7 +1448,7 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   }
   // write-back rider (tg_common.h: WbRider): STEP 4-5 share the launch of the attention block's last product, whose
   // epilogue stores STEP 6's rows; TG_WB_RIDER=0 keeps the write-back launch
-  static const int wbr_knob = getenv("TG_WB_RIDER") ? atoi(getenv("TG_WB_RIDER")) : 1;
+  static const int wbr_knob = env_int("TG_WB_RIDER", 1);
   // (not with io->h_new: those rows are read from the tables after the attention block, i.e. before STEP 4 must run)
   const bool want_rider = w.fused_wb && wbr_knob != 0 && !drop && !io->h_new;
   if (want_rider) pos.win_row = w.win_row;
@@ -1470,7 +1469,7 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   w.gtab = form.gtab;
   // collate prefetch (tg_step_io.prefetch_state): this step runs the NEXT batch's sampler + centres on its last launch;
   // `prefetched`: the previous call did that for this batch (a repeated collate would be harmless, just wasted)
-  static const int pf_knob = getenv("TG_PREFETCH") ? atoi(getenv("TG_PREFETCH")) : 1;
+  static const int pf_knob = env_int("TG_PREFETCH", 1);
   w.prefetch = pf_knob != 0 && io->prefetch_state && io->stream_len > 0 && io->offset_dev && io->advance && io->ws_is_clean &&
                w.lean && w.gtab && w.fused_wb && !lz && io->strategy == 0 && K <= 16 && !io->l1_nids && !io->l1_eids && !io->l1_ts &&
                // (large batches: the last product's launch takes no riders, see gemm_launch - the sampler half then runs on
@@ -1610,7 +1609,7 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
     if (gs.variant == 2) {  // the tail behind fc2, reading what the reference reads: left[v] and weight_hh / bias_hh
       t.direct = 1; t.t = m->left_vals; t.t_rows = w.upos; t.w = m->gru_w_hh; t.b = m->gru_b_hh;
       // ... and W_ih msg over the mailbox rows the write-back rider has just stored (on fc1's launch)
-      static const int box_knob = getenv("TG_GRU_SPLIT_BOX") ? atoi(getenv("TG_GRU_SPLIT_BOX")) : 1;
+      static const int box_knob = env_int("TG_GRU_SPLIT_BOX", 1);
       if (box_knob) {
         gi.a0 = ASeg{m->msg_vals, mw, mw, w.upos};
         gi.a1 = gi.a2 = gi.a3 = ASeg{};
@@ -1620,7 +1619,7 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   // collate prefetch: TG_PREFETCH_SPLIT=1 lets the sampler half of the NEXT batch's collate share fc2's launch (it reads the
   // graph and the stream only) and leaves the centres on the step's last launch.  Parity-green, measured SLOWER at C2 (87.2
   // against 85.2 us per step on the same box: fc2's launch grows by more than the last launch gives back); default 0
-  static const int pfs_knob = getenv("TG_PREFETCH_SPLIT") ? atoi(getenv("TG_PREFETCH_SPLIT")) : 0;
+  static const int pfs_knob = env_int("TG_PREFETCH_SPLIT", 0);
   CollateRider co_s{};
   if (w.prefetch && pfs_knob != 0 && !gsplit) {
     co_s.s = SampleBatchArgs{*g, io->B, io->src, io->dst, io->neg, io->ts, io->eids, (const int64_t*)io->offset_dev,

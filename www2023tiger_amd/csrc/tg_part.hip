@@ -151,7 +151,7 @@ extern "C" int tg_part_step(const tg_model* m, const tg_tcsr* g, const tg_step_i
   wa.B = p->Bg; wa.src = p->st_src; wa.dst = p->st_dst; wa.eids = p->st_eids; wa.upos = p->st_mine_node; wa.index = p->st_mine_index;
   wa.ts = p->st_ts32; wa.n_upos = p->st_n_mine; wa.err = io->err;
   wa.rows = io->h; wa.left_row = p->st_left_row; wa.owner = p->owner; wa.my_rank = p->rank; wa.new_from_pending = 1;
-  static const int ride_knob = getenv("TG_PART_WB_RIDER") ? atoi(getenv("TG_PART_WB_RIDER")) : 1;  // tuning knob: 0 = own launch
+  static const int ride_knob = env_int("TG_PART_WB_RIDER", 1);  // tuning knob: 0 = own launch
   WbRider wr{};
   wr.m = *m; wr.a = wa; wr.planned0 = 1;
   bool rode = false;

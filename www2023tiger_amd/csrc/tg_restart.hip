@@ -1284,7 +1284,7 @@ int mutual_step(const tg_model* m, const tg_tcsr* g, const tg_step_io* sio, cons
     // histories of 33 .. 64 events: the two row classes are two launches over the same grid that write disjoint rows - the
     // many short blocks of the 32-row class on the lane (when there is one) beside the few long ones of the 64-row class
     // (TG_SEQ_BWD_SPLIT=0: one after the other on the main stream)
-    static const int split_knob = getenv("TG_SEQ_BWD_SPLIT") ? atoi(getenv("TG_SEQ_BWD_SPLIT")) : 1;  // tuning knob
+    static const int split_knob = env_int("TG_SEQ_BWD_SPLIT", 1);  // tuning knob
     hipStream_t s32 = st;
     bool forked = false;
     if (H > 32 && side_ok && split_knob && side->used + 5 <= side->n && side->after_main(st)) {

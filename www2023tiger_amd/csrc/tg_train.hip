@@ -1059,7 +1059,7 @@ struct TrainLane {
   bool ok = false;
 };
 static TrainLane* train_lane(hipStream_t st) {
-  static const int knob = getenv("TG_TRAIN_SIDE") ? atoi(getenv("TG_TRAIN_SIDE")) : 1;  // tuning knob
+  static const int knob = env_int("TG_TRAIN_SIDE", 1);  // tuning knob
   if (!knob) return nullptr;
   static TrainLane lanes[16];
   int dev = 0;
@@ -1145,7 +1145,7 @@ extern "C" int tg_train_step(const tg_model* m_in, const tg_tcsr* g, const tg_tr
   // the SeqRestarter's forward runs beside the contrast half on a second stream.  It needs the batch's id list and nothing
   // else of the forward pass: the fork is recorded INSIDE step_forward, right behind the sampler's launch, so the lane's
   // 0.6 ms overlap the forward pass as well as the backward (TG_TRAIN_FORK=0: fork behind the whole forward pass)
-  static const int fork_knob = getenv("TG_TRAIN_FORK") ? atoi(getenv("TG_TRAIN_FORK")) : 1;  // tuning knob
+  static const int fork_knob = env_int("TG_TRAIN_FORK", 1);  // tuning knob
   TrainLane* lane = seq ? train_lane(st) : nullptr;
   if (lane && fork_knob) w.collate_done = lane->fork;
   if ((rc = step_forward(m, g, sio, w, t.gates, st, nullptr, &dc)) != TG_OK) return rc;

@@ -1,4 +1,4 @@
-"""Standalone dense entry points (float32 MFMA kernels of csrc/tg_gemm.hip)."""
+"""Standalone dense entry points (float32 MFMA kernels of csrc/tg_gemm.hip, tg_gru.hip and tg_gemm_tn.hip)."""
 import ctypes as C
 
 import torch

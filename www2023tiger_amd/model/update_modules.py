@@ -1,6 +1,6 @@
 """Memory updaters (reference: tiger/model/update_modules.py).  Parameter containers only: the
 attribute names (`cell`, `fn`) are what the reference's state_dict uses; inside the engine
-the update runs as tg_apply_messages (fused float32-MFMA GRU, csrc/tg_gemm.hip).  Calling a
+the update runs as tg_apply_messages (fused float32-MFMA GRU, csrc/tg_gru.hip).  Calling a
 module directly runs the same kernels on dense rows."""
 from torch import Tensor, nn
 

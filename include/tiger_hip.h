@@ -909,6 +909,35 @@ int tg_decoder_bwd(int64_t n, const float* x, int32_t d, const tg_decoder* w, fl
                    size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Trajectory encoding (replaces the per-event loops of encode_trajectory,    */
+/* tiger/eval_utils.py:158-178, and its final division, eval_utils.py:180-181) */
+/* ------------------------------------------------------------------------- */
+#define TG_TRAJ_LAST 0 /* agg == 'last': the row is assigned */
+#define TG_TRAJ_MAX 1  /* agg == 'max': elementwise maximum with the stored row (numpy's: a NaN propagates) */
+#define TG_TRAJ_SUM 2  /* any other agg ('mean', 'sum', ...): a source row is ADDED, a destination row ASSIGNED */
+#define TG_TRAJ_ERR_BAD_ID 1u /* bit of *err: an id outside [0, n_nodes) was met (and skipped) */
+/* One batch folded into the per-node table (eval_utils.py:160-178), one launch.  h: [2B, d] float32, rows 0..B-1 the
+ * sources' embeddings, rows B..2B-1 the destinations'.  The applied sequence is the sources in index order (use_src != 0),
+ * then the destinations in index order (use_dst != 0); for each position, with id its node: table[id, :] (float64
+ * [n_nodes, d]) takes the row as `mode` says and counts[id] (float64 [n_nodes]) grows by one.  The result is bit for bit
+ * that of the sequential loop: one wavefront per position, the wave of a node's first position applies all of the node's
+ * positions in order in registers (no atomics, deterministic); any B, any d.  src / dst: int64 id columns, read at element
+ * offset *offset_dev when offset_dev != NULL (a resident stream's columns; the offset is read on the device).  Ids outside
+ * [0, n_nodes) set TG_TRAJ_ERR_BAD_ID in *err (device uint32, not reset here) and are skipped: nothing is stored for them.
+ * TG_EINVAL for B < 0, d <= 0, n_nodes <= 0 or an unknown mode. */
+int tg_trajectory_accumulate(int64_t B, int32_t d, const float* h, const int64_t* src, const int64_t* dst,
+                             const int64_t* offset_dev, int32_t mode, int32_t use_src, int32_t use_dst, int64_t n_nodes,
+                             double* table, double* counts, uint32_t* err, void* stream);
+/* agg == 'mean' only (eval_utils.py:180-181): table[n, :] /= counts[n] + 1e-7 (IEEE float64 division). */
+int tg_trajectory_finish(int64_t n_nodes, int32_t d, double* table, const double* counts, void* stream);
+/* The same on the host (every pointer a HOST pointer): the sequential loop itself; identical outputs. */
+int tg_trajectory_accumulate_host(int64_t B, int32_t d, const float* h_host, const int64_t* src_host,
+                                  const int64_t* dst_host, const int64_t* offset_host, int32_t mode, int32_t use_src,
+                                  int32_t use_dst, int64_t n_nodes, double* table_host, double* counts_host,
+                                  uint32_t* err_host);
+int tg_trajectory_finish_host(int64_t n_nodes, int32_t d, double* table_host, const double* counts_host);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */
 /* the global batch, the embeddings having been computed on other ranks)      */

@@ -1,8 +1,9 @@
 """Mirror of tiger/eval_utils.py: `eval_edge_prediction` (eval_utils.py:15-68), `eval_node_classification`
-(eval_utils.py:71-99) and `warmup` (eval_utils.py:102-129).  The model forward is the same device path as in
-training; scores stay on the GPU until the end, where AP / AUC per window of `mean_over_n_samples` events come from
-one kernel (`tg_ap_auc`), and the node-classification AUC over the whole split from another (`tg_roc_auc`), instead
-of sklearn round trips.  Trajectory encoding (eval_utils.py:132-183) is a downstream task outside the scope table."""
+(eval_utils.py:71-99), `warmup` (eval_utils.py:102-129) and `encode_trajectory` (eval_utils.py:132-183).  The model
+forward is the same device path as in training; scores stay on the GPU until the end, where AP / AUC per window of
+`mean_over_n_samples` events come from one kernel (`tg_ap_auc`), and the node-classification AUC over the whole split
+from another (`tg_roc_auc`), instead of sklearn round trips.  The trajectory table is folded on the device, one
+launch per batch (`tg_trajectory_accumulate`), and read back once."""
 import math
 import os
 import warnings
@@ -619,3 +620,70 @@ def warmup(model, dl, device: torch.device, uptodate_nodes: Optional[set] = None
             model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
     model._poll_train_errors()
     return uptodate_nodes
+
+
+class _Trajectory:
+    """The float64 table / counts of encode_trajectory on the device and the per-batch launch that folds a step's
+    embeddings into them (tiger_hip.h: tg_trajectory_accumulate)."""
+
+    def __init__(self, model, agg: str, use_src: bool, use_dst: bool):
+        from ._lib import TG_TRAJ_LAST, TG_TRAJ_MAX, TG_TRAJ_SUM
+        dev = model.device
+        self.n_nodes, self.d, self.dev = int(model.n_nodes), int(model.nfeat_dim), dev
+        self.mode = {'last': TG_TRAJ_LAST, 'max': TG_TRAJ_MAX}.get(agg, TG_TRAJ_SUM)
+        self.use_src, self.use_dst = int(bool(use_src)), int(bool(use_dst))
+        self.table = torch.zeros(self.n_nodes, self.d, dtype=torch.float64, device=dev)
+        self.counts = torch.zeros(self.n_nodes, dtype=torch.float64, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def add(self, B: int, h: torch.Tensor, src_ptr: int, dst_ptr: int):
+        """h: [>= 2B, d] float32 contiguous on the device; src_ptr / dst_ptr: the batch's int64 id columns there"""
+        assert h.dtype == torch.float32 and h.is_contiguous() and h.shape[1] == self.d and h.shape[0] >= 2 * B
+        check(lib.tg_trajectory_accumulate(B, self.d, ptr(h), src_ptr, dst_ptr, None, self.mode, self.use_src, self.use_dst,
+                                           self.n_nodes, ptr(self.table), ptr(self.counts), ptr(self.err), stream_ptr(self.dev)),
+              'tg_trajectory_accumulate')
+
+    def finish(self, mean: bool) -> torch.Tensor:
+        if int(self.err.item()):
+            raise ValueError(f'encode_trajectory: a node id lies outside [0, {self.n_nodes})')
+        if mean:
+            check(lib.tg_trajectory_finish(self.n_nodes, self.d, ptr(self.table), ptr(self.counts), stream_ptr(self.dev)),
+                  'tg_trajectory_finish')
+        return self.table
+
+
+def encode_trajectory(model, dl, device: torch.device, agg: str, use_src: bool = True, use_dst: bool = True, *,
+                      as_tensor: bool = False):
+    """eval_utils.py:132-183: stream the loader through the model from an empty state (model.reset(), no restarts) and
+    fold every event's source / destination embedding into one float64 row per node -> [n_nodes, nfeat_dim].  Per batch
+    the sources are applied in index order (if `use_src`), then the destinations (if `use_dst`): 'last' assigns the
+    row, 'max' takes the elementwise maximum with the stored row (the table starts at zero, so no entry is negative),
+    any other `agg` ADDS a source row but ASSIGNS a destination row - the reference's asymmetry, kept because tables
+    are compared checkpoint for checkpoint with its output - and 'mean' alone divides by `count + 1e-7` at the end.
+    The table lives on the device: one launch per batch behind the step (a per-batch hook of the resident stream where
+    _resident_plan takes the loader, the per-batch loop otherwise), one read-back at the end; `as_tensor=True` returns
+    the device tensor instead of a numpy array."""
+    model.eval()
+    model.reset()
+    traj = _Trajectory(model, agg, use_src, use_dst)
+    plan = _resident_plan(model, dl, False)
+    with torch.no_grad():
+        if plan is not None:
+            model._poll_train_errors()
+
+            def fold(tb, row):
+                traj.add(tb.B, tb.sb.h, tb.sb.src.data_ptr() + 8 * row, tb.sb.dst.data_ptr() + 8 * row)
+
+            _eval_resident(model, dl, plan, 200, False, None, on_batch=fold)
+        else:
+            for src_ids, dst_ids, neg_dst_ids, ts, eids, _, comp_graph in BackgroundThreadGenerator(dl):
+                bs = len(src_ids)
+                src_ids, dst_ids, neg_dst_ids = (x.long().to(device) for x in (src_ids, dst_ids, neg_dst_ids))
+                ts, eids = ts.float().to(device), eids.long().to(device)
+                comp_graph.to(device)
+                _, h, *_ = model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
+                src_ids, dst_ids = src_ids.contiguous(), dst_ids.contiguous()
+                traj.add(bs, h.float().contiguous(), ptr(src_ids), ptr(dst_ids))
+            model._poll_train_errors()
+        table = traj.finish(agg == 'mean')
+    return table if as_tensor else table.cpu().numpy()

@@ -8,6 +8,10 @@ test), written against this package's mirror of the reference API.
 --neg_sample hist / ind evaluates the test splits on the historical / inductive negatives of AdversarialEdgeSampler
 (Poursafaei et al., NeurIPS 2022) instead of random ones; training and validation keep random negatives.
 
+--rank C (off by default) adds the one-vs-many protocol after testing: every test event's destination is ranked against C
+candidate destinations drawn by the sampler --neg_sample selects (rnd: RandEdgeSampler, hist / ind:
+AdversarialEdgeSampler), seed RANK_SEED; MRR and Hits@1/3/10 are printed for the transductive and the inductive split.
+
 Only `run()` matters; the few flags exist to make the file runnable.
 """
 import argparse
@@ -20,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from www2023tiger_amd.data.adversarial import AdversarialEdgeSampler  # noqa: E402
 from www2023tiger_amd.data.data_loader import BatchLoader, InteractionData  # noqa: E402
-from www2023tiger_amd.eval_utils import eval_edge_prediction, warmup  # noqa: E402
+from www2023tiger_amd.eval_utils import eval_edge_prediction, eval_edge_ranking, warmup  # noqa: E402
 from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
 from www2023tiger_amd.optim import Adam  # noqa: E402  (torch.optim.Adam works too; this one never stalls the loop)
 
@@ -75,9 +79,38 @@ def adversarial_test_loaders(neg_sample, full_data, full_graph, test_dl, ind_tes
     return mk(test, neg), mk(ind, neg[np.isin(test.eids, ind.eids)])
 
 
+RANK_SEED = 2023  # --rank: the seed of the candidate draws (column j is drawn with RANK_SEED + j)
+
+
+def rank_candidates(neg_sample, n_cand, full_data, full_graph, test):
+    """[len(test), n_cand] candidate destinations of the test events: column j is one pre-sampled negative stream of
+    the sampler `neg_sample` selects, seeded RANK_SEED + j"""
+    cols = []
+    for j in range(n_cand):
+        if neg_sample == 'rnd':
+            cols.append(InteractionData(test.src, test.dst, test.ts, test.eids, test.labels, seed=RANK_SEED + j, eval=True).neg_dst)
+        else:
+            adv = AdversarialEdgeSampler(full_data.src, full_data.dst, full_data.ts, test.src, test.ts, neg_sample,
+                                         seed=RANK_SEED + j, graph=full_graph)
+            cols.append(adv.pre_sample_neg_dsts(len(test)))
+    return np.stack(cols, 1).astype(np.int64)
+
+
+def rank_pair(model, dl, ind_dl, device, cand):
+    """eval_edge_ranking over the transductive then the inductive test split from the same memory state (as
+    evaluate_pair); the inductive events keep the candidates of their events"""
+    start = model.save_memory_state()
+    out = eval_edge_ranking(model, dl, device, cand)
+    end = model.save_memory_state()
+    model.load_memory_state(start)
+    ind = eval_edge_ranking(model, ind_dl, device, cand[np.isin(dl.dataset.eids, ind_dl.dataset.eids)])
+    model.load_memory_state(end)
+    return out, ind
+
+
 def run(data, root, *, seed=0, n_epochs=1, bs=200, lr=1e-4, dim=None, n_neighbors=10, n_heads=2, hit_type='bin',
         restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', restart_prob=0.01, mutual_coef=1.0,
-        warmup_steps=0, strategy='recent_edges', dropout=0.1, ckpt_path=None, neg_sample='rnd', device='cuda:0'):
+        warmup_steps=0, strategy='recent_edges', dropout=0.1, ckpt_path=None, neg_sample='rnd', rank=0, device='cuda:0'):
     device = torch.device(device)
     torch.manual_seed(seed)
     rng = np.random.RandomState(seed)
@@ -123,8 +156,20 @@ def run(data, root, *, seed=0, n_epochs=1, bs=200, lr=1e-4, dim=None, n_neighbor
         model.msg_store.clear()
         if warmup_steps:
             uptodate = warmup(model, test_warm_dl, device)
+    before_test = model.save_memory_state() if rank > 0 else None
     test = evaluate_pair(model, test_dl, ind_test_dl, device, restart_mode, uptodate)
-    return dict(epochs=log, test_ap=test[0], test_auc=test[1], ind_test_ap=test[2], ind_test_auc=test[3]), model
+    out = dict(epochs=log, test_ap=test[0], test_auc=test[1], ind_test_ap=test[2], ind_test_auc=test[3])
+    if rank > 0:  # one-vs-many over the same test events, from the state the test started from (no restarts: see eval_edge_ranking)
+        after_test = model.save_memory_state()
+        model.load_memory_state(before_test)
+        cand = rank_candidates(neg_sample, rank, full_data, full_graph, test_dl.dataset)
+        r, ind_r = rank_pair(model, test_dl, ind_test_dl, device, cand)
+        model.load_memory_state(after_test)
+        for name, m in (('test', r), ('ind_test', ind_r)):
+            out.update({f'{name}_mrr': m['mrr'], **{f'{name}_hits@{k}': v for k, v in m['hits'].items()}})
+            print(f"{name}: MRR {m['mrr']:.4f}  " + '  '.join(f'Hits@{k} {v:.4f}' for k, v in m['hits'].items())
+                  + f"  ({m['n_events']} events, {rank} {neg_sample} candidates)")
+    return out, model
 
 
 if __name__ == '__main__':
@@ -138,7 +183,9 @@ if __name__ == '__main__':
     ap.add_argument('--restart_prob', type=float, default=0.01)
     ap.add_argument('--dropout', type=float, default=0.1)
     ap.add_argument('--neg_sample', default='rnd', choices=['rnd', 'hist', 'ind'])
+    ap.add_argument('--rank', type=int, default=0, metavar='C',
+                    help='after testing: MRR / Hits@1/3/10 against C candidates per test event (0: off)')
     a = ap.parse_args()
     out, _ = run(a.data, a.root, n_epochs=a.n_epochs, bs=a.bs, lr=a.lr, restarter_type=a.restarter_type,
-                 restart_prob=a.restart_prob, dropout=a.dropout, neg_sample=a.neg_sample)
+                 restart_prob=a.restart_prob, dropout=a.dropout, neg_sample=a.neg_sample, rank=a.rank)
     print(out)

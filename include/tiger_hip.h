@@ -938,6 +938,46 @@ int tg_trajectory_accumulate_host(int64_t B, int32_t d, const float* h_host, con
 int tg_trajectory_finish_host(int64_t n_nodes, int32_t d, double* table_host, const double* counts_host);
 
 /* ------------------------------------------------------------------------- */
+/* Ranking evaluation, one-vs-many (no reference counterpart: the score head   */
+/* of tiger.py:257-288 with data_loader.py:61-75's hit features, applied to C  */
+/* candidate destinations per event; MRR / Hits@k as DGB / TGB report them)    */
+/* ------------------------------------------------------------------------- */
+/* scores [B, 1 + C] of the pairs (src_i, cand_ids[i, j]); column 0 is the true destination.  score = fc2(relu(fc1([xp | yp])))
+ * with the hit features of the PAIR: with nbr_src [B, K] / nbr_cand [B, 1 + C, K] the recent-edges neighbour ids of the
+ * source and of the candidate queries at the event's time, src hits = (nbr_cand[i, j, :] == src[i]), dst hits =
+ * (nbr_src[i, :] == cand_ids[i, j]); 'bin' / 'count' add hit_emb[max / sum of the hits] to x / y, 'vec' appends the K hits,
+ * 'none' uses neither (the four id arrays may then be NULL).  h_src [B, d] / h_cand [B, 1 + C, d]: the queries' embeddings.
+ * fc1's product is split by operand: the source half once per event, the hit embedding's rows once per class, the
+ * B (1 + C)-row candidate half on the float32 MFMA path with the rest of the head (ReLU, fc2, its bias) applied to the
+ * accumulators - neither the hidden rows nor the concatenated pair rows are written.  Three launches (two without
+ * 'bin' / 'count'), deterministic; a pair's score does not depend on its position: equal pairs give equal bits.
+ * ws: tg_rank_scores_workspace_bytes(B, d, sp) bytes.  B (1 + C) < 2^31.  TG_EUNSUPPORTED: 'vec' with 2 (d + K) not a
+ * multiple of 4, as the one-call evaluation step refuses it. */
+size_t tg_rank_scores_workspace_bytes(int64_t B, int32_t d, const tg_score_params* sp);
+int tg_rank_scores(int64_t B, int32_t C, int32_t d, int32_t K, const tg_score_params* sp, const float* h_src,
+                   const float* h_cand, const int64_t* nbr_src, const int64_t* nbr_cand, const int64_t* src,
+                   const int64_t* cand_ids, float* scores, void* ws, size_t ws_bytes, void* stream);
+
+/* Rank of the true destination among the candidates LEFT IN: candidate j >= 1 of event i is left out when
+ * cand_ids[i, j] == dst[i], when cand_ids[i, j] == 0 (the padding id) or when mask != NULL and mask[i, j - 1] == 0
+ * (mask: uint8 [B, C]).  Per event (int32 [B] each, rank float64 [B]): n_greater / n_equal = candidates left in whose
+ * score is > / == the positive's (float32 comparison of the stored scores, no tolerance), n_valid = candidates left in,
+ * rank = 1 + n_greater + n_equal / 2 (the mean of the optimistic and the pessimistic rank; 1 when nothing is left in).
+ * Accumulated (+=) into the caller's accumulators, which the caller zeroes once per pass: acc_f64 [1 + TG_RANK_MAX_K] =
+ * {sum of 1 / rank, sum of [rank <= ks_host[q]] for q < n_ks}; acc_i64 [2] = {events, non-finite scores met among the
+ * positives and the candidates left in}.  ks_host: n_ks <= TG_RANK_MAX_K positive cut-offs, read on the host.  One
+ * wavefront per event, then one wavefront folds the ranks in a fixed order: deterministic.  Two launches. */
+#define TG_RANK_MAX_K 8
+int tg_rank_stats(int64_t B, int32_t C, const float* scores, const int64_t* cand_ids, const int64_t* dst,
+                  const uint8_t* mask, int32_t n_ks, const int32_t* ks_host, int32_t* n_greater, int32_t* n_equal,
+                  int32_t* n_valid, double* rank, double* acc_f64, int64_t* acc_i64, void* stream);
+/* The same arithmetic on the host (every pointer a HOST pointer; events folded in index order). */
+int tg_rank_stats_host(int64_t B, int32_t C, const float* scores_host, const int64_t* cand_ids_host,
+                       const int64_t* dst_host, const uint8_t* mask_host, int32_t n_ks, const int32_t* ks_host,
+                       int32_t* n_greater_host, int32_t* n_equal_host, int32_t* n_valid_host, double* rank_host,
+                       double* acc_f64_host, int64_t* acc_i64_host);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */
 /* the global batch, the embeddings having been computed on other ranks)      */

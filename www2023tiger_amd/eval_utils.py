@@ -1,5 +1,6 @@
 """Mirror of tiger/eval_utils.py: `eval_edge_prediction` (eval_utils.py:15-68), `eval_node_classification`
-(eval_utils.py:71-99), `warmup` (eval_utils.py:102-129) and `encode_trajectory` (eval_utils.py:132-183).  The model
+(eval_utils.py:71-99), `warmup` (eval_utils.py:102-129) and `encode_trajectory` (eval_utils.py:132-183); beside them
+`eval_edge_ranking`, the one-vs-many protocol (MRR / Hits@k) the reference does not have.  The model
 forward is the same device path as in training; scores stay on the GPU until the end, where AP / AUC per window of
 `mean_over_n_samples` events come from one kernel (`tg_ap_auc`), and the node-classification AUC over the whole split
 from another (`tg_roc_auc`), instead of sklearn round trips.  The trajectory table is folded on the device, one
@@ -552,6 +553,62 @@ def eval_edge_prediction(model, dl, device: torch.device, restart_mode: bool, up
     if int(bad.item()):
         warnings.warn(f'Encounter invalid values: {int(bad.item())} non-finite predictions were dropped')
     return float(ap.mean().item()), float(auc.mean().item())
+
+
+def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 10), restart_mode: bool = False, mask=None,
+                      chunk_queries: int = 65536, return_ranks: bool = False) -> dict:
+    """One-vs-many link evaluation (the DGB / TGB protocol; no counterpart in the reference's eval_utils): every event's
+    true destination is ranked against its candidates by the scores of the state BEFORE its batch, then the batch runs as
+    in `eval_edge_prediction` (contrast_learning), so the state advances exactly as there.  -> dict(mrr, hits {k: value},
+    n_events[, ranks float64 [n_events]]).
+    candidates: int64 [n_events, C] aligned with the loader's events in order, or [C] shared by all; mask likewise
+    (bool, false = leave the candidate out).  A candidate equal to the event's destination or to the padding id 0 is left
+    out as well.  rank = 1 + #greater + #equal / 2 over the candidates left in; MRR = mean 1 / rank, Hits@k =
+    mean [rank <= k].  Scores come from TIGE.rank_scores, counts and sums from tg_rank_stats, folded on the device with
+    one read-back at the end; a non-finite score raises ValueError.  Refused: restart_mode (lazy restarts would have to
+    cover the candidates' neighbourhoods), and whatever TIGE.rank_scores refuses (strategy 'uniform', partitioned models)."""
+    from . import hip_ops
+    if restart_mode:
+        raise NotImplementedError('eval_edge_ranking: restart mode is not built (the lazy restarts of eval_edge_prediction '
+                                  "cover the batch's own neighbourhoods, not the candidates')")
+    model._refuse_partitioned('eval_edge_ranking')
+    model.eval()
+    ks = tuple(int(k) for k in ks)
+    cand = torch.as_tensor(candidates).long().to(device)
+    if cand.dim() not in (1, 2):
+        raise ValueError('candidates: int64 [n_events, C] or [C]')
+    if mask is not None:
+        mask = torch.as_tensor(mask).to(device).bool()
+        if mask.dim() != cand.dim() or (mask.dim() == 1 and mask.shape != cand.shape):
+            raise ValueError('mask must have the shape of candidates')
+    graph = getattr(getattr(dl, 'collate_fn', None), 'graph', None)
+    acc = hip_ops.new_rank_acc(device)
+    ranks, row = [], 0
+    with torch.no_grad():
+        for src_ids, dst_ids, neg_dst_ids, ts, eids, _, comp_graph in BackgroundThreadGenerator(dl):
+            src_ids, dst_ids, neg_dst_ids = (x.long().to(device) for x in (src_ids, dst_ids, neg_dst_ids))
+            ts, eids = ts.float().to(device), eids.long().to(device)
+            comp_graph.to(device)
+            B = len(src_ids)
+            if cand.dim() == 2 and row + B > cand.shape[0]:
+                raise ValueError(f'candidates has {cand.shape[0]} rows, the loader more events')
+            c = cand.unsqueeze(0).expand(B, -1) if cand.dim() == 1 else cand[row:row + B]
+            mk = None if mask is None else (mask.unsqueeze(0).expand(B, -1) if mask.dim() == 1 else mask[row:row + B])
+            ts64 = getattr(comp_graph, 'ts64', None)
+            g = graph if graph is not None else getattr(comp_graph, 'graph', None)
+            scores = model.rank_scores(src_ids, dst_ids, ts if ts64 is None else ts64, c, chunk_queries=chunk_queries, graph=g)
+            st = hip_ops.rank_stats(scores, torch.cat([dst_ids[:, None], c], 1), dst_ids, mask=mk, ks=ks, acc=acc)
+            if return_ranks:
+                ranks.append(st['rank'])
+            model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
+            row += B
+    model._poll_train_errors()
+    if cand.dim() == 2 and row != cand.shape[0]:
+        raise ValueError(f'candidates has {cand.shape[0]} rows, the loader {row} events')
+    out = hip_ops.rank_metrics(acc, ks)
+    if return_ranks:
+        out['ranks'] = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.float64, device=device)
+    return out
 
 
 def _decode_resident(encoder, decoder, dl, plan):

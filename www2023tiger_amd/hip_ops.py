@@ -157,3 +157,56 @@ def memory_scatter(table: Tensor, ts_table: Tensor, active: Optional[Tensor], id
     check(lib.tg_memory_scatter(ids.numel(), None, ptr(ids), ptr(src_index), table.shape[1], ptr(vals), ptr(ts),
                                 ptr(table), ptr(ts_table), ptr(active), 1 if check_past else 0, ptr(err),
                                 stream_ptr(table.device)), 'tg_memory_scatter')
+
+
+# ---- ranking evaluation (tg_rank_stats / tg_rank_stats_host) --------------------------------------------------------------
+def new_rank_acc(device) -> Tuple[Tensor, Tensor]:
+    """zeroed accumulators of one ranking pass: float64 [1 + TG_RANK_MAX_K] = {sum 1/rank, sum [rank <= k] per cut-off},
+    int64 [2] = {events, non-finite scores}"""
+    return (torch.zeros(1 + _lib.TG_RANK_MAX_K, dtype=torch.float64, device=device),
+            torch.zeros(2, dtype=torch.int64, device=device))
+
+
+def rank_stats(scores: Tensor, cand_ids: Tensor, dst: Tensor, *, mask: Optional[Tensor] = None, ks=(1, 3, 10), acc=None):
+    """Rank of column 0 of scores [B, 1 + C] among the candidates left in (tiger_hip.h: tg_rank_stats): candidate j is left
+    out when cand_ids[i, j] == dst[i], when it is the padding id 0, or when mask[i, j - 1] is false (mask: [B, C]).
+    -> dict(n_greater, n_equal, n_valid: int32 [B]; rank: float64 [B]; acc: the (float64, int64) accumulators of
+    `new_rank_acc`, to which this batch was added - pass them back in to fold a whole split).  Device tensors take the
+    device entry, host tensors the host twin: same arithmetic."""
+    dev = scores.device
+    scores = scores.float().contiguous()
+    B, C1 = scores.shape
+    cand_ids, dst = _i64(cand_ids.to(dev)), _i64(dst.to(dev))
+    if cand_ids.shape != (B, C1) or dst.shape != (B,):
+        raise ValueError(f'rank_stats: scores {tuple(scores.shape)}, cand_ids {tuple(cand_ids.shape)}, dst {tuple(dst.shape)}')
+    if mask is not None:
+        mask = mask.to(dev).to(torch.uint8).contiguous()
+        if mask.shape != (B, C1 - 1):
+            raise ValueError(f'rank_stats: mask {tuple(mask.shape)} for {C1 - 1} candidates of {B} events')
+    ks = [int(k) for k in ks]
+    if len(ks) > _lib.TG_RANK_MAX_K or any(k < 1 for k in ks):
+        raise ValueError(f'rank_stats: at most {_lib.TG_RANK_MAX_K} positive cut-offs')
+    ks_host = torch.tensor(ks, dtype=torch.int32)
+    acc = new_rank_acc(dev) if acc is None else acc
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(n_greater=torch.zeros(B, **i32), n_equal=torch.zeros(B, **i32), n_valid=torch.zeros(B, **i32),
+               rank=torch.ones(B, dtype=torch.float64, device=dev), acc=acc)
+    args = (B, C1 - 1, ptr(scores), ptr(cand_ids), ptr(dst), ptr(mask), len(ks), ptr(ks_host), ptr(out['n_greater']),
+            ptr(out['n_equal']), ptr(out['n_valid']), ptr(out['rank']), ptr(acc[0]), ptr(acc[1]))
+    if dev.type == 'cpu':
+        check(lib.tg_rank_stats_host(*args), 'tg_rank_stats_host')
+    else:
+        check(lib.tg_rank_stats(*args, stream_ptr(dev)), 'tg_rank_stats')
+    return out
+
+
+def rank_metrics(acc, ks=(1, 3, 10)) -> dict:
+    """One read-back of a pass's accumulators -> dict(mrr, hits {k: value}, n_events).  A non-finite score among the
+    ranked ones raises ValueError."""
+    f, i = acc[0].cpu(), acc[1].cpu()
+    n, bad = int(i[0]), int(i[1])
+    if bad:
+        raise ValueError(f'Input contains {bad} non-finite scores.')
+    nan = float('nan')
+    return dict(mrr=float(f[0]) / n if n else nan, hits={int(k): (float(f[1 + q]) / n if n else nan) for q, k in enumerate(ks)},
+                n_events=n)

@@ -40,6 +40,13 @@ _TSFM = {'id': 0, 'linear': 1, 'mlp': 2}
 _UPD = {'gru': 0, 'merge': 1}
 
 
+class _QueryGraph:
+    """What the embedding reads of a computation graph (layers, involved bitmap), for a flat list of (node, t) queries"""
+
+    def __init__(self, layers, bitmap):
+        self.layers, self.bitmap = layers, bitmap
+
+
 class TIGE(nn.Module):
     _born_rows = None
 
@@ -759,6 +766,95 @@ class TIGE(nn.Module):
             xp = xn = x
             yp, yn = y, neg_y
         return self.score_fn(xp, yp).squeeze(1), self.score_fn(xn, yn).squeeze(1)
+
+    # ---- ranking evaluation (one-vs-many) -------------------------------------------------
+    def rank_scores(self, src_ids: Tensor, dst_ids: Tensor, ts: Tensor, cand: Tensor, *, chunk_queries: int = 65536,
+                    graph=None) -> Tensor:
+        """scores [B, 1 + C] of every event's true destination (column 0) and of its C candidate destinations cand[i, :]
+        on the model's CURRENT state: column 0 is `pos_scores` of contrast_learning on this batch, column 1 + j its
+        `neg_scores` had the negatives been cand[:, j] (tiger.py:174-288) - STEP 1-3 over the flat list of B (2 + C)
+        (node, t) queries on the operator path, the score head over all pairs as one call (tg_rank_scores); STEP 4-6 never
+        run and NOTHING is written: memories, mailbox and derived tables are what they were.  ts: the event times, float64
+        where the caller has them (the sampler searches float64).  cand: int64 [B, C], or [C] shared by all events.
+        Events are processed in chunks of at most `chunk_queries` queries (at least one event), so the workspace is bounded
+        whatever C is; a score does not depend on the chunking.  graph: the graph neighbourhoods are sampled from
+        (default: model.graph; an evaluation loop passes its collator's).  eval() mode only.  Refused before anything
+        runs: strategy 'uniform' (a score would depend on the graph's random stream), a partitioned model, 'vec' hits with
+        2 (d + K) not a multiple of 4 (as the one-call evaluation step)."""
+        from ..data.data_loader import GraphCollator
+        from .training import score_struct
+        self._refuse_partitioned('rank_scores')
+        graph = self.graph if graph is None else graph
+        strategy = getattr(graph, 'strategy', 'recent_edges')
+        if strategy not in ('recent_edges', 'recent_nodes'):
+            raise NotImplementedError(f"rank_scores samples 'recent_edges' or 'recent_nodes'; strategy={strategy!r} would make a "
+                                      "score depend on the graph's random stream")
+        if self.n_layers not in (1, 2):
+            raise NotImplementedError('rank_scores: the operator path embeds with n_layers 1 or 2')
+        d, K, dev = self.memory_dim, self.n_neighbors, self.device
+        if self.hit_type == 'vec' and (2 * (d + K)) % 4:
+            raise NotImplementedError("rank_scores: 'vec' hits need 2 (d + n_neighbors) to be a multiple of 4")
+        if self.training:
+            raise RuntimeError('rank_scores scores the model in eval() mode')
+        if chunk_queries < 1:
+            raise ValueError('chunk_queries must be positive')
+        self.check_graph(graph)
+        src_ids, dst_ids = (x.to(dev).long().contiguous() for x in (src_ids, dst_ids))
+        cand = torch.as_tensor(cand).to(dev).long()
+        B = src_ids.numel()
+        if cand.dim() == 1:
+            cand = cand.unsqueeze(0).expand(B, -1)
+        if cand.dim() != 2 or cand.shape[0] != B or dst_ids.numel() != B or ts.numel() != B:
+            raise ValueError(f'rank_scores: {B} events, dst {tuple(dst_ids.shape)}, ts {tuple(ts.shape)}, cand {tuple(cand.shape)}')
+        ids_all = torch.cat([dst_ids[:, None], cand], 1)
+        if B:
+            lo_id, hi_id = torch.aminmax(torch.cat([src_ids, ids_all.reshape(-1)]))
+            if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
+                raise ValueError('rank_scores: a node id outside [0, n_nodes)')
+        ts64 = ts.to(dev).double().contiguous()
+        C1 = cand.shape[1] + 1
+        scores = torch.empty(B, C1, dtype=torch.float32, device=dev)
+        if B == 0:
+            return scores
+        with torch.no_grad():
+            self._poll_train_errors()
+            # pre-multiplied attention weights follow the parameters, as before a streaming / evaluation step; the eager
+            # update and query-row tables are neither read (the operator path consumes the mailbox itself) nor made stale
+            # (no state changes): they are left exactly as they are
+            if self._fused is not None and self._fused_stamp != self._attn_stamp():
+                self.fuse_attention()
+            coll = GraphCollator(graph, K, self.n_layers)
+            sp = score_struct(self)
+            hits = self.hit_type != 'none'
+            err = hip_ops.new_err(dev)
+            s = stream_ptr(dev)
+            step = max(1, int(chunk_queries) // (C1 + 1))
+            for lo in range(0, B, step):
+                hi = min(B, lo + step)
+                b = hi - lo
+                ids = ids_all[lo:hi].contiguous()
+                nodes = torch.cat([src_ids[lo:hi], ids.reshape(-1)])
+                t64 = torch.cat([ts64[lo:hi], ts64[lo:hi].repeat_interleave(C1)])
+                layers, bitmap, _ = coll.collate_memory_nodes(nodes, t64)
+                Q = nodes.numel()
+                cap = min(Q * (1 + K + (K * K if self.n_layers == 2 else 0)), self.n_nodes)
+                comp, reprs = self._consume(bitmap, cap, err)  # STEP 1-2, read-only
+                cg = _QueryGraph(layers, bitmap)
+                m = self.model_struct()
+                h = self.temporal_embedding_fn.compute_embedding_with_computation_graph(  # STEP 3
+                    reprs, nodes, t64.float(), cg, m if self.n_layers == 1 else self.model_struct, comp['rank'])
+                nb_src = nb_cand = None
+                if hits:  # hit windows are recent-edges lists whatever the graph's strategy (data_loader.py:61-75)
+                    nb = layers[-1][0] if strategy == 'recent_edges' else graph.sample_device(
+                        nodes, t64, K, strategy='recent_edges', want_dirs=False)[0]
+                    nb_src, nb_cand = nb[:b], nb[b:]
+                nbytes = int(lib.tg_rank_scores_workspace_bytes(b, d, C.byref(sp)))
+                ws = self._ws('rank', nbytes)
+                out = scores[lo:hi]
+                check(lib.tg_rank_scores(b, C1 - 1, d, K, C.byref(sp), ptr(h[:b]), ptr(h[b:]), ptr(nb_src), ptr(nb_cand),
+                                         ptr(nodes[:b]), ptr(ids), ptr(out), ptr(ws), ws.numel(), s), 'tg_rank_scores')
+            hip_ops.raise_if_err(err)
+        return scores
 
     # ---- fused path ---------------------------------------------------------------------
     class StepBuffers:

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from _rank_ref import numpy_ranks
 from _util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -157,16 +158,6 @@ def assert_same_state(a, b):
         assert torch.equal(a[k], b[k]), k
 
 
-def numpy_ranks(s, ids, dst, mask=None):
-    s0 = s[:, :1]
-    left_in = (ids[:, 1:] != dst[:, None]) & (ids[:, 1:] != 0)
-    if mask is not None:
-        left_in &= mask
-    g = ((s[:, 1:] > s0) & left_in).sum(1)
-    e = ((s[:, 1:] == s0) & left_in).sum(1)
-    return g, e, left_in.sum(1), 1.0 + g.astype(np.float64) + 0.5 * e.astype(np.float64)
-
-
 # ------------------------------------------------------------------------------------------ scores against the oracle
 SHAPES = [  # (d, d_e, K, B, C)
     (16, 16, 10, 5, 7),     # 40 pair rows: neither 32 nor 64
@@ -259,6 +250,30 @@ def test_chunked_equals_unchunked_bit_for_bit():
     assert torch.equal(whole, parts)
     single = c['model'].rank_scores(c['src'], c['dst'], c['ts'], c['cand'], chunk_queries=1)   # one event per chunk
     assert torch.equal(whole, single)
+
+
+def test_chunked_equals_unchunked_where_row_counts_straddle_kernel_choices():
+    """d = 172, 48 events x 301 pairs.  Embedded among its own rows, a one-event chunk (302 queries) would take fc1
+    (k = 3 d = 516) as K-split blocks (tg_gemm.hip: k_gemm_ks16, at most 1100 48-row tiles), the whole call (14 496
+    queries) as plain 64 x 64 blocks that sum k in one order, a 16-event chunk (4 832) in between: other bits.
+    rank_scores embeds every query in a call of RANK_EMBED_ROWS rows, so all three agree bit for bit."""
+    d, K, B, C = 172, 10, 48, 300
+    model, orc, st = build(d, 4, K, 'bin', seed=d + K)
+    warm(model, orc, st, K, with_oracle=False)
+    lo, hi = WARM[-1], WARM[-1] + B
+    src, dst, _, ts, _ = batch(st, lo, hi)
+    cand = np.random.RandomState(11).randint(1, st['n_nodes'], (B, C)).astype(np.int64)
+    t = lambda x, dt=torch.int64: torch.as_tensor(x).to(dev(), dt)
+    src, dst, ts, cand = t(src), t(dst), t(ts, torch.float64), t(cand)
+    R = model.RANK_EMBED_ROWS
+    assert (C + 2) < R < 16 * (C + 2) < B * (C + 2)   # a chunk below one unit, one of two units, a call of four
+    before = state_of(model)
+    whole = model.rank_scores(src, dst, ts, cand)
+    assert torch.isfinite(whole).all() and whole.unique().numel() > B
+    for per_chunk in (1, 16 * (C + 2)):
+        parts = model.rank_scores(src, dst, ts, cand, chunk_queries=per_chunk)
+        assert torch.equal(whole, parts), per_chunk
+    assert_same_state(before, state_of(model))
 
 
 def test_shared_candidates_equal_the_broadcast_form():

@@ -768,6 +768,11 @@ class TIGE(nn.Module):
         return self.score_fn(xp, yp).squeeze(1), self.score_fn(xn, yn).squeeze(1)
 
     # ---- ranking evaluation (one-vs-many) -------------------------------------------------
+    # rows of every embedding call of rank_scores.  The library chooses the kernels of the attention products and of the
+    # updater by the row count (K-split variants for launches that do not fill the chip), so the bits of an embedding
+    # depend on how many rows it was computed among; a fixed count makes a score a function of its pair and the state alone
+    RANK_EMBED_ROWS = 4096
+
     def rank_scores(self, src_ids: Tensor, dst_ids: Tensor, ts: Tensor, cand: Tensor, *, chunk_queries: int = 65536,
                     graph=None) -> Tensor:
         """scores [B, 1 + C] of every event's true destination (column 0) and of its C candidate destinations cand[i, :]
@@ -777,7 +782,8 @@ class TIGE(nn.Module):
         run and NOTHING is written: memories, mailbox and derived tables are what they were.  ts: the event times, float64
         where the caller has them (the sampler searches float64).  cand: int64 [B, C], or [C] shared by all events.
         Events are processed in chunks of at most `chunk_queries` queries (at least one event), so the workspace is bounded
-        whatever C is; a score does not depend on the chunking.  graph: the graph neighbourhoods are sampled from
+        whatever C is; a score does not depend on the chunking, nor on B or C: every query is embedded in a call of
+        exactly RANK_EMBED_ROWS rows (see there).  graph: the graph neighbourhoods are sampled from
         (default: model.graph; an evaluation loop passes its collator's).  eval() mode only.  Refused before anything
         runs: strategy 'uniform' (a score would depend on the graph's random stream), a partitioned model, 'vec' hits with
         2 (d + K) not a multiple of 4 (as the one-call evaluation step)."""
@@ -829,24 +835,40 @@ class TIGE(nn.Module):
             err = hip_ops.new_err(dev)
             s = stream_ptr(dev)
             step = max(1, int(chunk_queries) // (C1 + 1))
+            R = self.RANK_EMBED_ROWS
+            cap = min(R * (1 + K + (K * K if self.n_layers == 2 else 0)), self.n_nodes)
             for lo in range(0, B, step):
                 hi = min(B, lo + step)
                 b = hi - lo
                 ids = ids_all[lo:hi].contiguous()
                 nodes = torch.cat([src_ids[lo:hi], ids.reshape(-1)])
                 t64 = torch.cat([ts64[lo:hi], ts64[lo:hi].repeat_interleave(C1)])
-                layers, bitmap, _ = coll.collate_memory_nodes(nodes, t64)
+                # STEP 1-3 in units of exactly RANK_EMBED_ROWS queries (the last one filled up with copies of its last query)
+                # and one involved-set capacity: the products and the updater pick their kernel - K-split or not - by
+                # the row count, and a K split sums in another order, so a query embedded among another number of rows
+                # could round differently.  Every query now meets the same kernels whatever B, C and chunk_queries are
                 Q = nodes.numel()
-                cap = min(Q * (1 + K + (K * K if self.n_layers == 2 else 0)), self.n_nodes)
-                comp, reprs = self._consume(bitmap, cap, err)  # STEP 1-2, read-only
-                cg = _QueryGraph(layers, bitmap)
-                m = self.model_struct()
-                h = self.temporal_embedding_fn.compute_embedding_with_computation_graph(  # STEP 3
-                    reprs, nodes, t64.float(), cg, m if self.n_layers == 1 else self.model_struct, comp['rank'])
+                h = torch.empty(Q, d, dtype=torch.float32, device=dev)
+                nb = torch.empty(Q, K, dtype=torch.int64, device=dev) if hits else None
+                for off in range(0, Q, R):
+                    n = min(R, Q - off)
+                    qn, qt = nodes[off:off + n], t64[off:off + n]
+                    if n < R:
+                        qn = torch.cat([qn, qn[-1:].expand(R - n)])
+                        qt = torch.cat([qt, qt[-1:].expand(R - n)])
+                    layers, bitmap, _ = coll.collate_memory_nodes(qn.contiguous(), qt.contiguous())
+                    comp, reprs = self._consume(bitmap, cap, err)  # STEP 1-2, read-only
+                    cg = _QueryGraph(layers, bitmap)
+                    m = self.model_struct()
+                    hq = self.temporal_embedding_fn.compute_embedding_with_computation_graph(  # STEP 3
+                        reprs, qn, qt.float(), cg, m if self.n_layers == 1 else self.model_struct, comp['rank'])
+                    h[off:off + n] = hq[:n]
+                    if hits:  # hit windows are recent-edges lists whatever the graph's strategy (data_loader.py:61-75)
+                        nbq = layers[-1][0] if strategy == 'recent_edges' else graph.sample_device(
+                            qn, qt, K, strategy='recent_edges', want_dirs=False)[0]
+                        nb[off:off + n] = nbq[:n]
                 nb_src = nb_cand = None
-                if hits:  # hit windows are recent-edges lists whatever the graph's strategy (data_loader.py:61-75)
-                    nb = layers[-1][0] if strategy == 'recent_edges' else graph.sample_device(
-                        nodes, t64, K, strategy='recent_edges', want_dirs=False)[0]
+                if hits:
                     nb_src, nb_cand = nb[:b], nb[b:]
                 nbytes = int(lib.tg_rank_scores_workspace_bytes(b, d, C.byref(sp)))
                 ws = self._ws('rank', nbytes)

@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Top-k recommendation lists of a trained TIGER model on one MI355X: load a link-prediction checkpoint (its memories are
+those the validation pass left, as when examples/link_prediction.py tests), and for every event of the test split list
+the k best destinations of its source among ALL destination nodes of the dataset, on the state before the event's batch
+(`TIGE.recommend`: the score head over every (source, item) pair, then the device top-k `tg_topk_rows`); the batch then
+streams as in evaluation.  Writes ids.npy [n_test, k] / scores.npy [n_test, k] and prints the line of
+`eval_recommendation` (hit rate, NDCG and MRR of the true destination in those lists).
+
+    python examples/recommend.py --data wikipedia --root /path/with/data --ckpt model.pt --k 10 [--exclude_seen]
+
+Only `run()` matters; the few flags exist to make the file runnable.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from www2023tiger_amd import hip_ops  # noqa: E402
+from www2023tiger_amd.eval_utils import eval_recommendation  # noqa: E402
+from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
+
+
+def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
+        hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
+        device='cuda:0'):
+    """-> (ids [n_test, k], scores [n_test, k], the eval_recommendation dict).  The model settings must be those the
+    checkpoint was trained with (examples/link_prediction.py defaults here)."""
+    device = torch.device(device)
+    torch.manual_seed(seed)
+    basic, (train_graph, full_graph), dls = init_data(
+        data, root, seed, num_workers=0, bs=bs, warmup_steps=0, subset=1.0, strategy=strategy, n_layers=1,
+        n_neighbors=n_neighbors, restarter_type=restarter_type, hist_len=hist_len, device=device)
+    nfeats, efeats, full_data = basic[:3]
+    test_dl = dls[4]
+    model = init_model(nfeats, efeats, train_graph, full_graph, full_data, device, dim=dim, n_layers=1, n_heads=n_heads,
+                       n_neighbors=n_neighbors, hit_type=hit_type, dropout=0.0, restarter_type=restarter_type,
+                       hist_len=hist_len, msg_src=msg_src, upd_src=upd_src, msg_tsfm_type='id', mem_update_type='gru')
+    model.load_state_dict(torch.load(ckpt_path, map_location=device))
+    model.eval()
+    model.graph = full_graph
+    catalogue = torch.from_numpy(np.unique(full_data.dst).astype(np.int64)).to(device)
+    col_of = hip_ops.catalogue_index(catalogue, model.n_nodes)
+    start = model.save_memory_state()
+    ids, scores = [], []
+    with torch.no_grad():  # the lists themselves: the loop of eval_recommendation, keeping what recommend returns
+        for src, dst, neg, ts, eids, _, cg in test_dl:
+            src, dst, neg, eids = (x.long().to(device) for x in (src, dst, neg, eids))
+            cg.to(device)
+            i, s, _ = model.recommend(src, cg.ts64, catalogue, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
+            ids.append(i.cpu().numpy())
+            scores.append(s.cpu().numpy())
+            model.contrast_learning(src, dst, neg, ts.float().to(device), eids, cg)
+    ids, scores = np.concatenate(ids), np.concatenate(scores)
+    np.save(os.path.join(out_dir, 'ids.npy'), ids)
+    np.save(os.path.join(out_dir, 'scores.npy'), scores)
+    model.load_memory_state(start)  # the same pass once more, folded into the metrics
+    out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen)
+    return ids, scores, out
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser(description='Write top-k recommendation lists for the test split of a TIGER checkpoint.')
+    ap.add_argument('-d', '--data', default='wikipedia')
+    ap.add_argument('--root', default='.')
+    ap.add_argument('--ckpt', required=True, help='checkpoint written by examples/link_prediction.py')
+    ap.add_argument('--k', type=int, default=10)
+    ap.add_argument('--exclude_seen', action='store_true', help='leave out the items a source has already interacted with')
+    ap.add_argument('--out_dir', default='.')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--bs', type=int, default=200)
+    ap.add_argument('--restarter_type', default='seq', choices=['seq', 'static'])
+    a = ap.parse_args()
+    ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
+                    restarter_type=a.restarter_type)
+    print(f"test: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "
+          f"coverage {m['coverage']:.4f}  ({m['n_events']} events, {ids.shape[0]} lists written)")

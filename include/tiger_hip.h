@@ -978,6 +978,51 @@ int tg_rank_stats_host(int64_t B, int32_t C, const float* scores_host, const int
                        double* acc_f64_host, int64_t* acc_i64_host);
 
 /* ------------------------------------------------------------------------- */
+/* Top-k recommendation (no reference counterpart): per-row top-k selection    */
+/* over a score matrix with the leave-out rules of tg_rank_stats, and the      */
+/* seen-item filter over the T-CSR                                             */
+/* ------------------------------------------------------------------------- */
+/* The k best columns of every row of scores [B, C] (row stride ld >= C floats).  cand_ids: int64 [B, C], or [C] shared by
+ * all rows when cand_shared != 0; mask: uint8 [B, C] or NULL.
+ * Which columns take part: column j of row i is left out when its candidate id is 0 (the padding id) or when
+ * mask[i, j] == 0.  A remaining column whose score is NaN or +-inf is counted into *n_nonfinite (a += accumulator the
+ * caller zeroes once per pass, like acc_i64 of tg_rank_stats) and left out as well.  n_valid[i] (int32 [B]) = the number
+ * of columns of row i left in after all three rules.
+ * Order (total): higher float32 score first, equal scores in ascending column order.  "Equal" is float32 comparison, so
+ * -0.0 ties +0.0; duplicate candidate ids in a row are separate columns.
+ * out_ids int64 / out_scores float32 / out_cols int32, [B, k] each: position p holds the p-th best column's id, its
+ * score with the stored bits, and its column index; positions p >= min(k, n_valid[i]) hold id 0, score -inf, column -1.
+ * n_seg: the number of column segments a row is split into, one wavefront each (a first launch leaves every segment's
+ * best k in the workspace, a second merges them per row; one launch when a row is one segment); 0: the library
+ * chooses from B, C and k, so that a few long rows still fill the chip.  The result is bit-identical for every n_seg,
+ * n_seg > C included: the order is total.  ws: tg_topk_rows_workspace_bytes(B, C, k, n_seg) bytes (0 when a row is one
+ * segment; ws may then be NULL), 8-byte aligned; a short one returns TG_EWORKSPACE before anything is written.
+ * TG_EINVAL unless 1 <= k <= TG_TOPK_MAX_K, B >= 0, 0 <= C < 2^31, ld >= C, n_seg >= 0, B * max(n_seg, 1) < 2^31.
+ * B == 0 or C == 0 is valid (C == 0: every position is padding). */
+#define TG_TOPK_MAX_K 64
+size_t tg_topk_rows_workspace_bytes(int64_t B, int64_t C, int32_t k, int32_t n_seg);
+int tg_topk_rows(int64_t B, int64_t C, int32_t k, const float* scores, int64_t ld, const int64_t* cand_ids,
+                 int32_t cand_shared, const uint8_t* mask, int32_t n_seg, int64_t* out_ids, float* out_scores,
+                 int32_t* out_cols, int32_t* n_valid, int64_t* n_nonfinite, void* ws, size_t ws_bytes, void* stream);
+/* The same selection on the host (every pointer a HOST pointer; n_seg is validated and otherwise unused). */
+int tg_topk_rows_host(int64_t B, int64_t C, int32_t k, const float* scores_host, int64_t ld,
+                      const int64_t* cand_ids_host, int32_t cand_shared, const uint8_t* mask_host, int32_t n_seg,
+                      int64_t* out_ids_host, float* out_scores_host, int32_t* out_cols_host, int32_t* n_valid_host,
+                      int64_t* n_nonfinite_host);
+
+/* Seen-item filter.  col_of: int32 [g->num_node], the column of a node id in a shared catalogue of C items, -1 when the
+ * node is not in it.  For every event i, mask[i, col_of[nbr]] (uint8 [B, C]) is cleared for each T-CSR entry of src[i]
+ * whose time is < ts[i] - strict float64, the sampler's cut; both edge directions count, as the T-CSR stores them.  The
+ * call ONLY CLEARS bytes: the caller pre-fills mask with ones, or with its own mask.  A source with no entry before
+ * ts[i] clears nothing.  One wavefront per event.  src[i] must lie in [0, num_node): the device entry cannot see the
+ * ids and treats one outside as a node without entries - its caller checks them where they are visible; the host twin
+ * returns TG_EINVAL. */
+int tg_seen_mask(const tg_tcsr* g, int64_t B, const int64_t* src, const double* ts, int64_t C, const int32_t* col_of,
+                 uint8_t* mask, void* stream);
+int tg_seen_mask_host(const tg_tcsr* g, int64_t B, const int64_t* src_host, const double* ts_host, int64_t C,
+                      const int32_t* col_of_host, uint8_t* mask_host);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */
 /* the global batch, the embeddings having been computed on other ranks)      */

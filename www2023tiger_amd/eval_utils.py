@@ -611,6 +611,70 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
     return out
 
 
+def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 10, exclude_seen: bool = False,
+                        chunk_queries: int = 65536, restart_mode: bool = False, return_positions: bool = False) -> dict:
+    """Top-k recommendation quality over a loader (no counterpart in the reference's eval_utils): for every batch the k best
+    items of the shared `catalogue` (int64 [C], no id twice) are listed for the batch's sources on the state BEFORE the
+    batch (TIGE.recommend), then the batch runs as in `eval_edge_ranking` (contrast_learning), so the state advances
+    exactly as there.  -> dict(hit_rate, ndcg, mrr_at_k, n_events, coverage[, positions int64 [n_events]]).
+    position = the 0-based place of the event's true destination in its list, -1 when it is not listed; over ALL events
+    hit_rate = mean [position >= 0], ndcg = mean of 1 / log2(position + 2) (one relevant item: the ideal DCG is 1),
+    mrr_at_k = mean of 1 / (position + 1), a miss counting 0.  coverage = the share of events whose destination is in
+    the catalogue and left in (not the padding id; with exclude_seen=True not an item the source has an edge with before
+    the event's time - tg_seen_mask over the loader's graph): an upper bound of hit_rate.  Positions and folds are a few
+    [B, k] torch ops accumulated on the device, one read-back at the end.  Refused: restart_mode, and whatever
+    TIGE.recommend refuses."""
+    from . import hip_ops
+    if restart_mode:
+        raise NotImplementedError('eval_recommendation: restart mode is not built (the lazy restarts of eval_edge_prediction '
+                                  "cover the batch's own neighbourhoods, not the catalogue's)")
+    model._refuse_partitioned('eval_recommendation')
+    model.eval()
+    k = int(k)
+    cat = torch.as_tensor(catalogue).long().to(device)
+    if cat.dim() != 1:
+        raise ValueError('catalogue: int64 [C], shared by all events')
+    C = cat.numel()
+    col_of = hip_ops.catalogue_index(cat, model.n_nodes)
+    graph = getattr(getattr(dl, 'collate_fn', None), 'graph', None)
+    acc = torch.zeros(4, dtype=torch.float64, device=device)  # hits, sum of gains, sum of reciprocal places, covered
+    place = torch.arange(k, dtype=torch.int64, device=device)
+    positions, n = [], 0
+    with torch.no_grad():
+        for src_ids, dst_ids, neg_dst_ids, ts, eids, _, comp_graph in BackgroundThreadGenerator(dl):
+            src_ids, dst_ids, neg_dst_ids = (x.long().to(device) for x in (src_ids, dst_ids, neg_dst_ids))
+            ts, eids = ts.float().to(device), eids.long().to(device)
+            comp_graph.to(device)
+            ts64 = getattr(comp_graph, 'ts64', None)
+            t = (ts if ts64 is None else ts64).to(device)
+            g = graph if graph is not None else getattr(comp_graph, 'graph', None)
+            g = model.graph if g is None else g
+            seen = hip_ops.seen_mask(g, src_ids, t, col_of, C) if exclude_seen else None
+            ids, _, _ = model.recommend(src_ids, t, cat, k, mask=seen, graph=g, chunk_queries=chunk_queries)
+            hit = (ids == dst_ids[:, None]) & (ids != 0)
+            pos = torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1)   # the first listing (there is one at most)
+            listed = pos >= 0
+            p64 = pos.clamp(min=0).double()
+            col = col_of[dst_ids.clamp(0, model.n_nodes - 1)].long()
+            covered = (col >= 0) & (dst_ids != 0)
+            if seen is not None and C:
+                covered &= seen[torch.arange(len(src_ids), device=device), col.clamp(min=0)]
+            acc += torch.stack([listed.sum().double(), (listed / torch.log2(p64 + 2.0)).sum(), (listed / (p64 + 1.0)).sum(),
+                                covered.sum().double()])
+            if return_positions:
+                positions.append(pos)
+            model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
+            n += len(src_ids)
+    model._poll_train_errors()
+    a = acc.cpu().tolist()
+    nan = float('nan')
+    out = dict(hit_rate=a[0] / n if n else nan, ndcg=a[1] / n if n else nan, mrr_at_k=a[2] / n if n else nan, n_events=n,
+               coverage=a[3] / n if n else nan)
+    if return_positions:
+        out['positions'] = torch.cat(positions) if positions else torch.zeros(0, dtype=torch.int64, device=device)
+    return out
+
+
 def _decode_resident(encoder, decoder, dl, plan):
     """eval_node_classification's loop over a RESIDENT stream (_eval_resident, the same steps as eval_edge_prediction's
     pass): after each step a tg_decoder_fwd launch reads the batch's source embeddings (tb.sb.h[:B]) and writes their

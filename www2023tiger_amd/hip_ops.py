@@ -210,3 +210,98 @@ def rank_metrics(acc, ks=(1, 3, 10)) -> dict:
     nan = float('nan')
     return dict(mrr=float(f[0]) / n if n else nan, hits={int(k): (float(f[1 + q]) / n if n else nan) for q, k in enumerate(ks)},
                 n_events=n)
+
+
+# ---- top-k recommendation (tg_topk_rows / tg_seen_mask and their host twins) ----------------------------------------------
+def topk_rows(scores: Tensor, cand_ids: Tensor, k: int, *, mask: Optional[Tensor] = None, n_seg: int = 0, acc=None) -> dict:
+    """The k best columns of every row of scores [B, C] (tiger_hip.h: tg_topk_rows).  cand_ids: int64 [B, C], or [C] shared
+    by all rows.  A column is left out when its id is the padding id 0, when mask[i, j] is false (mask: [B, C]) or when
+    its score is not finite (counted).  Order: higher float32 score first, equal scores (-0.0 == +0.0) by ascending column.
+    -> dict(ids int64 [B, k], scores float32 [B, k], cols int32 [B, k]; n_valid int32 [B]; n_nonfinite int64 [1], the
+    accumulator `acc` when given - pass it back in to count over a whole pass).  Positions past min(k, n_valid) hold id 0,
+    score -inf, column -1.  n_seg: column segments per row (0: the library chooses); the result does not depend on it.
+    scores may be a view with a row stride above C.  Device tensors take the device entry, host tensors the host twin."""
+    dev = scores.device
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError('topk_rows: scores is float32 [B, C]')
+    if scores.numel() and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    B, C = scores.shape
+    ld = scores.stride(0) if B > 1 and C > 0 else C
+    if ld < C:
+        scores, ld = scores.contiguous(), C
+    cand_ids = _i64(cand_ids.to(dev))
+    shared = cand_ids.dim() == 1
+    if cand_ids.shape != ((C,) if shared else (B, C)):
+        raise ValueError(f'topk_rows: scores {tuple(scores.shape)}, cand_ids {tuple(cand_ids.shape)}')
+    if mask is not None:
+        mask = mask.to(dev).to(torch.uint8).contiguous()
+        if mask.shape != (B, C):
+            raise ValueError(f'topk_rows: mask {tuple(mask.shape)} for scores {tuple(scores.shape)}')
+    k, n_seg = int(k), int(n_seg)
+    if not 1 <= k <= _lib.TG_TOPK_MAX_K:
+        raise ValueError(f'topk_rows: 1 <= k <= {_lib.TG_TOPK_MAX_K}')
+    if n_seg < 0:
+        raise ValueError('topk_rows: n_seg is 0 (chosen by the library) or positive')
+    acc = torch.zeros(1, dtype=torch.int64, device=dev) if acc is None else acc
+    out = dict(ids=torch.empty(B, k, dtype=torch.int64, device=dev), scores=torch.empty(B, k, dtype=torch.float32, device=dev),
+               cols=torch.empty(B, k, dtype=torch.int32, device=dev), n_valid=torch.empty(B, dtype=torch.int32, device=dev),
+               n_nonfinite=acc)
+    args = (B, C, k, ptr(scores), ld, ptr(cand_ids), 1 if shared else 0, ptr(mask), n_seg, ptr(out['ids']),
+            ptr(out['scores']), ptr(out['cols']), ptr(out['n_valid']), ptr(acc))
+    if dev.type == 'cpu':
+        check(lib.tg_topk_rows_host(*args), 'tg_topk_rows_host')
+    else:
+        nbytes = int(lib.tg_topk_rows_workspace_bytes(B, C, k, n_seg))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.tg_topk_rows(*args, ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_topk_rows')
+    return out
+
+
+def catalogue_index(cand: Tensor, n_nodes: int) -> Tensor:
+    """int32 [n_nodes] on cand's device: the column of every node id in the shared catalogue cand [C], -1 for a node that
+    is not in it (the `col_of` of seen_mask).  ValueError for an id outside [0, n_nodes) or listed twice."""
+    cand = _i64(torch.as_tensor(cand)).reshape(-1)
+    C = cand.numel()
+    if C and (int(cand.min()) < 0 or int(cand.max()) >= n_nodes):
+        raise ValueError('catalogue_index: a node id outside [0, n_nodes)')
+    if C and int(torch.bincount(cand, minlength=1).max()) > 1:
+        raise ValueError('catalogue_index: duplicate node ids in the catalogue')
+    col_of = torch.full((int(n_nodes),), -1, dtype=torch.int32, device=cand.device)
+    col_of[cand] = torch.arange(C, dtype=torch.int32, device=cand.device)
+    return col_of
+
+
+def seen_mask(graph, src: Tensor, ts: Tensor, col_of: Tensor, C: int, mask: Optional[Tensor] = None) -> Tensor:
+    """bool [B, C]: false where column c of the catalogue is a node src[i] has an edge with (either direction) before
+    ts[i] - strict float64, the sampler's cut (tiger_hip.h: tg_seen_mask) - or where the caller's `mask` already was.
+    col_of: `catalogue_index(cand, graph.num_node)`.  Device tensors take the device entry over graph.tcsr, host tensors
+    the host twin over the graph's host arrays.  ValueError for a source outside [0, num_node)."""
+    import ctypes as C_
+    dev = src.device
+    src = _i64(src).reshape(-1)
+    B, C = src.numel(), int(C)
+    ts = ts.to(dev).double().contiguous().reshape(-1)
+    col_of = col_of.to(dev).contiguous()
+    if ts.numel() != B or col_of.dtype != torch.int32 or col_of.numel() != graph.num_node:
+        raise ValueError(f'seen_mask: {B} sources, ts {tuple(ts.shape)}, col_of {col_of.dtype} {tuple(col_of.shape)} '
+                         f'for {graph.num_node} nodes')
+    if B and (int(src.min()) < 0 or int(src.max()) >= graph.num_node):
+        raise ValueError('seen_mask: a source id outside [0, num_node)')
+    if mask is None:
+        m8 = torch.ones(B, C, dtype=torch.uint8, device=dev)
+    else:
+        if mask.shape != (B, C):
+            raise ValueError(f'seen_mask: mask {tuple(mask.shape)} for {B} sources and {C} columns')
+        m8 = mask.to(dev).ne(0).to(torch.uint8).contiguous()  # (a fresh buffer: the caller's mask is not written)
+    if dev.type == 'cpu':
+        h = graph._host_tcsr()
+        tc = _lib.TgTcsr(graph.num_node, len(h[1]), *(ptr(a) for a in h))
+        check(lib.tg_seen_mask_host(C_.byref(tc), B, ptr(src), ptr(ts), C, ptr(col_of), ptr(m8)), 'tg_seen_mask_host')
+    else:
+        gd = graph.device
+        if gd.type != dev.type or (gd.index is not None and dev.index is not None and gd.index != dev.index):
+            raise ValueError(f'seen_mask: the graph lives on {graph.device}, the queries on {dev}')
+        check(lib.tg_seen_mask(C_.byref(graph.tcsr), B, ptr(src), ptr(ts), C, ptr(col_of), ptr(m8), stream_ptr(dev)),
+              'tg_seen_mask')
+    return m8.bool()

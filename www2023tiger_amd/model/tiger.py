@@ -16,7 +16,7 @@ Ways to run a batch:
   * `fuse_attention()` - inference with fixed parameters: pre-multiplied attention weights.
 """
 import ctypes as C
-from typing import Tuple, Union
+from typing import Optional, Tuple, Union
 
 import numpy as np
 import os
@@ -25,7 +25,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import hip_ops
-from .._lib import TgLazyRestart, TgLinear, TgModel, TgStepIo, check, lib, ptr
+from .._lib import TG_TOPK_MAX_K, TgLazyRestart, TgLinear, TgModel, TgStepIo, check, lib, ptr
 from ..hip_ops import stream_ptr
 from .basic_modules import MergeLayer
 from .memory import Memory, MessageStoreNoGradLastOnly
@@ -787,24 +787,8 @@ class TIGE(nn.Module):
         (default: model.graph; an evaluation loop passes its collator's).  eval() mode only.  Refused before anything
         runs: strategy 'uniform' (a score would depend on the graph's random stream), a partitioned model, 'vec' hits with
         2 (d + K) not a multiple of 4 (as the one-call evaluation step)."""
-        from ..data.data_loader import GraphCollator
-        from .training import score_struct
-        self._refuse_partitioned('rank_scores')
-        graph = self.graph if graph is None else graph
-        strategy = getattr(graph, 'strategy', 'recent_edges')
-        if strategy not in ('recent_edges', 'recent_nodes'):
-            raise NotImplementedError(f"rank_scores samples 'recent_edges' or 'recent_nodes'; strategy={strategy!r} would make a "
-                                      "score depend on the graph's random stream")
-        if self.n_layers not in (1, 2):
-            raise NotImplementedError('rank_scores: the operator path embeds with n_layers 1 or 2')
-        d, K, dev = self.memory_dim, self.n_neighbors, self.device
-        if self.hit_type == 'vec' and (2 * (d + K)) % 4:
-            raise NotImplementedError("rank_scores: 'vec' hits need 2 (d + n_neighbors) to be a multiple of 4")
-        if self.training:
-            raise RuntimeError('rank_scores scores the model in eval() mode')
-        if chunk_queries < 1:
-            raise ValueError('chunk_queries must be positive')
-        self.check_graph(graph)
+        graph, strategy = self._pair_refusals('rank_scores', graph, chunk_queries)
+        dev = self.device
         src_ids, dst_ids = (x.to(dev).long().contiguous() for x in (src_ids, dst_ids))
         cand = torch.as_tensor(cand).to(dev).long()
         B = src_ids.numel()
@@ -813,12 +797,42 @@ class TIGE(nn.Module):
         if cand.dim() != 2 or cand.shape[0] != B or dst_ids.numel() != B or ts.numel() != B:
             raise ValueError(f'rank_scores: {B} events, dst {tuple(dst_ids.shape)}, ts {tuple(ts.shape)}, cand {tuple(cand.shape)}')
         ids_all = torch.cat([dst_ids[:, None], cand], 1)
+        return self._pair_scores('rank_scores', src_ids, ids_all, ts, graph, strategy, chunk_queries)
+
+    def _pair_refusals(self, what: str, graph, chunk_queries: int):
+        """what rank_scores and recommend refuse before anything runs -> (graph, its sampling strategy)"""
+        self._refuse_partitioned(what)
+        graph = self.graph if graph is None else graph
+        strategy = getattr(graph, 'strategy', 'recent_edges')
+        if strategy not in ('recent_edges', 'recent_nodes'):
+            raise NotImplementedError(f"{what} samples 'recent_edges' or 'recent_nodes'; strategy={strategy!r} would make a "
+                                      "score depend on the graph's random stream")
+        if self.n_layers not in (1, 2):
+            raise NotImplementedError(f'{what}: the operator path embeds with n_layers 1 or 2')
+        if self.hit_type == 'vec' and (2 * (self.memory_dim + self.n_neighbors)) % 4:
+            raise NotImplementedError(f"{what}: 'vec' hits need 2 (d + n_neighbors) to be a multiple of 4")
+        if self.training:
+            raise RuntimeError(f'{what} scores the model in eval() mode')
+        if chunk_queries < 1:
+            raise ValueError('chunk_queries must be positive')
+        self.check_graph(graph)
+        return graph, strategy
+
+    def _pair_scores(self, what: str, src_ids: Tensor, ids_all: Tensor, ts: Tensor, graph, strategy: str,
+                     chunk_queries: int) -> Tensor:
+        """scores [B, C1] of the pairs (src_ids[i], ids_all[i, j]) at ts[i] on the current state, nothing written (the body
+        of rank_scores, which passes [dst | cand]; recommend passes its candidates alone).  C1 >= 1; `_pair_refusals` has
+        run; src_ids int64 [B] and ids_all int64 [B, C1] live on the model's device."""
+        from ..data.data_loader import GraphCollator
+        from .training import score_struct
+        d, K, dev = self.memory_dim, self.n_neighbors, self.device
+        B = src_ids.numel()
         if B:
             lo_id, hi_id = torch.aminmax(torch.cat([src_ids, ids_all.reshape(-1)]))
             if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
-                raise ValueError('rank_scores: a node id outside [0, n_nodes)')
+                raise ValueError(f'{what}: a node id outside [0, n_nodes)')
         ts64 = ts.to(dev).double().contiguous()
-        C1 = cand.shape[1] + 1
+        C1 = ids_all.shape[1]
         scores = torch.empty(B, C1, dtype=torch.float32, device=dev)
         if B == 0:
             return scores
@@ -877,6 +891,67 @@ class TIGE(nn.Module):
                                          ptr(nodes[:b]), ptr(ids), ptr(out), ptr(ws), ws.numel(), s), 'tg_rank_scores')
             hip_ops.raise_if_err(err)
         return scores
+
+    # ---- top-k recommendation ------------------------------------------------------------
+    def recommend(self, src_ids: Tensor, ts: Tensor, cand: Tensor, k: int, *, mask: Optional[Tensor] = None,
+                  exclude_seen: bool = False, graph=None, chunk_queries: int = 65536, col_of: Optional[Tensor] = None):
+        """The k best destinations of every (source, time) query among its candidates, on the model's CURRENT state,
+        writing nothing -> (ids int64 [B, k], scores float32 [B, k], n_valid int32 [B]).  cand: int64 [B, C], or [C]
+        shared by all queries (a catalogue).  A candidate is left out when it is the padding id 0, when mask[i, j] is false
+        (mask: bool [B, C], or [C] with a shared catalogue), or - exclude_seen=True, shared catalogue only - when the
+        source has an edge with it before ts[i] in `graph` (tg_seen_mask; col_of: `hip_ops.catalogue_index(cand, n_nodes)`
+        when the caller has it, built here otherwise).  Order: higher score first, equal scores in the candidates'
+        order (tg_topk_rows); positions past n_valid[i] hold id 0 and score -inf.  The scores are those of rank_scores
+        (the same pair scores through `_pair_scores`, so a pair's bits do not depend on where it stands); queries run in
+        chunks of at most `chunk_queries` pair scores.  A non-finite score among the candidates left in raises ValueError.
+        Refused before anything runs: whatever rank_scores refuses (strategy 'uniform', a partitioned model, training
+        mode, unaligned 'vec' hits); exclude_seen with per-query candidates."""
+        graph, strategy = self._pair_refusals('recommend', graph, chunk_queries)
+        dev = self.device
+        src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
+        cand = torch.as_tensor(cand).to(dev).long().contiguous()
+        B, k = src_ids.numel(), int(k)
+        shared = cand.dim() == 1
+        if not 1 <= k <= TG_TOPK_MAX_K:
+            raise ValueError(f'recommend: 1 <= k <= {TG_TOPK_MAX_K}')
+        if cand.dim() not in (1, 2) or (not shared and cand.shape[0] != B) or ts.numel() != B:
+            raise ValueError(f'recommend: {B} queries, ts {tuple(ts.shape)}, cand {tuple(cand.shape)}')
+        if exclude_seen and not shared:
+            raise ValueError('recommend: exclude_seen needs a shared catalogue cand [C]')
+        Cc = cand.shape[-1]
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(dev).bool()
+            if mask.shape != ((Cc,) if mask.dim() == 1 and shared else (B, Cc)):
+                raise ValueError(f'recommend: mask {tuple(mask.shape)} for cand {tuple(cand.shape)} of {B} queries')
+        if B and Cc:
+            lo_id, hi_id = torch.aminmax(torch.cat([src_ids, cand.reshape(-1)]))
+            if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
+                raise ValueError('recommend: a node id outside [0, n_nodes)')
+        if exclude_seen and col_of is None:
+            col_of = hip_ops.catalogue_index(cand, self.n_nodes)
+        ts64 = ts.to(dev).double().contiguous().reshape(-1)
+        out_ids = torch.zeros(B, k, dtype=torch.int64, device=dev)
+        out_scores = torch.full((B, k), float('-inf'), dtype=torch.float32, device=dev)
+        n_valid = torch.zeros(B, dtype=torch.int32, device=dev)
+        if B == 0 or Cc == 0:
+            return out_ids, out_scores, n_valid
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        step = max(1, int(chunk_queries) // (Cc + 1))
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            ids = cand.unsqueeze(0).expand(hi - lo, -1) if shared else cand[lo:hi]
+            scores = self._pair_scores('recommend', src_ids[lo:hi], ids, ts64[lo:hi], graph, strategy, chunk_queries)
+            mk = None
+            if mask is not None:
+                mk = mask.unsqueeze(0).expand(hi - lo, -1) if mask.dim() == 1 else mask[lo:hi]
+            if exclude_seen:
+                mk = hip_ops.seen_mask(graph, src_ids[lo:hi], ts64[lo:hi], col_of, Cc, mask=mk)
+            top = hip_ops.topk_rows(scores, cand if shared else ids, k, mask=mk, acc=bad)
+            out_ids[lo:hi], out_scores[lo:hi], n_valid[lo:hi] = top['ids'], top['scores'], top['n_valid']
+        n_bad = int(bad.item())
+        if n_bad:
+            raise ValueError(f'Input contains {n_bad} non-finite scores.')
+        return out_ids, out_scores, n_valid
 
     # ---- fused path ---------------------------------------------------------------------
     class StepBuffers:

@@ -8,7 +8,12 @@ streams as in evaluation.  Writes ids.npy [n_test, k] / scores.npy [n_test, k] a
 
     python examples/recommend.py --data wikipedia --root /path/with/data --ckpt model.pt --k 10 [--exclude_seen]
 
-Only `run()` matters; the few flags exist to make the file runnable.
+--online replays the test split as a deployed model meets it: the graph is built over the train + validation events
+only, and every batch first asks `recommend` at its own (source, time) queries and is then ingested with `TIGE.observe`
+(the graph is extended on the device, the batch streams).  The same replay on the full graph with `stream_step` runs
+beside it, and the two lines printed - hit rate / NDCG / MRR@k - must be equal exactly (`run_online` asserts it).
+
+Only `run()` and `run_online()` matter; the few flags exist to make the file runnable.
 """
 import argparse
 import os
@@ -61,6 +66,62 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     return ids, scores, out
 
 
+def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest):
+    """recommend, then `ingest`, batch by batch over the test split -> (ids [n_test, k], dict of the metrics of
+    eval_recommendation: position of the true destination in its list, folded the same way)"""
+    dev = model.device
+    ids, pos = [], []
+    place = torch.arange(k, device=dev)
+    for lo in range(0, len(test.src), bs):
+        src, dst, ts, eids = (np.ascontiguousarray(getattr(test, f)[lo:lo + bs]) for f in ('src', 'dst', 'ts', 'eids'))
+        q, t, d = torch.from_numpy(src).to(dev), torch.from_numpy(ts.astype(np.float64)).to(dev), torch.from_numpy(dst).to(dev)
+        i, _, _ = model.recommend(q, t, catalogue, k, exclude_seen=exclude_seen, col_of=col_of)
+        hit = (i == d[:, None]) & (i != 0)
+        pos.append(torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1))
+        ids.append(i)
+        ingest(src, dst, ts.astype(np.float64), eids)
+    pos = torch.cat(pos)
+    listed, p = pos >= 0, pos.clamp(min=0).double()
+    n = max(1, pos.numel())
+    return torch.cat(ids).cpu().numpy(), dict(hit_rate=float(listed.sum()) / n, ndcg=float((listed / torch.log2(p + 2)).sum()) / n,
+                                              mrr_at_k=float((listed / (p + 1)).sum()) / n, n_events=pos.numel())
+
+
+def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
+               hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
+               device='cuda:0'):
+    """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
+    covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`."""
+    from www2023tiger_amd.data.graph import Graph
+    device = torch.device(device)
+    torch.manual_seed(seed)
+    basic, (train_graph, full_graph), dls = init_data(
+        data, root, seed, num_workers=0, bs=bs, warmup_steps=0, subset=1.0, strategy=strategy, n_layers=1,
+        n_neighbors=n_neighbors, restarter_type=restarter_type, hist_len=hist_len, device=device)
+    nfeats, efeats, full_data, test = basic[0], basic[1], basic[2], basic[5]
+    model = init_model(nfeats, efeats, train_graph, full_graph, full_data, device, dim=dim, n_layers=1, n_heads=n_heads,
+                       n_neighbors=n_neighbors, hit_type=hit_type, dropout=0.0, restarter_type=restarter_type,
+                       hist_len=hist_len, msg_src=msg_src, upd_src=upd_src, msg_tsfm_type='id', mem_update_type='gru')
+    model.load_state_dict(torch.load(ckpt_path, map_location=device))
+    model.eval()
+    catalogue = torch.from_numpy(np.unique(full_data.dst).astype(np.int64)).to(device)
+    col_of = hip_ops.catalogue_index(catalogue, model.n_nodes)
+    n_seen = len(full_data.src) - len(test.src)   # the test split is the tail of the stream
+    start = model.save_memory_state()
+    with torch.no_grad():
+        model.graph = full_graph
+        ids_off, offline = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
+                                   lambda s, d, t, e: model.stream_step(s, d, d, t, e))
+        model.load_memory_state(start)
+        # the edge table already holds the rows of the test events; a live system hands them to observe(efeats=...)
+        model.graph = Graph.from_arrays(full_data.src[:n_seen], full_data.dst[:n_seen], full_data.ts[:n_seen],
+                                        full_data.eids[:n_seen], strategy=full_graph.strategy, seed=seed,
+                                        max_node_id=full_graph.num_node - 1, device=device)
+        ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs, model.observe)
+    assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
+    return online, offline
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser(description='Write top-k recommendation lists for the test split of a TIGER checkpoint.')
     ap.add_argument('-d', '--data', default='wikipedia')
@@ -72,7 +133,15 @@ if __name__ == '__main__':
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--bs', type=int, default=200)
     ap.add_argument('--restarter_type', default='seq', choices=['seq', 'static'])
+    ap.add_argument('--online', action='store_true', help='replay the test split through TIGE.observe on a graph that '
+                    'starts at train + validation, beside the replay on the full graph')
     a = ap.parse_args()
+    if a.online:
+        for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
+                                                              seed=a.seed, bs=a.bs, restarter_type=a.restarter_type)):
+            print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "
+                  f"({m['n_events']} events)")
+        sys.exit(0)
     ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
                     restarter_type=a.restarter_type)
     print(f"test: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "

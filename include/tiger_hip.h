@@ -99,6 +99,24 @@ int tg_tcsr_build_device(int64_t num_events, const int64_t* src, const int64_t* 
                          const int64_t* eid, int64_t num_node, int64_t* indptr, double* ts_out,
                          int32_t* nbr_out, int32_t* eid_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Online ingestion: the T-CSR of `g` extended by n_new NEW events, written to caller-owned arrays (indptr_out
+ * [num_node + 1]; ts_out / nbr_out / eid_out [g->num_entry + 2 n_new]); `g` itself is only read.  Contract - the caller
+ * checks, as for tg_tcsr_build_device: the batch is non-decreasing in ts, its first ts is >= every ts already in g (equal
+ * is allowed), ids lie in [0, num_node), eids in [0, 2^31), g->num_entry + 2 n_new < 2^32.  Under it the out arrays equal,
+ * byte for byte, what tg_tcsr_build_host gives for the old events followed by the new ones (graph.py:11-42,226-241: every
+ * node's list is its old list followed by its new entries in event order, a self loop's flag-0 entry before its flag-1
+ * entry).  n_new == 0 copies; an old graph without entries works.  All pointers are DEVICE pointers; asynchronous on
+ * `stream`; TG_EWORKSPACE is returned before anything is launched.  Every old entry is read and written once. */
+size_t tg_tcsr_append_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node);
+int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* src, const int64_t* dst, const double* ts,
+                   const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out, int32_t* eid_out,
+                   void* ws, size_t ws_bytes, void* stream);
+/* The host twin: HOST pointers (those of `g` included), plain C++.  Ids and eids are checked (TG_EINVAL); the time
+ * order is the caller's to check. */
+int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_t* src_host, const int64_t* dst_host,
+                        const double* ts_host, const int64_t* eid_host, int64_t* indptr_out_host, double* ts_out_host,
+                        int32_t* nbr_out_host, int32_t* eid_out_host);
+
 /* Graph.sample_temporal_neighbor(strategy='recent_edges') and Graph.get_history
  * (graph.py:67-127,150-155): per query the last K entries with ts < t (strict),
  * left padded with zeros.  out_dir may be NULL.  If mark_flags != NULL every query

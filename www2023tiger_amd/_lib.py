@@ -164,6 +164,9 @@ SIGNATURES = {
     'tg_rand_edge_pairs': (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     'tg_tcsr_build_device_workspace_bytes': (sz, [i64, i64]),
     'tg_tcsr_build_device': (C.c_int, [i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_tcsr_append_workspace_bytes': (sz, [i64, i64, i64]),
+    'tg_tcsr_append': (C.c_int, [P(TgTcsr), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_tcsr_append_host': (C.c_int, [P(TgTcsr), i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     'tg_sample_recent_edges': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     'tg_sample_recent_nodes': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp]),
     'tg_sample_uniform': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),

@@ -148,6 +148,8 @@ class AdversarialEdgeSampler:
 
     def _index(self):
         g = self.graph
+        if self._ix is not None and self._ix_serial != g.serial:
+            self._ix = None  # `graph` was replaced (Graph.extended): the index is aligned with the arrays of the graph it saw
         if self._ix is None:
             if self._device is None:
                 h = g._host_tcsr()
@@ -171,6 +173,7 @@ class AdversarialEdgeSampler:
             if P != 2 * len(self.full_srcs):
                 raise ValueError('the graph is not over the full stream (it needs two T-CSR entries per event)')
             self._ix = (nxt, fst)
+            self._ix_serial = g.serial
         return self._ix
 
     def _launch(self, mode, srcs, t0, t1, counter, out_count=False):

@@ -7,9 +7,11 @@ types, but the per-query Python loop (graph.py:94-146, "Bottleneck! Total time
 
 The object is immutable after construction, so the collator thread and the main
 thread may sample concurrently (each call allocates its own outputs and runs on
-the calling thread's current stream).
+the calling thread's current stream).  New events are ingested by `extended`, which
+returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was.
 """
 import ctypes as C
+import itertools
 from typing import Optional, Tuple
 
 import numpy as np
@@ -18,6 +20,19 @@ from torch import Tensor
 
 from .._lib import TgTcsr, check, lib, ptr
 from ..hip_ops import stream_ptr
+
+
+class _HostRoot:
+    """Host-side origin of a graph: the events of from_arrays and / or the host T-CSR arrays.  Shared by reference along a
+    chain of `extended` graphs until one of them materialises its own host view."""
+    __slots__ = ('events', 'host')
+
+    def __init__(self):
+        self.events = None  # (src, dst, ts, eids) of from_arrays, the input of either builder
+        self.host = None    # host T-CSR arrays (indptr, ts, nbr, eid), built on demand
+
+
+_SERIAL = itertools.count(1)  # process-wide: next() is atomic under the GIL
 
 
 class Graph:
@@ -40,22 +55,74 @@ class Graph:
         if len(eid) and (eid.min() < 0 or eid.max() > 0x7FFFFFFF):
             raise ValueError('edge ids must fit in 31 bits')
         self._init_common(len(adj_list), strategy, seed, alpha, device)
+        self._t_last = float(ts.max()) if len(ts) else -np.inf
         packed = eid[order].astype(np.uint32) | (np.asarray(flag, dtype=np.uint32)[order] << np.uint32(31))
         self._host = (np.concatenate([[0], np.cumsum(np.bincount(owner, minlength=self.num_node))]).astype(np.int64),
                       ts[order], np.asarray(nbr, dtype=np.int64)[order].astype(np.int32), packed.view(np.int32))
 
-    def _init_common(self, num_node, strategy, seed, alpha, device):
+    def _init_common(self, num_node, strategy, seed, alpha, device, rng=None):
         self.num_node = int(num_node)
         self.strategy = strategy
         self.seed = seed
         self.alpha = alpha
-        self.rng = np.random.RandomState(seed)  # graph.py:22; its state seeds the device MT19937
+        # graph.py:22; its state seeds the device MT19937 (rng: an extended graph continues its parent's stream)
+        self.rng = np.random.RandomState(seed) if rng is None else rng
         self._device = torch.device(device) if device is not None else None
         self._dev = None  # device tensors, built / uploaded lazily
         self._mt = None
-        self._events = None  # (src, dst, ts, eids) of from_arrays, the input of either builder
-        self._host = None    # host T-CSR arrays (indptr, ts, nbr, eid), built on demand
+        self._root = _HostRoot()  # the host view: `_events`, `_host` below
+        self._log = None     # extended graphs: (parent's log, batch) - the batches appended to the root, newest first
         self._time_ordered = False
+        self._t_last = -np.inf  # latest event time, kept on the host (a 0-d device tensor after an unvalidated device batch)
+        self.serial = next(_SERIAL)  # a struct's address can be reused after its graph died; a serial number cannot
+        self.last_batch = None  # extended graphs: the (src, dst, ts, eids) they were extended by - device tensors when that
+                                # happened on the device, so a caller that streams the same batch next need not upload it again
+
+    # the host view is produced lazily for an extended graph (the device path of `extended` touches no host array)
+    @property
+    def _events(self):
+        self._materialise()
+        return self._root.events
+
+    @_events.setter
+    def _events(self, value):
+        self._root.events = value
+
+    @property
+    def _host(self):
+        return self._root.host if self._log is None else None
+
+    @_host.setter
+    def _host(self, value):
+        self._root.host = value
+
+    def _materialise(self):
+        """fold the appended batches into a host view of this graph's own: the root's events followed by the batches, and
+        the root's host T-CSR extended by them (tg_tcsr_append_host: what the host builder gives over the concatenation)"""
+        if self._log is None:
+            return
+        batches, node = [], self._log
+        while node is not None:  # (a loop: a chain may be thousands of batches long)
+            node, b = node
+            batches.append(b)
+        batches.reverse()
+        to_np = lambda x, dt: np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=dt)
+        src, dst, ts, eids = (np.concatenate([to_np(b[i], dt) for b in batches])
+                              for i, dt in enumerate((np.int64, np.int64, np.float64, np.int64)))
+        old, new = self._root, _HostRoot()
+        if old.events is not None:
+            new.events = tuple(np.concatenate([a, b]) for a, b in zip(old.events, (src, dst, ts, eids)))
+        if old.host is not None or old.events is None or not self._time_ordered:
+            if old.host is None:
+                old.host = self._build_host(old.events)
+            n = len(src)
+            h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(len(old.host[1]) + 2 * n, dtype=np.float64),
+                 np.empty(len(old.host[1]) + 2 * n, dtype=np.int32), np.empty(len(old.host[1]) + 2 * n, dtype=np.int32))
+            g = TgTcsr(self.num_node, len(old.host[1]), *(ptr(a) for a in old.host))
+            check(lib.tg_tcsr_append_host(C.byref(g), n, ptr(src), ptr(dst), ptr(ts), ptr(eids), *(ptr(a) for a in h)),
+                  'tg_tcsr_append_host')
+            new.host = h
+        self._root, self._log = new, None
 
     @classmethod
     def from_arrays(cls, src, dst, ts, eids, strategy='recent_nodes', seed=None, max_node_id=None, device=None):
@@ -73,20 +140,25 @@ class Graph:
         if E and (eids.min() < 0 or eids.max() > 0x7FFFFFFF):
             raise ValueError('edge ids must fit in 31 bits')
         self._events = (src, dst, ts, eids)
+        self._t_last = float(ts.max()) if E else -np.inf
         # a time-ordered stream (every JODIE file) is built on the GPU; others take the host builder,
         # which also performs the reference's stable per-node sort by time (graph.py:32)
         self._time_ordered = bool(E < 2 or np.all(ts[1:] >= ts[:-1])) and 2 * E < 2 ** 32
         return self
 
+    def _build_host(self, events):
+        src, dst, ts, eids = events
+        E = len(src)
+        h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(2 * E, dtype=np.float64),
+             np.empty(2 * E, dtype=np.int32), np.empty(2 * E, dtype=np.int32))
+        check(lib.tg_tcsr_build_host(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), self.num_node, *(ptr(a) for a in h)),
+              'tg_tcsr_build_host')
+        return h
+
     def _host_tcsr(self):
+        self._materialise()
         if self._host is None:
-            src, dst, ts, eids = self._events
-            E = len(src)
-            h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(2 * E, dtype=np.float64),
-                 np.empty(2 * E, dtype=np.int32), np.empty(2 * E, dtype=np.int32))
-            check(lib.tg_tcsr_build_host(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), self.num_node, *(ptr(a) for a in h)),
-                  'tg_tcsr_build_host')
-            self._host = h
+            self._host = self._build_host(self._events)
         return self._host
 
     _h_indptr = property(lambda self: self._host_tcsr()[0])
@@ -133,8 +205,12 @@ class Graph:
                 self._dev = self._build_on_device(dev)  # tg_tcsr_build_device: stable radix sort on the owner id
             else:
                 self._dev = tuple(torch.from_numpy(a).to(dev) for a in self._host_tcsr())
-            self._struct = TgTcsr(self.num_node, self._dev[1].numel(), *[t.data_ptr() for t in self._dev])
+            self._set_struct()
         return self._dev
+
+    def _set_struct(self):
+        self._struct = TgTcsr(self.num_node, self._dev[1].numel(), *[t.data_ptr() for t in self._dev])
+        self._struct.serial = self.serial  # (TIGE._prefetch_stamp: which graph a struct belongs to)
 
     @property
     def tcsr(self) -> TgTcsr:
@@ -147,6 +223,85 @@ class Graph:
             st = np.concatenate([key.astype(np.uint32), np.array([pos], dtype=np.uint32)]).view(np.int32)
             self._mt = torch.from_numpy(st.copy()).to(self.device)
         return self._mt
+
+    # ---- online ingestion -----------------------------------------------------------
+    def extended(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None) -> 'Graph':
+        """A NEW Graph over this graph's events followed by the batch (src, dst, ts, eids) - what `from_arrays` over the
+        concatenated stream builds, bit for bit (tg_tcsr_append; graph.py:11-42,226-241 has no counterpart: the reference
+        builds over the whole stream in advance).  This graph stays valid and unchanged: whatever holds it (captured
+        graphs, resident evaluation runs, a collator thread) keeps working.  The batch must be non-decreasing in time and
+        start no earlier than this graph's latest event (equal is allowed); ids in [0, num_node) - num_node never grows,
+        the model's tables are sized by it -; eids within 31 bits: ValueError otherwise, before anything is launched.
+        Host inputs (numpy, CPU tensors) are checked on the host; device tensors with torch reductions and one read-back,
+        or not at all with validate=False.  A device-resident parent costs no host work proportional to its size and no
+        synchronisation (one launch pair over the old entries, on the current stream); the host view of the new graph is
+        produced on first use.  strategy / seed / alpha / device carry over, and the child shares the parent's `rng` and
+        device MT19937 state: 'uniform' draws continue one stream.  eid_rows: the rows of the caller's edge-feature table -
+        an eid at or beyond it is refused with the rest (TIGE.observe; it shares the one read-back)."""
+        on_dev = torch.is_tensor(src) and src.device.type != 'cpu'
+        if on_dev:
+            batch = tuple(torch.as_tensor(x).to(src.device, dt).contiguous().reshape(-1)
+                          for x, dt in zip((src, dst, ts, eids), (torch.int64, torch.int64, torch.float64, torch.int64)))
+        else:
+            np_of = lambda x, dt: np.ascontiguousarray(x.detach().numpy() if torch.is_tensor(x) else x, dtype=dt).reshape(-1)
+            batch = (np_of(src, np.int64), np_of(dst, np.int64), np_of(ts, np.float64), np_of(eids, np.int64))
+        n = int(batch[0].shape[0])
+        if any(int(b.shape[0]) != n for b in batch):
+            raise ValueError('extended: src, dst, ts and eids must have one entry per event')
+        t_last = self._t_last
+        if n and (validate or not on_dev):
+            if torch.is_tensor(t_last):
+                t_last = self._t_last = float(t_last)
+            s, d, t, e = batch
+            if on_dev:  # a handful of reductions and the one read-back (ids and eids are exact in float64 below 2^53)
+                ordered = (t[1:] >= t[:-1]).all().reshape(1)
+                ints = torch.stack(torch.aminmax(torch.cat([s, d])) + torch.aminmax(e))
+                st = torch.cat([ordered.double(), t[:1], t[-1:], ints.double()]).tolist()
+            else:
+                st = [float(n < 2 or np.all(t[1:] >= t[:-1])), t[0], t[-1], min(s.min(), d.min()), max(s.max(), d.max()),
+                      e.min(), e.max()]
+            if not st[0] or st[1] != st[1] or st[2] != st[2]:
+                raise ValueError('extended: the batch must be non-decreasing in time')
+            if st[1] < t_last:
+                raise ValueError(f'extended: the batch starts at t = {st[1]}, before the latest event of the graph ({t_last})')
+            if st[3] < 0 or st[4] >= self.num_node:
+                raise ValueError('node ids must lie in [0, num_node) (num_node does not grow: the model\'s tables are sized by it)')
+            if st[5] < 0 or st[6] > 0x7FFFFFFF:
+                raise ValueError('edge ids must fit in 31 bits')
+            if eid_rows is not None and st[6] >= eid_rows:
+                raise ValueError(f'edge id {int(st[6])} is no row of the edge table ({eid_rows} rows)')
+            t_last = float(st[2])
+        elif n:
+            t_last = batch[2][-1]  # trusted device batch: stays on the device until a later validation asks for it
+        old_entries = self._dev[1].numel() if self._dev is not None else None
+        if old_entries is None:
+            self._materialise()
+            old_entries = len(self._host[1]) if self._host is not None else 2 * len(self._root.events[0])
+        if old_entries + 2 * n >= 2 ** 32:
+            raise ValueError('extended: the device T-CSR holds fewer than 2^32 entries')
+        child = Graph.__new__(Graph)
+        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
+        child._time_ordered = self._time_ordered
+        child._t_last = t_last
+        if self._dev is not None:  # device-resident parent: extend on the device
+            dev = self.device
+            g = self.tcsr
+            d_batch = batch if on_dev and batch[0].device == dev else tuple(torch.as_tensor(b).to(dev) for b in batch)
+            batch = d_batch  # kept as uploaded (`last_batch`); the host view downloads it if it is ever asked for
+            P = old_entries + 2 * n
+            out = (torch.empty(self.num_node + 1, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.float64, device=dev),
+                   torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev))
+            nbytes = int(lib.tg_tcsr_append_workspace_bytes(old_entries, n, self.num_node))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            # (inputs and workspace come from the caching allocator: their memory is reused in stream order, no wait needed)
+            check(lib.tg_tcsr_append(C.byref(g), n, *(ptr(b) for b in d_batch), *(ptr(t) for t in out), ptr(ws), nbytes,
+                                     stream_ptr(dev)), 'tg_tcsr_append')
+            child._dev = out
+            child._set_struct()
+            child._mt = self._mt_state()
+        child._root, child._log = self._root, (self._log, batch)
+        child.last_batch = batch
+        return child
 
     # ---- sampling -------------------------------------------------------------------
     def sample_device(self, nids: Tensor, ts: Tensor, n_neighbors: int, strategy: Optional[str] = None,

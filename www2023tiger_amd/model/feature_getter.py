@@ -54,6 +54,29 @@ class NumericalFeature(nn.Module):
             self._nz_cache = hit
         return hit[1]
 
+    def append_edge_rows(self, rows) -> bool:
+        """Append rows [n, d_e] to the edge table (online ingestion, TIGE.observe) -> whether the table's data pointer moved
+        (the caller then drops whatever caches it: TIGE.invalidate_struct).  The table is a leading view of a backing
+        storage that grows geometrically, so most calls copy the new rows and nothing else.  Without an edge table there is
+        nothing to do; tables pinned in host memory (register_buffer=False) do not grow."""
+        if self.efeats is None:
+            return False
+        if not self.pin_mem:
+            raise NotImplementedError('append_edge_rows: the edge table lives in pinned host memory (register_buffer=False)')
+        cur = self.efeats
+        rows = torch.as_tensor(rows).to(cur.device, cur.dtype).reshape(-1, cur.shape[1])
+        n0, n1 = cur.shape[0], cur.shape[0] + rows.shape[0]
+        store = getattr(self, '_ef_store', None)
+        if (store is None or store.device != cur.device or store.data_ptr() != cur.data_ptr() or store.shape[0] < n0
+                or store.shape[0] < n1):  # no backing yet (or the table was moved / replaced), or it is full: a new one
+            store = torch.empty(max(n1, 2 * n0, 16), cur.shape[1], dtype=cur.dtype, device=cur.device)
+            store[:n0] = cur
+            self._ef_store = store
+        store[n0:n1] = rows
+        self.efeats = store[:n1]
+        self.n_edges = n1
+        return self.efeats.data_ptr() != cur.data_ptr()
+
     def _lookup(self, table, ids, width):
         if table is None:
             return torch.zeros(*ids.shape, width, device=ids.device)

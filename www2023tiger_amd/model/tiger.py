@@ -1211,7 +1211,9 @@ class TIGE(nn.Module):
         (as for the eager-update table), that no other step ran on this model since, the stream offset tensor and the
         graph.  (Graph replays change none of these: a graph captured with the flag set on entry and exit keeps it
         valid by construction.)"""
-        return (self._state_stamp(), getattr(self, '_step_serial', 0), buf.offset._version, id(buf.offset), C.addressof(g))
+        # (the graph by its serial number too: the address of a dead graph's struct can be handed out again - Graph.extended)
+        return (self._state_stamp(), getattr(self, '_step_serial', 0), buf.offset._version, id(buf.offset), C.addressof(g),
+                getattr(g, 'serial', 0))
 
     @torch.no_grad()
     def stream_step(self, src, dst, neg, ts, eids, want_prev: bool = False, check_invariants: bool = True,
@@ -1234,6 +1236,36 @@ class TIGE(nn.Module):
                 from .._lib import raise_invariants
                 raise_invariants(word & 0xFFFFFFFF)
         return buf
+
+    def observe(self, src, dst, ts, eids, *, efeats=None, neg=None, want_prev: bool = False):
+        """Online ingestion of one time-ordered batch of NEW events: their edge-feature rows (efeats [n, d_e], for a model
+        with an edge table) are appended to the table, the graph is replaced by `graph.extended(...)` and the batch is
+        streamed (`stream_step`; neg defaults to dst) -> the step's StepBuffers.  Extending first is what the reference's
+        graph over the whole stream implies: an event sees same-batch events with a strictly earlier timestamp as
+        neighbours.  A model that starts from a graph over a prefix of the stream and observes the rest ends in the state,
+        and returns the embeddings, of a model that had the full graph from the start - bit for bit.  Afterwards
+        `recommend(..., exclude_seen=True)` and `rank_scores` see the new edges.  eval() mode only; refused before anything
+        runs: a partitioned model, training mode, an eid that is no row of the edge table (tg_model carries no row count:
+        the step would read past the table), and what `Graph.extended` refuses."""
+        self._refuse_partitioned('observe')
+        if self.training:
+            raise RuntimeError('observe streams the model in eval() mode')
+        fg = self.raw_feat_getter
+        n = len(src)
+        if efeats is not None and fg.efeats is not None:
+            efeats = torch.as_tensor(efeats)
+            if efeats.dim() != 2 or efeats.shape[0] != n or efeats.shape[1] != fg.efeats.shape[1]:
+                raise ValueError(f'observe: efeats {tuple(efeats.shape)} for {n} events of width {fg.efeats.shape[1]}')
+        rows = None if fg.efeats is None else fg.efeats.shape[0] + (n if efeats is not None else 0)
+        # (validates, the eids against the table's rows included - on the host, before any launch; nothing has changed if
+        # it raises)
+        new_graph = self.graph.extended(src, dst, ts, eids, eid_rows=rows)
+        if efeats is not None and fg.efeats is not None and fg.append_edge_rows(efeats):
+            self.invalidate_struct()
+        self.graph = new_graph
+        if torch.is_tensor(new_graph.last_batch[0]):  # extended on the device: the batch is already there
+            src, dst, ts, eids = new_graph.last_batch
+        return self.stream_step(src, dst, dst if neg is None else neg, ts, eids, want_prev=want_prev)
 
     # ---- remaining reference methods -----------------------------------------------------
     @torch.no_grad()

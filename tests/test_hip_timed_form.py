@@ -328,14 +328,10 @@ def test_prefetched_collate_is_discarded_when_state_offset_or_form_change():
     compare_state_with_oracle(model, orc)
 
 
-@pytest.mark.parametrize('side', ['1', '0'], ids=['side_stream', 'one_stream'])
-def test_large_batch_side_stream_form_matches_oracle(side, monkeypatch):
-    """Batches above 16 384 events host no riders; with TG_SIDE_STREAM=1 the write-back (STEP 4-5) runs on the library's
-    side stream beside fc1 and the NEXT batch's sampler beside the updater and the query rows (csrc/tg_model.hip:
-    SideLane), as parallel branches of a captured graph too (opt-in: measured not faster).  B = 20 000 on a small graph:
-    two eager steps, then a graph of two steps replayed twice; neighbour lists bit-exact, embeddings and the final
-    state against the oracle - in both forms."""
-    monkeypatch.setenv('TG_SIDE_STREAM', side)
+def test_large_batch_rider_free_form_matches_oracle():
+    """Batches above 16 384 events host no riders: the write-back (STEP 4-6) is a launch of its own and nothing of the NEXT
+    batch is prefetched (csrc/tg_model.hip: SIDE_MIN_B).  B = 20 000 on a small graph: two eager steps, then a graph of two
+    steps replayed twice; neighbour lists bit-exact, embeddings and the final state against the oracle."""
     import bench
     from oracle import tiger_oracle as O
     from test_hip_parity import compare_state_with_oracle
@@ -350,7 +346,7 @@ def test_large_batch_side_stream_form_matches_oracle(side, monkeypatch):
     buf = model.StepBuffers(model, B, False, resident=_resident(stream), prefetch=True, debug_lists=True)
     buf.io.lean = 1
     _ = model.graph.tcsr, model.model_struct()
-    side_on = side == '1' and os.environ.get('TG_PREFETCH', '1') != '0'
+    side_on = False
 
     def oracle_step(b, compare):
         a = [stream[k][b * B:(b + 1) * B] for k in ('src', 'dst', 'neg', 'ts', 'eids')]
@@ -371,7 +367,7 @@ def test_large_batch_side_stream_form_matches_oracle(side, monkeypatch):
         model.launch_step(buf)
         cnt = oracle_step(b, True)
         model.note_rows(cnt[1], cnt[2])
-        if b >= 1:  # side stream: the step started with its attention core, its sampler ran beside the last updater
+        if b >= 1:  # (no prefetch: the step starts with its own sampler)
             assert buf._pf_state.value == (1 if side_on else 0)
     side = torch.cuda.Stream()
     snap = buf.offset.clone()

@@ -1006,188 +1006,6 @@ __device__ __forceinline__ void gemm_direct_block(const GemmArgs& g, unsigned bi
     if (m0 < M && n0 < g.n) gemm_direct_tile<NS, RW, CW>(g, M, m0, n0);
   }
 }
-// ---- the tail of the split updater (tg_dense.h: GruTail) ----------------------------------------------------------------
-// gemm_direct_tile's scheme with RW = 1 and the four column sets being the four PLANES of one 16-column tile: rows of
-// [W2 ; W_hh W2] at n0 + li + {0, d, 2d, 3d}.  A wavefront owns 16 rows x 16 hidden columns: 4 NS x 4 MFMAs after ONE
-// exposed memory latency, then the gates (update_modules.py:33-37 = torch.nn.GRUCell) with gi read from the buffer the
-// second problem of fc1's launch left.  The h plane is the same k-ordered chain as fc2's row of that position.
-template <int NS, bool DIRECT>
-__device__ __forceinline__ void gru_tail_tile(const GruTail& g, int64_t M, int64_t m0, int n0) {
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 15, lk = lane >> 4;
-  const int d = g.d;
-  const int nch = d / 4;  // 16-byte chunks per row
-  // Two passes of two planes each: all four planes' operands at once are 4 NS + NS float4 = 220 registers at d = 172 - one
-  // wavefront per SIMD; here the operands of planes 2, 3 are requested, slot by slot, into the registers planes 0, 1 have
-  // just been multiplied from (their latency hides behind the first pass's MFMAs): 3 NS float4, two wavefronts per SIMD.
-  // DIRECT: planes r, z then n alone over weight_hh as stored; h is read, not computed
-  constexpr int P0 = DIRECT ? 0 : 1;  // weight plane of accumulator 1 (r)
-  float4 a[NS], w[2][NS];
-  unsigned livem = 0u;
-#pragma unroll
-  for (int s_ = 0; s_ < NS; ++s_)
-    if (lk + 4 * s_ < nch) livem |= 1u << s_;
-  {
-    const int64_t m = min(m0 + li, M - 1);
-    const float* row = g.t + g.t_rows[m] * (int64_t)d;
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) a[s_] = ldg4(row + 4 * min(lk + 4 * s_, nch - 1));
-  }
-  const int jc = min(n0 + li, d - 1);
-  const float* wrow = g.w + (int64_t)jc * d;
-  const int64_t ps = (int64_t)d * d;  // plane stride
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) w[p][s_] = ldg4(wrow + (P0 + p) * ps + 4 * min(lk + 4 * s_, nch - 1));
-  float bias[4], gi[4][3], addv[4], hold[4];
-  int orow[4];
-  f32x4m acc[4];  // r, z | n, h
-#pragma unroll
-  for (int p = 0; p < 4; ++p) acc[p] = f32x4m{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    constexpr int NP1 = DIRECT ? 1 : 2;  // planes of the second pass
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-      if (pass == 1 && s_ == NS / 2) {  // epilogue operands behind three quarters of the MFMAs (see gemm_direct_tile)
-        __builtin_amdgcn_sched_barrier(0);
-        if (DIRECT) {
-          bias[3] = 0.f;
-#pragma unroll
-          for (int p = 0; p < 3; ++p) bias[p] = g.b[p * d + jc];
-        } else {
-          bias[3] = g.b[jc];  // h
-#pragma unroll
-          for (int p = 0; p < 3; ++p) bias[p] = g.b[(1 + p) * d + jc];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int64_t m = min(m0 + 4 * lk + q, M - 1);
-          orow[q] = g.out_rows[m];
-#pragma unroll
-          for (int p = 0; p < 3; ++p) gi[q][p] = g.gi[m * 3 * (int64_t)d + p * d + jc];
-          hold[q] = DIRECT ? g.t[g.t_rows[m] * (int64_t)d + jc] : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) addv[q] = (g.out2 && g.add2) ? g.add2[(int64_t)orow[q] * d + jc] : 0.f;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const bool lv = (livem >> s_) & 1u;
-      const float4 x = lv ? a[s_] : zero4();
-      const float av[4] = {x.x, x.y, x.z, x.w};
-      float wv[2][4];
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        wv[p][0] = w[p][s_].x; wv[p][1] = w[p][s_].y; wv[p][2] = w[p][s_].z; wv[p][3] = w[p][s_].w;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int p = 0; p < (pass == 0 ? 2 : NP1); ++p)
-          acc[2 * pass + p] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv[p][j], acc[2 * pass + p], 0, 0, 0);
-      if (pass == 0) {  // this slot's registers are free: the same slot of the remaining planes (n; h = plane 0 of the blob)
-        __builtin_amdgcn_sched_barrier(0);
-        w[0][s_] = ldg4(wrow + (P0 + 2) * ps + 4 * min(lk + 4 * s_, nch - 1));
-        if (!DIRECT) w[1][s_] = ldg4(wrow + 4 * min(lk + 4 * s_, nch - 1));
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-  const int n = n0 + li;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int64_t m = m0 + 4 * lk + q;
-    const float h = DIRECT ? hold[q] : acc[3][q] + bias[3];
-    const float rg = fast_sigmoid(gi[q][0] + (acc[0][q] + bias[0]));
-    const float zg = fast_sigmoid(gi[q][1] + (acc[1][q] + bias[1]));
-    const float ng = fast_tanh(gi[q][2] + rg * (acc[2][q] + bias[2]));
-    const float hv = (1.f - zg) * ng + zg * h;
-    if (n < d && m < M) {
-      g.out[(int64_t)orow[q] * d + n] = hv;
-      if (g.out2) g.out2[(int64_t)orow[q] * d + n] = hv + addv[q];
-    }
-  }
-}
-// block `bid` of g.blocks (a multiple of 8): four wavefronts = four 16-row tiles of one 16-column tile (the weight slab of
-// the tile is shared through the CU's cache); XCD chunks of the (row group, column tile) sequence
-template <int NS>
-__device__ void GruTail::run(unsigned bid) const {
-  int64_t M = cap;
-  if (n_dev) M = min(M, (int64_t)*n_dev);
-  if (M <= 0) return;
-  const int NT = (d + 15) / 16;
-  const int64_t total = ((M + 63) / 64) * NT;
-  const int64_t per = (total + 7) / 8;
-  const int wave = threadIdx.x >> 6;
-  for (int64_t jx = bid >> 3; jx < per; jx += blocks >> 3) {
-    const int64_t b = (int64_t)(bid & 7) * per + jx;
-    if (b >= total) break;
-    const int64_t mt = b / NT;
-    const int nt = (int)(b - mt * NT);
-    const int64_t m0 = mt * 64 + 16 * wave;
-    if (m0 >= M) continue;
-    if (direct) gru_tail_tile<NS, true>(*this, M, m0, nt * 16);
-    else gru_tail_tile<NS, false>(*this, M, m0, nt * 16);
-  }
-}
-template <int NS>
-__global__ void __launch_bounds__(256) k_gru_tail(GruTail g) {
-  g.run<NS>(blockIdx.x);
-}
-// (the launch of its own always reads h directly: an instance without the pre-multiplied form's fourth plane)
-template <int NS>
-__global__ void __launch_bounds__(256) k_gru_tail_direct(GruTail g) {
-  int64_t M = g.cap;
-  if (g.n_dev) M = min(M, (int64_t)*g.n_dev);
-  if (M <= 0) return;
-  const int NT = (g.d + 15) / 16;
-  const int64_t total = ((M + 63) / 64) * NT;
-  const int64_t per = (total + 7) / 8;
-  const int wave = threadIdx.x >> 6;
-  for (int64_t jx = blockIdx.x >> 3; jx < per; jx += gridDim.x >> 3) {
-    const int64_t b = (int64_t)(blockIdx.x & 7) * per + jx;
-    if (b >= total) break;
-    const int64_t mt = b / NT;
-    const int nt = (int)(b - mt * NT);
-    const int64_t m0 = mt * 64 + 16 * wave;
-    if (m0 < M) gru_tail_tile<NS, true>(g, M, m0, nt * 16);
-  }
-}
-static unsigned gru_tail_blocks(const GruTail& t) {
-  const int64_t rows = t.rows_hint > 0 ? std::min(t.rows_hint, t.cap) : t.cap;
-  return (unsigned)std::min<int64_t>(256, 8 * cdiv(cdiv(rows, 64) * cdiv(t.d, 16), 8));
-}
-int gru_tail_launch(const GruTail& t, hipStream_t st) {
-  if (t.cap <= 0) return TG_OK;
-  const int nsl = (int)cdiv(cdiv(t.d, 4), 4);
-  if ((t.d % 4) || nsl > 11) return TG_EUNSUPPORTED;
-  GruTail g = t;
-  g.blocks = gru_tail_blocks(t);
-  if (g.direct) {
-    if (nsl <= 7) TG_KLAUNCH(k_gru_tail_direct<7>, dim3(g.blocks), dim3(256), 0, st, g);
-    else TG_KLAUNCH(k_gru_tail_direct<11>, dim3(g.blocks), dim3(256), 0, st, g);
-  } else if (nsl <= 7) {
-    TG_KLAUNCH(k_gru_tail<7>, dim3(g.blocks), dim3(256), 0, st, g);
-  } else {
-    TG_KLAUNCH(k_gru_tail<11>, dim3(g.blocks), dim3(256), 0, st, g);
-  }
-  return check_launch("gru_tail");
-}
-
-template <int NS, class R>
-__device__ __forceinline__ void run_rider(const R& r, unsigned bid) {
-  if constexpr (std::is_same<R, GruTail>::value) r.template run<NS>(bid);
-  else r.run(bid);
-}
-// a long-K product (k_gemm_ks16's 48 x 48 blocks, A of up to four segments) behind a short-K product's blocks: the split
-// updater's W_ih msg shares fc2's launch, whose 144 blocks leave 112 CUs idle at C2
-template <int RT, int CT, int NW, int NSEG>
-__device__ __forceinline__ void gemm_ks16_blocks(const GemmArgs& g, unsigned bid, unsigned nblk, float* sc_raw);
-struct GiRider {
-  GemmArgs g;
-  unsigned blocks;
-};
 template <int NS, int RW, int CW>
 __global__ void __launch_bounds__(256) k_gemm_direct(GemmArgs g) {
   gemm_direct_block<NS, RW, CW>(g, blockIdx.x, gridDim.x);
@@ -1196,12 +1014,7 @@ template <class R, int NS, int RW, int CW>
 __global__ void __launch_bounds__(256) k_gemm_direct_r(GemmArgs g, R r) {
   const unsigned own = gridDim.x - r.blocks;  // riders behind the product's blocks
   if (blockIdx.x >= own) {
-    if constexpr (std::is_same<R, GiRider>::value) {
-      __shared__ float sc_raw[4 * 3 * 9 * 64];
-      gemm_ks16_blocks<3, 3, 4, 4>(r.g, blockIdx.x - own, r.blocks, sc_raw);
-    } else {
-      run_rider<NS>(r, blockIdx.x - own);
-    }
+    r.run(blockIdx.x - own);
     return;
   }
   gemm_direct_block<NS, RW, CW>(g, blockIdx.x, own);
@@ -1217,8 +1030,7 @@ __global__ void __launch_bounds__(256) k_gemm_direct_r(GemmArgs g, R r) {
 // in one reduce-scatter round through LDS (summed in wavefront order: bit-reproducible) and the first four wavefronts
 // run the epilogue (bias, second bias on valid rows, alpha, ReLU) - the product leaves its final values, so its consumer
 // is a plain product.  256 persistent blocks, XCD chunks of the tile sequence.
-// NSEG = 4: A is four column segments, every one optionally gathered, the third possibly a slice of zeros (GemmArgs.a2 / a3)
-template <int RT, int CT, int NW, int NSEG = 2>
+template <int RT, int CT, int NW>
 __device__ __forceinline__ void gemm_ks16_tile(const GemmArgs& g, int64_t M, int64_t m0, int n0, float* sc_raw) {
   constexpr int NS = RT * CT;  // 16 x 16 subtiles of the block
   // diagnostic only (g.dbg & 16; tools/phase_budget.py): s_memtime stamps {entry, first tile requested, k-loop done, exit}
@@ -1228,21 +1040,13 @@ __device__ __forceinline__ void gemm_ks16_tile(const GemmArgs& g, int64_t M, int
   const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int K = g.k, N = g.n, kw0 = g.a0.w;
-  const int kw1 = kw0 + g.a1.w, kw2 = kw1 + (NSEG == 4 ? g.a2.w : 0);  // segment ends (NSEG = 4)
-  const bool zero2 = NSEG == 4 && !g.a2.p;                              // the third segment is zeros
   const float* ar0[RT];
   const float* ar1[RT];
-  const float* ar2[NSEG == 4 ? RT : 1];
-  const float* ar3[NSEG == 4 ? RT : 1];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int64_t m = min(m0 + 16 * rt + li, M - 1);
     ar0[rt] = g.a0.p + (g.a0.idx ? g.a0.idx[m] : m) * g.a0.ld;
     ar1[rt] = g.a1.p ? g.a1.p + (g.a1.idx ? g.a1.idx[m] : m) * g.a1.ld - kw0 : ar0[rt];
-    if (NSEG == 4) {
-      ar2[rt] = g.a2.p ? g.a2.p + (g.a2.idx ? g.a2.idx[m] : m) * g.a2.ld - kw1 : ar0[rt];
-      ar3[rt] = g.a3.p ? g.a3.p + (g.a3.idx ? g.a3.idx[m] : m) * g.a3.ld - kw2 : ar0[rt];
-    }
   }
   const float* wr[CT];
 #pragma unroll
@@ -1266,8 +1070,7 @@ __device__ __forceinline__ void gemm_ks16_tile(const GemmArgs& g, int64_t M, int
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int k = kb + 4 * q;
-      const bool dead = k >= K || (zero2 && k >= kw1 && k < kw2);  // (a chunk of the zero segment: multiplied as zeros)
-      if (!dead && ks < nkt) A.live |= 1u << q;
+      if (k < K && ks < nkt) A.live |= 1u << q;
       A.kc[q] = k < K ? k : 0;
     }
   };
@@ -1275,10 +1078,7 @@ __device__ __forceinline__ void gemm_ks16_tile(const GemmArgs& g, int64_t M, int
     const int q = l & 1, r = l >> 1;
     if (r < RT) {
       const int k = A.kc[q];
-      const float* row;
-      if (NSEG == 4) row = k < kw0 ? ar0[r] : k < kw1 ? ar1[r] : k < kw2 ? ar2[r] : ar3[r];
-      else row = k < kw0 ? ar0[r] : ar1[r];
-      T.a[r][q] = ldg4(row + k);
+      T.a[r][q] = ldg4((k < kw0 ? ar0[r] : ar1[r]) + k);
     } else {
       T.w[r - RT][q] = ldg4(wr[r - RT] + A.kc[q]);
     }
@@ -1416,7 +1216,7 @@ __device__ __forceinline__ void gemm_ks16_tile(const GemmArgs& g, int64_t M, int
 }
 
 // persistent blocks of one product: block `bid` of `nblk` (a multiple of 8) works through its XCD's chunk of the tile sequence
-template <int RT, int CT, int NW, int NSEG>
+template <int RT, int CT, int NW>
 __device__ __forceinline__ void gemm_ks16_blocks(const GemmArgs& g, unsigned bid, unsigned nblk, float* sc_raw) {
   int64_t M = g.m_cap;
   if (g.m_dev) M = min(M, (int64_t)*g.m_dev);
@@ -1430,226 +1230,19 @@ __device__ __forceinline__ void gemm_ks16_blocks(const GemmArgs& g, unsigned bid
     if (b >= total) break;
     const int64_t mt = b / NT;
     const int nt = (int)(b - mt * NT);
-    gemm_ks16_tile<RT, CT, NW, NSEG>(g, M, mt * BM, nt * BN, sc_raw);
+    gemm_ks16_tile<RT, CT, NW>(g, M, mt * BM, nt * BN, sc_raw);
     __syncthreads();  // the fold's LDS is re-used by the next tile
   }
 }
-// A second product in the same launch (S2 = Ks16Second): `blocks` further persistent blocks behind the first product's, in
-// front of the riders.  Two resident blocks per CU then interleave their MFMA streams (one block's four wavefronts - one
-// per SIMD, issuing in order - keep the matrix pipe ~40 % busy).
-struct NoSecond {
-  unsigned blocks;
-};
-struct Ks16Second {
-  GemmArgs g;
-  unsigned blocks;
-  unsigned seq;  // 1: no further blocks - the first product's blocks work through the second product's tiles afterwards
-};
-template <class R, int RT, int CT, int NW, class S2 = NoSecond>
-__global__ void __launch_bounds__(64 * NW) k_gemm_ks16(GemmArgs g, R r, S2 s2) {
+template <class R, int RT, int CT, int NW>
+__global__ void __launch_bounds__(64 * NW) k_gemm_ks16(GemmArgs g, R r) {
   __shared__ float sc_raw[4 * (NW - 1) * RT * CT * 64];
-  const unsigned own = gridDim.x - r.blocks - s2.blocks;  // persistent blocks of the product; second product, then riders
-  if (blockIdx.x >= own + s2.blocks) {
-    r.run(blockIdx.x - own - s2.blocks);
-    return;
-  }
-  if constexpr (std::is_same<S2, Ks16Second>::value) {
-    if (blockIdx.x >= own) {
-      gemm_ks16_blocks<RT, CT, NW, 4>(s2.g, blockIdx.x - own, s2.blocks, sc_raw);
-      return;
-    }
-  }
-  gemm_ks16_blocks<RT, CT, NW, 2>(g, blockIdx.x, own, sc_raw);
-  if constexpr (std::is_same<S2, Ks16Second>::value) {
-    if (s2.seq) gemm_ks16_blocks<RT, CT, NW, 4>(s2.g, blockIdx.x, own, sc_raw);
-  }
-}
-
-// ---- fc1 and fc2 of the attention block in ONE launch ------------------------------------------------------------------
-// The block's last two products are t = relu([S | c] W1f^T + b1 + valid c1) (K = n_head kvw + d) and h = t W2^T + b2 (K = d).
-// A block that owns WHOLE rows of t can run fc2 on them as its epilogue: 16 rows x all d columns (CT column subtiles of 16),
-// the k-loop of k_gemm_ks16 (LDS-free, K split over four wavefronts) with 1 x CT subtiles, the fold leaves the tile of t in
-// LDS, and the four wavefronts then share fc2's column subtiles: A fragments from that tile, W2 rows straight from memory
-// (requested before the fold), 4 NS MFMAs per subtile, h stored - and scattered a second time into the left memory for
-// the winning positions (STEP 6, GemmArgs.c2 form).  C2: 192 blocks of 16 rows instead of 256 blocks of 48 x 48 + a launch
-// of 144 blocks; fc2's launch - ten microseconds of which one is matrix work - is gone, the 64 CUs the product leaves idle
-// host the write-back riders.  Measured slower (see gemm_fc12_launch): kept as an opt-in form.
-struct Fc2Fuse {
-  const float* w;    // [n2, ldw] (torch Linear layout), n2 <= 16 CT
-  int64_t ldw;
-  const float* bias;
-  float* c;          // [M, ldc]
-  int64_t ldc;
-  int n;             // output columns of fc2
-  float* c2;         // nullable: second, scattered destination (rows c2_rows[m] for m < c2_m, -1 = none)
-  const int32_t* c2_rows;
-  int64_t c2_m, ldc2;
-};
-template <int CT>
-__device__ __forceinline__ void gemm_ks16_fc2_tile(const GemmArgs& g, const Fc2Fuse& f, int64_t M, int64_t m0, float* t_raw) {
-  // COLUMN split: wavefront ks owns column subtiles CW ks .. CW ks + CW - 1 of the 16-row block over the WHOLE K - no fold,
-  // ~100 registers (a K split over the four wavefronts with all CT subtiles per wavefront needs two tiles of 2 (1 + CT)
-  // operand chunks in flight: 512 registers and spills, 37.5 us at C2 against 33.5 us for the two launches).  The operand
-  // chunks of D = 4 k-tiles are in flight: a tile's registers are reloaded for tile i + D right after its MFMAs.
-  constexpr int NW = 4, CW = (CT + NW - 1) / NW, D = 4;
-  constexpr int TS = 16 * CT + 4;              // row stride of the t tile in LDS
-  constexpr int NS2 = (16 * CT + 15) / 16;     // chunk slots of fc2's K (= columns of t, 16 per slot)
-  float (*ts)[TS] = reinterpret_cast<float (*)[TS]>(t_raw);
-  const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
-  const int li = lane & 15, lk = lane >> 4;
-  const int K = g.k, N = g.n, kw0 = g.a0.w;
-  const int64_t m = min(m0 + li, M - 1);
-  const float* ar0 = g.a0.p + (g.a0.idx ? g.a0.idx[m] : m) * g.a0.ld;
-  const float* ar1 = g.a1.p ? g.a1.p + (g.a1.idx ? g.a1.idx[m] : m) * g.a1.ld - kw0 : ar0;
-  const float* wr[CW];
-#pragma unroll
-  for (int c = 0; c < CW; ++c) wr[c] = g.w + (int64_t)min(16 * (CW * ks + c) + li, N - 1) * g.ldw;
-  const int nkt = (K + BK - 1) / BK;
-  struct Tile {
-    float4 a[2], w[CW][2];
-  };
-  auto load_tile = [&](int t, Tile& T) {  // raw loads from clamped addresses; chunks past K are zeroed when they are used
-    const int kb = min(t, nkt - 1) * BK + 8 * lk;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int k = kb + 4 * q;
-      const int kc = k < K ? k : 0;
-      T.a[q] = ldg4((kc < kw0 ? ar0 : ar1) + kc);
-#pragma unroll
-      for (int c = 0; c < CW; ++c) T.w[c][q] = ldg4(wr[c] + kc);
-    }
-  };
-  f32x4m acc[CW];
-#pragma unroll
-  for (int c = 0; c < CW; ++c) acc[c] = f32x4m{0.f, 0.f, 0.f, 0.f};
-  auto mma_tile = [&](int t, const Tile& T) {
-    const int kb = t * BK + 8 * lk;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const float4 a = (kb + 4 * q < K) ? T.a[q] : zero4();
-      const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          const float wv = j == 0 ? T.w[c][q].x : j == 1 ? T.w[c][q].y : j == 2 ? T.w[c][q].z : T.w[c][q].w;
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv, acc[c], 0, 0, 0);
-        }
-    }
-  };
-  Tile T[D];
-#pragma unroll
-  for (int b = 0; b < D; ++b) load_tile(b, T[b]);
-  // epilogue operands of fc1 and fc2's weights: requested behind the first tiles, long before they are needed
-  float bias[CW], bias2[CW];
-#pragma unroll
-  for (int c = 0; c < CW; ++c) {
-    const int n = min(16 * (CW * ks + c) + li, N - 1);
-    bias[c] = g.bias ? g.bias[n] : 0.f;
-    bias2[c] = g.bias2 ? g.bias2[n] : 0.f;
-  }
-  uint8_t v2[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) v2[q] = g.bias2 ? g.bias2_valid[min(m0 + 4 * lk + q, M - 1)] : 0;
-  int t = 0;
-  for (; t + D <= nkt; t += D) {
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      mma_tile(t + b, T[b]);
-      __builtin_amdgcn_sched_barrier(0);
-      load_tile(t + b + D, T[b]);  // (past the end: a redundant reload of the last tile)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < D; ++b)
-    if (t + b < nkt) mma_tile(t + b, T[b]);
-  // fc2's operands of this wavefront's column subtiles (the same CW ks .. of fc2's output columns)
-  const int K2 = N, nch2 = K2 / 4;
-  float4 w2[CW][NS2];
-  float b2[CW];
-#pragma unroll
-  for (int c = 0; c < CW; ++c) {
-    const int n2 = min(16 * (CW * ks + c) + li, f.n - 1);
-    const float* row = f.w + (int64_t)n2 * f.ldw;
-    b2[c] = f.bias ? f.bias[n2] : 0.f;
-#pragma unroll
-    for (int s_ = 0; s_ < NS2; ++s_) {
-      const float4 v = ldg4(row + 4 * min(lk + 4 * s_, nch2 - 1));
-      w2[c][s_] = (lk + 4 * s_ < nch2) ? v : zero4();
-    }
-  }
-  int crow2[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int64_t mm = min(m0 + 4 * lk + q, M - 1);
-    crow2[q] = (f.c2 && m0 < f.c2_m) ? f.c2_rows[min(mm, f.c2_m - 1)] : -1;
-  }
-  // t = relu(alpha (acc + b1 + valid c1)); the tile goes to LDS (columns past N: zeros - they are fc2's k range too)
-#pragma unroll
-  for (int c = 0; c < CW; ++c) {
-    const int n = 16 * (CW * ks + c) + li;
-    if (n >= 16 * CT) continue;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float x = g.alpha * (acc[c][q] + bias[c] + (v2[q] ? bias2[c] : 0.f));
-      if (g.relu) x = fmaxf(x, 0.f);
-      ts[4 * lk + q][n] = n < N ? x : 0.f;
-      if (g.c && n < N && m0 + 4 * lk + q < M) g.c[(m0 + 4 * lk + q) * g.ldc + n] = x;  // (t itself, when somebody reads it)
-    }
-  }
-  __syncthreads();
-  // ---- fc2 on the tile: h[16, n2] = t W2^T + b2, this wavefront's column subtiles (their MFMA chains interleaved)
-  f32x4m a2[CW];
-#pragma unroll
-  for (int c = 0; c < CW; ++c) a2[c] = f32x4m{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s_ = 0; s_ < NS2; ++s_) {
-    const int kk = 4 * min(lk + 4 * s_, (16 * CT) / 4 - 1);
-    const float4 x = *reinterpret_cast<const float4*>(&ts[li][kk]);
-    const bool lv = lk + 4 * s_ < nch2;
-    const float av[4] = {lv ? x.x : 0.f, lv ? x.y : 0.f, lv ? x.z : 0.f, lv ? x.w : 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        const float wv = j == 0 ? w2[c][s_].x : j == 1 ? w2[c][s_].y : j == 2 ? w2[c][s_].z : w2[c][s_].w;
-        a2[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv, a2[c], 0, 0, 0);
-      }
-  }
-#pragma unroll
-  for (int c = 0; c < CW; ++c) {
-    const int n2 = 16 * (CW * ks + c) + li;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t mm = m0 + 4 * lk + q;
-      const float hv = a2[c][q] + b2[c];
-      if (n2 < f.n && mm < M) {
-        f.c[mm * f.ldc + n2] = hv;
-        if (crow2[q] >= 0 && mm < f.c2_m) f.c2[(int64_t)crow2[q] * f.ldc2 + n2] = hv;
-      }
-    }
-  }
-}
-template <class R, int CT>
-__global__ void __launch_bounds__(256) k_gemm_ks16_fc2(GemmArgs g, Fc2Fuse f, R r) {
-  __shared__ float t_raw[16 * (16 * CT + 4)];
   const unsigned own = gridDim.x - r.blocks;  // persistent blocks of the product; riders behind them
   if (blockIdx.x >= own) {
     r.run(blockIdx.x - own);
     return;
   }
-  int64_t M = g.m_cap;
-  if (g.m_dev) M = min(M, (int64_t)*g.m_dev);
-  if (M <= 0) return;
-  const int64_t total = (M + 15) / 16;
-  const int64_t per = (total + 7) / 8;  // XCD x works through the chunk [x per, (x + 1) per) of the row tiles
-  for (int64_t jx = blockIdx.x >> 3; jx < per; jx += own >> 3) {
-    const int64_t b = (int64_t)(blockIdx.x & 7) * per + jx;
-    if (b >= total) break;
-    gemm_ks16_fc2_tile<CT>(g, f, M, b * 16, t_raw);
-    __syncthreads();  // the LDS tiles are re-used by the next row tile
-  }
+  gemm_ks16_blocks<RT, CT, NW>(g, blockIdx.x, own, sc_raw);
 }
 
 // Is the product one for k_gemm_ks16?  Long K, plain epilogue (+ second bias), few enough 48 x 48 tiles that the blocks
@@ -1661,17 +1254,13 @@ static bool plain_epilogue(const GemmArgs& g) {
   return !g.ask_part && g.nbatch == 1 && !g.w_kmajor && !g.bias_rs && !g.row_valid && !g.relu_mask && !g.accumulate;
 }
 static unsigned rider_blocks(int64_t live, int threads, int64_t rows);  // (below, with gemm_launch)
-static bool ks16_second_ok(const GemmArgs* s);
-static unsigned ks16_second_blocks(const GemmArgs& s);
 struct NoRider {  // (k_gemm_ks16 without riders)
   unsigned blocks;
   __device__ __forceinline__ void run(unsigned) const {}
 };
-bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode, const GemmArgs* second,
-                      bool* second_rode) {
+bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode) {
   static const int knob = env_int("TG_GEMM_KS16", 1);
   if (rode) *rode = false;
-  if (second_rode) *second_rode = false;
   if (!knob || g.m_cap <= 0 || !plain_epilogue(g) || g.c_rows || g.c2 || (g.k % 4) || (g.a0.w % 4) || (g.ldw % 4) ||
       g.a0.w + (g.a1.p ? g.a1.w : 0) != g.k)
     return false;
@@ -1692,16 +1281,15 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
   static const int gdbg16 = env_int("TG_GEMM_DBG", 0) & 16;  // diagnostic: phase stamps
   gd.dbg = (gdbg16 && phase_selected(g)) ? 16 : 0;
   const NoRider nr{0u};
-  const NoSecond ns{0u};
   if (ct != 3) {
     // (rows per block: 16 when that fits the chip at once, else 32)
     const bool r1 = cdiv(g.m_cap, 16) * ntc <= 256;
     if (ct == 4) {
-      if (r1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 4, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
-      else TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 4, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
+      if (r1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 4, 4>), dim3(256), dim3(256), 0, st, gd, nr);
+      else TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 4, 4>), dim3(256), dim3(256), 0, st, gd, nr);
     } else {
-      if (r1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 7, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
-      else TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 7, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
+      if (r1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 7, 4>), dim3(256), dim3(256), 0, st, gd, nr);
+      else TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 7, 4>), dim3(256), dim3(256), 0, st, gd, nr);
     }
     return true;
   }
@@ -1719,67 +1307,16 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
       const int64_t live = std::min<int64_t>(256, cdiv(g.m_cap, 16 * rt) * nt48);
       wr.blocks = rider_blocks(live, 256, 2 * wr.a.B);
       wr.last = 1u;
-      // (second product: plain epilogue, A of up to four segments, K a multiple of 4, final values)
-      const bool two = second_rode && ks16_second_ok(second);
-      if (two) {
-        Ks16Second s2{*second, 0u, 0u};
-        s2.g.dbg = 0;
-        // TG_KS16_SECOND (tuning knob): 0 = co-resident blocks of the second product, 1 = the same blocks, afterwards
-        static const int seq_knob = env_int("TG_KS16_SECOND", 1);
-        s2.seq = seq_knob == 1 ? 1u : 0u;
-        s2.blocks = s2.seq ? 0u : ks16_second_blocks(*second);
-        const dim3 gr2(256 + s2.blocks + wr.blocks);
-        TG_KLAUNCH((k_gemm_ks16<WbRider, 3, 3, 4, Ks16Second>), gr2, dim3(256), 0, st, gd, wr, s2);
-        *second_rode = true;
-      } else {
-        const dim3 gr(256 + wr.blocks);
-        TG_KLAUNCH((k_gemm_ks16<WbRider, 3, 3, 4>), gr, dim3(256), 0, st, gd, wr, ns);
-      }
+      const dim3 gr(256 + wr.blocks);
+      TG_KLAUNCH((k_gemm_ks16<WbRider, 3, 3, 4>), gr, dim3(256), 0, st, gd, wr);
       *rode = true;
       return true;
     }
   }
-  if (knob == 8) TG_KLAUNCH((k_gemm_ks16<NoRider, 3, 3, 8>), dim3(256), dim3(512), 0, st, gd, nr, ns);
-  else if (rt == 1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
-  else if (rt == 2) TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
-  else TG_KLAUNCH((k_gemm_ks16<NoRider, 3, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr, ns);
-  return true;
-}
-
-// fc1 + fc2 in one launch (k_gemm_ks16_fc2): g = fc1 (long K, plain epilogue + second bias, N <= 176), g2 = fc2 over fc1's
-// output (K = g.n, plain epilogue, optionally the second scattered destination); one round of 16-row blocks that leaves
-// CUs for the riders.  MEASURED at C2 (1x MI355X, 100 replays): parity-green and SLOWER - the launch takes 47 us against
-// 23.2 + 10.3 us for the two (step 0.0994 against 0.0850 ms); as a K split over the four wavefronts with all 11 subtiles per
-// wavefront (512 registers, spills) 37.5 us.  A block of 16 whole rows reads ALL of W1f (828 KB) for 16 x 176 outputs - 1.6 x
-// the operand bytes per flop of the 48 x 48 blocks (159 MB against 118 MB per launch through the CUs' memory paths), and
-// that traffic, not the launch count, bounds fc1 at this size.  Opt-in: TG_FC12=1.
-bool gemm_fc12_launch(const GemmArgs& g, const GemmArgs& g2, hipStream_t st, const WbRider* rider, bool* rode) {
-  static const int knob = env_int("TG_FC12", 0);  // tuning knob (default off, see above)
-  if (rode) *rode = false;
-  if (!knob || g.m_cap <= 0 || !plain_epilogue(g) || g.c_rows || g.c2 || (g.k % 4) || (g.a0.w % 4) || (g.ldw % 4) ||
-      g.a0.w + (g.a1.p ? g.a1.w : 0) != g.k || g.k < 512)
-    return false;
-  if (g.n > 176 || g.n <= 112 || (g.n % 4)) return false;  // (narrower outputs: the 48 / 112-column blocks of k_gemm_ks16)
-  if (!plain_epilogue(g2) || g2.bias2 || g2.c_rows || g2.a1.p || g2.a0.idx || g2.relu || g2.alpha != 1.f || g2.k != g.n ||
-      g2.n > 176 || (g2.ldw % 4) || g2.m_cap != g.m_cap || g2.m_dev != g.m_dev || g2.a0.p != g.c)
-    return false;
-  const int64_t tiles = cdiv(g.m_cap, 16);
-  if (tiles > 232 || tiles < 128) return false;  // one round with CUs to spare; few tiles: the 48-column blocks fill more CUs
-  GemmArgs gd = g;
-  gd.dbg = 0;
-  gd.c = nullptr;  // t itself has no other reader
-  Fc2Fuse f{g2.w, g2.ldw, g2.bias, g2.c, g2.ldc, g2.n, g2.c2, g2.c2_rows, g2.c2_m, g2.ldc2};
-  const unsigned own = (unsigned)(8 * cdiv(tiles, 8));
-  if (rider && rode) {
-    WbRider wr = *rider;
-    wr.blocks = rider_blocks(own, 256, 2 * wr.a.B);
-    wr.last = 1u;
-    TG_KLAUNCH((k_gemm_ks16_fc2<WbRider, 11>), dim3(own + wr.blocks), dim3(256), 0, st, gd, f, wr);
-    *rode = true;
-  } else {
-    const NoRider nr{0u};
-    TG_KLAUNCH((k_gemm_ks16_fc2<NoRider, 11>), dim3(own), dim3(256), 0, st, gd, f, nr);
-  }
+  if (knob == 8) TG_KLAUNCH((k_gemm_ks16<NoRider, 3, 3, 8>), dim3(256), dim3(512), 0, st, gd, nr);
+  else if (rt == 1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr);
+  else if (rt == 2) TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr);
+  else TG_KLAUNCH((k_gemm_ks16<NoRider, 3, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr);
   return true;
 }
 
@@ -1863,28 +1400,15 @@ static unsigned rider_blocks(int64_t live, int threads, int64_t rows) {
 static void collate_blocks(CollateRider& c) {
   const int64_t Q = 3 * c.s.B;
   const int64_t sg = cdiv(Q, (int64_t)16), cg = cdiv(Q * (c.cr.m.d / 4), (int64_t)256);
-  c.sblocks = (c.parts == 2) ? 0u : (unsigned)std::min<int64_t>(sg, 1024);
-  c.cr.blocks = (c.parts == 1) ? 0u : (unsigned)std::min<int64_t>(cdiv(cg, (int64_t)4), 512);
+  c.sblocks = (unsigned)std::min<int64_t>(sg, 1024);
+  c.cr.blocks = (unsigned)std::min<int64_t>(cdiv(cg, (int64_t)4), 512);
   c.blocks = (c.sblocks + c.cr.blocks + 7u) & ~7u;
   c.last = 1u;
 }
 
-// may the product ride as k_gemm_ks16 blocks (plain epilogue, final values, A of two to four segments)?
-static bool ks16_second_ok(const GemmArgs* s) {
-  return s && s->m_cap > 0 && plain_epilogue(*s) && !s->c_rows && !s->c2 && !(s->k % 4) && !(s->a0.w % 4) && !(s->a1.w % 4) &&
-         !(s->a2.w % 4) && !(s->ldw % 4) && s->a0.w + s->a1.w + s->a2.w + s->a3.w == s->k && s->a0.p && (s->a1.p || !s->a1.w) &&
-         (s->a3.p || !s->a3.w);
-}
-static unsigned ks16_second_blocks(const GemmArgs& s) {
-  const int64_t rows2 = s.m_hint > 0 ? std::min(s.m_hint, s.m_cap) : s.m_cap;
-  return (unsigned)std::min<int64_t>(256, 8 * cdiv(cdiv(rows2, 48) * cdiv(s.n, 48), 8));
-}
-int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode, const CollateRider* collate,
-                const GruTail* tail, const GemmArgs* second) {
+int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode, const CollateRider* collate) {
   if (rode) *rode = false;
-  if ((rider || collate || tail || second) &&
-      (!rode || ((rider != nullptr) + (collate != nullptr) + (tail != nullptr) + (second != nullptr) > 1)))
-    return TG_EINVAL;
+  if ((rider || collate) && (!rode || (rider && collate))) return TG_EINVAL;
   if (g.c2 && (g.bias_rs || g.bias2 || g.row_valid || g.relu_mask || g.c_rows || g.accumulate || !g.c2_rows || g.nbatch != 1))
     return TG_EINVAL;  // the second destination exists in the plain epilogue only
   if (g.m_cap <= 0) return TG_OK;
@@ -1897,7 +1421,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
             g.a0.idx != nullptr, g.relu, g.relu_mask != nullptr, g.accumulate, g.c_rows != nullptr, g.bias2 != nullptr, g.bias_rs != nullptr);
   if (g.a0.w + (g.a1.p ? g.a1.w : 0) != g.k) return TG_EINVAL;
   // long K, few tiles: LDS-free K-split blocks (k_gemm_ks16)
-  if (!rider && !collate && !tail && !second && !g.bias2 && gemm_ks16_launch(g, st)) return check_launch("gemm(ks16)");
+  if (!rider && !collate && !g.bias2 && gemm_ks16_launch(g, st)) return check_launch("gemm(ks16)");
   constexpr int BM = 64, BN = 64;
   const int64_t MT = cdiv(g.m_cap, BM);
   const int NT = (int)cdiv(g.n, BN);
@@ -1986,14 +1510,6 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       const bool ride = nsl <= 11;  // (the K <= 192 instance hosts no riders)
       CollateRider co = (collate && ride) ? *collate : CollateRider{};
       WbRider wr = (rider && ride) ? *rider : WbRider{};
-      GruTail tl = (tail && ride && (int)cdiv(cdiv(tail->d, 4), 4) == nsl) ? *tail : GruTail{};
-      if (tl.cap > 0) tl.blocks = gru_tail_blocks(tl);
-      GiRider gi{};
-      if (ride && ks16_second_ok(second)) {
-        gi.g = *second;
-        gi.g.dbg = 0;
-        gi.blocks = ks16_second_blocks(*second);
-      }
       if (collate && ride) collate_blocks(co);
       if (rider && ride) {
         wr.blocks = rider_blocks(std::min<int64_t>(tiles64, 256), 256, 2 * wr.a.B);
@@ -2001,14 +1517,10 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       } else {
         no_ride();
       }
-      const dim3 gr(own + co.blocks + wr.blocks + tl.blocks + gi.blocks);
+      const dim3 gr(own + co.blocks + wr.blocks);
 #define TG_DIRECT(NS_)                                                                                                  \
   do {                                                                                                                  \
-    if (gi.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<GiRider, NS_, 2, 3>), gr, dim3(256), 0, st, gd, gi);       \
-    else if (gi.blocks) TG_KLAUNCH((k_gemm_direct_r<GiRider, NS_, 2, 2>), gr, dim3(256), 0, st, gd, gi);         \
-    else if (tl.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<GruTail, NS_, 2, 3>), gr, dim3(256), 0, st, gd, tl);  \
-    else if (tl.blocks) TG_KLAUNCH((k_gemm_direct_r<GruTail, NS_, 2, 2>), gr, dim3(256), 0, st, gd, tl);         \
-    else if (wr.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<WbRider, NS_, 2, 3>), gr, dim3(256), 0, st, gd, wr);      \
+    if (wr.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<WbRider, NS_, 2, 3>), gr, dim3(256), 0, st, gd, wr);      \
     else if (wr.blocks) TG_KLAUNCH((k_gemm_direct_r<WbRider, NS_, 2, 2>), gr, dim3(256), 0, st, gd, wr);        \
     else if (co.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<CollateRider, NS_, 2, 3>), gr, dim3(256), 0, st, gd, co); \
     else if (co.blocks) TG_KLAUNCH((k_gemm_direct_r<CollateRider, NS_, 2, 2>), gr, dim3(256), 0, st, gd, co);   \
@@ -2019,7 +1531,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       else if (nsl <= 11) TG_DIRECT(11);
       else TG_KLAUNCH((k_gemm_direct<12, 2, 2>), dim3(own), dim3(256), 0, st, gd);
 #undef TG_DIRECT
-      if (((collate || rider) && ride) || tl.blocks || gi.blocks) *rode = true;
+      if ((collate || rider) && ride) *rode = true;
       return check_launch("gemm(direct)");
     }
   }

@@ -1,8 +1,7 @@
 // The fused GRU cell on the float32 MFMA: gates in the GEMM epilogue (a15).
 // Reference: nn.GRUCell as used at tiger/model/update_modules.py:30-37.
 // Holds the LDS-staged blocks (k_gru<NW, KS> with the 16-column tail gru_tail16), the LDS-free blocks (k_gru_direct,
-// k_gru_direct16) and their dispatcher gru_launch.  The split updater's tail (GruTail) is a rider of k_gemm_direct_r and
-// stays in tg_gemm.hip.
+// k_gru_direct16) and their dispatcher gru_launch.
 #include <cstdlib>
 
 #include "tg_mfma.h"

@@ -450,10 +450,6 @@ int attn_dims_ok(const tg_model* m) {
   return 1;
 }
 
-static int gru_split_knob() {
-  static const int k = env_int("TG_GRU_SPLIT", 0);  // tuning knob (0 = off, the default)
-  return k;
-}
 static bool carve_attn(const tg_model* m, int64_t Q, Carver& cv, AttnWs& w) {
   const int d = m->d, kvw = 2 * m->d + m->d_e, nh = m->n_head;
   w.cc = cv.take<float>((size_t)Q * d);
@@ -549,55 +545,6 @@ void launch_attn_core(const tg_model* m, int64_t Q, const float* ts, const int64
 #undef TG_CORE
 }
 
-// ---- side lane: a second HIP stream per device for work that is independent of the launches beside it -----------------
-// At large batches the step's launches are long and bound by different resources: the products and the updater by the
-// matrix pipe, the write-back and the sampler by memory round trips.  Riders (workgroups of the same launch) were measured
-// to cost such products more than they save (see gemm_launch); a forked stream lets the dispatcher co-schedule the two
-// kernels' workgroups instead.  fork: the lane waits for everything enqueued on `st` so far; join: `st` waits for the lane.
-// Under stream capture (a hipGraph of several steps) the event pair makes the lane part of the capture: a parallel branch
-// of the graph.  The lane is created by the first call outside a capture (every caller runs a step eagerly first).
-// MEASURED at C5 shape (B = 65 536, d = 256, 1x MI355X, 30 steps): NOT faster - 3.905 ms per step against 3.861 ms with
-// everything on one stream: fc1 grows by the write-back's own duration (1.10 -> 1.28 ms), the updater and the query rows
-// by the sampler's (1.13 -> 1.23, 0.40 -> 0.54 ms incl. the centres launch).  The matrix kernels fill the register file
-// (k_gru<4, 1>: 2 x 256 registers per SIMD lane, k_gemm_rb<2, 2>: 2 x 228), so the side kernel's wavefronts only get
-// slots the matrix kernel's blocks give up - time slicing, not overlap.  Hence OFF by default; TG_SIDE_STREAM=1 switches
-// the form on (read at every call: tests/test_hip_timed_form.py runs it against the oracle).
-struct SideLane {
-  hipStream_t s = nullptr;
-  hipEvent_t fork[2] = {nullptr, nullptr}, join[2] = {nullptr, nullptr};
-  bool ok = false;
-};
-static SideLane* side_lane(hipStream_t st) {
-  if (env_int("TG_SIDE_STREAM", 0) == 0) return nullptr;  // tuning knob (read per call; default off, see above)
-  static SideLane lanes[16];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  SideLane& L = lanes[dev];
-  if (L.ok) return &L;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-    (void)hipGetLastError();
-    return nullptr;  // not now: no stream / event is created inside a capture
-  }
-  bool good = hipStreamCreateWithFlags(&L.s, hipStreamNonBlocking) == hipSuccess;
-  for (int i = 0; i < 2 && good; ++i)
-    good = hipEventCreateWithFlags(&L.fork[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&L.join[i], hipEventDisableTiming) == hipSuccess;
-  if (!good) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  L.ok = true;
-  return &L;
-}
-static bool lane_fork(SideLane* L, int i, hipStream_t st) {
-  return hipEventRecord(L->fork[i], st) == hipSuccess && hipStreamWaitEvent(L->s, L->fork[i], 0) == hipSuccess;
-}
-static bool lane_join(SideLane* L, int i, hipStream_t st) {
-  return hipEventRecord(L->join[i], L->s) == hipSuccess && hipStreamWaitEvent(st, L->join[i], 0) == hipSuccess;
-}
-// the write-back rider's pass (STEP 4-5 and the bookkeeping of STEP 6: writeback_fused_body<false>) as a launch of its own
-__global__ void __launch_bounds__(256) k_wb_rider(WbRider r) { r.run(blockIdx.x); }
 constexpr int64_t SIDE_MIN_B = 16384;  // batches above this: launches that host no riders (gemm_launch, step_forward)
 
 static void launch_centres(const tg_model* m, int64_t Q, const int64_t* nids, const float* reprs, const uint64_t* bm,
@@ -620,8 +567,7 @@ static int attn_forward_fused(const tg_model* m, int64_t Q, const int64_t* nids,
                               const int64_t* l1_nids, const int64_t* l1_eids, const float* l1_ts, const float* reprs,
                               const uint64_t* bm, const uint32_t* rank, float* out, const AttnWs& w, hipStream_t st,
                               tg_profiler* pf, const PosArgs* pos, const DirectArgs* da, bool centres_done,
-                              const float* key_rows, bool use_gtab, const WbRider* wbr, bool* wb_rode, GruSplit* gs,
-                              const CollateRider* sampler, bool* sampler_rode) {
+                              const float* key_rows, bool use_gtab, const WbRider* wbr, bool* wb_rode) {
   // stage numbering of the profiler is kept: q -> "merged q+g", g -> skipped, v/out -> skipped, fc1 -> fused
   int stage = ST_ATTN_FIRST + 1;
   const int d = m->d;
@@ -674,46 +620,11 @@ static int attn_forward_fused(const tg_model* m, int64_t Q, const int64_t* nids,
   // short-K product
   SkPlan sk{};
   KSlot ks_fc1(KT_FC1);
-  {
-    // fc1 and fc2 as ONE launch where the batch makes 128 .. 232 blocks of 16 whole rows (C2: 192; tg_gemm.hip:
-    // k_gemm_ks16_fc2): fc2 runs as the epilogue of the block that owns the rows, STEP 6's rows leave it, the write-back
-    // rider takes the CUs the product leaves idle
-    const bool ext12 = wbr && wbr->planned0;
-    const bool own12 = !ext12 && wbr && pos && pos->win_row;
-    GemmArgs g2{};
-    g2.m_cap = Q; g2.n = d; g2.k = d;
-    g2.a0 = ASeg{w.t, d, d, nullptr};
-    g2.w = m->attn_fc2.w; g2.ldw = d; g2.bias = m->attn_fc2.b;
-    g2.c = out; g2.ldc = d; g2.alpha = 1.f; g2.nbatch = 1;
-    if (own12) { g2.c2 = m->left_vals; g2.c2_rows = pos->win_row; g2.c2_m = 2 * wbr->a.B; g2.ldc2 = d; }
-    bool rode12 = false;
-    if (!gs && !sampler && gemm_fc12_launch(g, g2, st, (ext12 || own12) ? wbr : nullptr, &rode12)) {
-      prof_mark(pf, stage++, st);
-      if (wb_rode) *wb_rode = rode12;
-      return check_launch("tg_temporal_attn_fwd(fused, fc1 + fc2)");
-    }
-  }
   bool wb_on_fc1 = false;  // the write-back rider on the fc1 launch: then fc2 only stores STEP 6's rows (c2)
-  bool gi_rode = false;  // the split updater's input-side product as a second problem of this launch (variant 1)
   const bool ext = wbr && wbr->planned0;  // a caller's rider (tg_part_step): hosted like the write-back rider, no second row copy
-  const bool ks16 = gemm_ks16_launch(g, st, (ext || (wbr && pos && pos->win_row)) ? wbr : nullptr, &wb_on_fc1,
-                                     (gs && gs->variant == 1) ? &gs->gi : nullptr, &gi_rode);
+  const bool ks16 = gemm_ks16_launch(g, st, (ext || (wbr && pos && pos->win_row)) ? wbr : nullptr, &wb_on_fc1);
   const bool pieces = !ks16 && gemm_sk_partials(g, w.sk, TG_SK_WS_FLOATS, st, &sk);
-  // large batch (this product hosts no rider): the write-back rider as a launch of its own on the side lane, beside this
-  // product - STEP 4-5 read the snapshot and the winners the core's launch left, nothing this product touches - joined in
-  // front of fc2, whose epilogue stores STEP 6's rows
-  SideLane* lane = nullptr;
-  bool wb_side = false;
-  if (!ks16 && !pieces && !ext && wbr && pos && pos->win_row && !gs && wbr->a.B > SIDE_MIN_B && (lane = side_lane(st)) != nullptr) {
-    if (!lane_fork(lane, 0, st)) return TG_EHIP;
-    WbRider wr = *wbr;
-    wr.blocks = flat_grid(2 * wr.a.B, 4);
-    wr.last = 0u;
-    hipLaunchKernelGGL(k_wb_rider, dim3(wr.blocks), dim3(256), 0, lane->s, wr);
-    wb_side = true;
-  }
   if (!ks16 && !pieces && (rc = gemm_launch(g, st)) != TG_OK) return rc;
-  if (wb_side && !lane_join(lane, 0, st)) return TG_EHIP;
   prof_mark(pf, stage++, st);
   KSlot ks_fc2(KT_FC2);
   g = GemmArgs{};
@@ -733,34 +644,8 @@ static int attn_forward_fused(const tg_model* m, int64_t Q, const int64_t* nids,
   } else {
     wbr = nullptr;
   }
-  if (wb_on_fc1 && gs && gs->variant == 2) {
-    // ... and the split updater's W_ih msg shares THIS launch (variant 2): fc2's 144 blocks leave 112 CUs idle at C2 and its
-    // other blocks finish early; the tail then is a short launch of its own behind it (step_writeback_b)
-    bool gi_here = false;
-    if ((rc = gemm_launch(g, st, nullptr, &gi_here, nullptr, nullptr, &gs->gi)) != TG_OK) return rc;
-    gs->gi_done = gi_here;
-    rode = true;
-  } else if (wb_on_fc1 && gi_rode) {  // ... and the updater's tail shares this launch (it reads t, like fc2)
-    bool tail_rode = false;
-    if ((rc = gemm_launch(g, st, nullptr, &tail_rode, nullptr, &gs->tail)) != TG_OK) return rc;
-    if (!tail_rode && (rc = gru_tail_launch(gs->tail, st)) != TG_OK) return rc;
-    gs->done = true;
-    rode = true;
-  } else if (wb_side) {  // STEP 4-5 ran beside fc1 (side lane): this product only stores STEP 6's rows (c2)
+  if (wb_on_fc1) {  // ... or rode on fc1's already: this product only stores STEP 6's rows (c2)
     if ((rc = gemm_launch(g, st)) != TG_OK) return rc;
-    rode = true;
-  } else if (wb_on_fc1) {  // ... or rode on fc1's already: this launch is free to host the NEXT batch's sampler (collate
-    // prefetch; the stream offset has been advanced on fc1's launch, nothing from here on reads this batch's query arrays
-    // or neighbour lists)
-    bool srode = false;
-    if (sampler && !ext) {
-      CollateRider cs = *sampler;
-      cs.parts = 1u;
-      if ((rc = gemm_launch(g, st, nullptr, &srode, &cs)) != TG_OK) return rc;
-    } else if ((rc = gemm_launch(g, st)) != TG_OK) {
-      return rc;
-    }
-    if (sampler_rode) *sampler_rode = srode;
     rode = true;
   } else if ((rc = gemm_launch(g, st, wbr, &rode)) != TG_OK) {
     return rc;
@@ -774,18 +659,15 @@ int attn_forward(const tg_model* m, int64_t Q, const int64_t* nids, const float*
                  const uint32_t* rank, float* out, const AttnWs& w, hipStream_t st, tg_profiler* pf = nullptr,
                  const DropCfg* drop = nullptr, const PosArgs* pos = nullptr, const DirectArgs* da = nullptr,
                  const float* key_rows = nullptr, bool centres_done = false, bool use_gtab = false,
-                 const WbRider* wbr = nullptr, bool* wb_rode = nullptr, GruSplit* gs = nullptr,
-                 const CollateRider* sampler = nullptr, bool* sampler_rode = nullptr) {
+                 const WbRider* wbr = nullptr, bool* wb_rode = nullptr) {
   if (wb_rode) *wb_rode = false;
-  if (sampler_rode) *sampler_rode = false;
-  if (gs) gs->done = false;
   const DropCfg dc = drop ? *drop : DropCfg{};
   int stage = ST_ATTN_FIRST;
   prof_mark(pf, stage++, st);
   const int d = m->d, d_e = m->d_e, kvw = 2 * d + d_e, nh = m->n_head, dh = 2 * d / nh, E = 2 * d;
   if (m->attn_fused && dc.p == 0.f)  // (the pre-multiplied weights do not care where the node part of a key row comes from)
     return attn_forward_fused(m, Q, nids, ts, l1_nids, l1_eids, l1_ts, reprs, bm, rank, out, w, st, pf, pos, da, centres_done,
-                              key_rows, use_gtab && m->g_table && !key_rows, wbr, wb_rode, gs, sampler, sampler_rode);
+                              key_rows, use_gtab && m->g_table && !key_rows, wbr, wb_rode);
   const int qblocks = (int)cdiv(2 * d, 4);
   if (da) {  // the constant half of the query projection from the rank-form kernel (no centre rows), then the direct centres
     hipLaunchKernelGGL(k_attn_centres, dim3(1 + qblocks), dim3(256), 0, st, (int64_t)0, d / 4, nids, (const float4*)reprs, bm,
@@ -1334,15 +1216,6 @@ bool carve_step(const tg_model* m, int64_t B, Carver& cv, StepWs& w, int n_layer
     w.emb2 = cv.take<float>(Q2 * m->d);
     if (!carve_attn(m, (int64_t)Q2, cv, w.attn2)) return false;
   }
-  // the split updater's buffers (TG_GRU_SPLIT, off by default and measured not faster: DESIGN.md s0.1 of round 4) are carved
-  // - and the centres pass stores the 2B time-encoding rows into them - only when the knob is set (static per process, so a
-  // prefetched collate sees the same choice): 0.5 GB of workspace and 2B x d dead stores per step at C5 shape otherwise
-  if (gru_split_knob()) {
-    w.snap_te = cv.take<float>((size_t)2 * B * m->d);
-    w.oth = cv.take<int64_t>((size_t)2 * B);
-    w.weid = cv.take<int64_t>((size_t)2 * B);
-    w.gi = cv.take<float>((size_t)2 * B * 3 * m->d);
-  }
   return cv.ok;
 }
 // the carve above on a dry run: workspace size and the must-be-zero prefix without a second copy of the layout
@@ -1414,7 +1287,6 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
                  tg_profiler* pf, const DropCfg* drop, bool eager) {
   w.eager = eager;
   w.wb_rode = false;
-  w.upd_done = false;
   const tg_model* inner = w.h2n ? io->inner : nullptr;  // two attention layers (the workspace was carved for them)
   const int64_t B = io->B, Q = 3 * B, K = m->n_neighbors, cap = involved_cap(m, B, inner ? 2 : 1);
   prof_mark(pf, ST_QUERIES, st);
@@ -1452,19 +1324,6 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   // (not with io->h_new: those rows are read from the tables after the attention block, i.e. before STEP 4 must run)
   const bool want_rider = w.fused_wb && wbr_knob != 0 && !drop && !io->h_new;
   if (want_rider) pos.win_row = w.win_row;
-  // split updater (tg_dense.h: GruTail; VERDICT r03 task 1a): the updater's input-side product W_ih msg - 80 % of its flops,
-  // independent of the attention block - leaves the updater launch.  Needs the raw messages as gathered segments of the
-  // snapshot (GRU, no message transform), h = this batch's h(t-) (upd_src = left: fc2's rows), the per-node tables and the
-  // write-back rider's winner lists.  TG_GRU_SPLIT: 1 = W_ih msg as a second problem of fc1's launch + the tail (W_hh h
-  // through the parameter product W_hh W2, gates) on fc2's launch: NO updater launch; 2 = W_ih msg on fc2's launch + the
-  // tail as a short launch behind it.  Both parity-green, both measured NOT faster at C2 (MI355X, 100 replays; 0 / 1 / 2:
-  // 83.7-86.4 / 83.7-85.0 / 86.5-87.8 us per step on three boxes): a 48 x 48 x 688 tile costs its launch 11-14 us wherever
-  // it rides (fc1 25.0 -> 39.5 us, fc2 13.0 -> 24.2 us by HIP events) against the 16.3 us the updater launch gives back,
-  // and one fork / join inside the captured graph costs more than the product (tools/micro/fork_join.py).  Default 0.
-  const int split_knob = gru_split_knob();
-  const float* tail_w = gru_tail_weights(m);
-  const bool split_ok = split_knob != 0 && tail_w && m->upd_fn == TG_UPD_GRU && m->tsfm == TG_TSFM_ID && m->upd_src == TG_SRC_LEFT;
-  if (want_rider && split_ok) { pos.eids = w.eids; pos.oth = w.oth; pos.weid = w.weid; }
   const PosArgs* pp = (io->embed_only && !untouched) ? nullptr : &pos;
   w.gtab = form.gtab;
   // collate prefetch (tg_step_io.prefetch_state): this step runs the NEXT batch's sampler + centres on its last launch;
@@ -1472,10 +1331,7 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   static const int pf_knob = env_int("TG_PREFETCH", 1);
   w.prefetch = pf_knob != 0 && io->prefetch_state && io->stream_len > 0 && io->offset_dev && io->advance && io->ws_is_clean &&
                w.lean && w.gtab && w.fused_wb && !lz && io->strategy == 0 && K <= 16 && !io->l1_nids && !io->l1_eids && !io->l1_ts &&
-               // (large batches: the last product's launch takes no riders, see gemm_launch - the sampler half then runs on
-               // the side lane beside the updater, the centres half behind the query rows: step_writeback_b)
-               (B <= SIDE_MIN_B || (m->c_table && side_lane(st) != nullptr));
-  w.prefetch_side = w.prefetch && B > SIDE_MIN_B;
+               B <= SIDE_MIN_B;  // (large batches: the last product's launch takes no riders, see gemm_launch)
   const int pf_in = io->prefetch_state ? *io->prefetch_state : 0;
   const bool prefetched = w.prefetch && pf_in == 1;
   if (io->prefetch_state) *io->prefetch_state = 0;  // set again by the end of the step, once the rider is enqueued
@@ -1489,8 +1345,6 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   }
   DirectArgs da{w.lean ? nullptr : w.outdated, w.counts + 1, cap, io->err, w.fused_wb ? (float4*)w.snap : nullptr,
                 w.snap_ts, 2 * B, w.lean ? 1 : 0};
-  if (w.fused_wb && split_ok) da.snap_te = (float4*)w.snap_te;  // (whenever the snapshot is taken: a prefetched collate of
-                                                                //  this batch ran before this step chose its form)
   // lean: the centres need nothing the sampler produces and share its launch
   // (with the per-node table of centre rows - tg_model.c_table, a step that uses the query-row table - no per-batch copy
   // of the centre rows is made: the centres pass keeps its checks, the first dedup pass and the snapshot)
@@ -1590,52 +1444,10 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
     wbr.a.snap = w.snap;
     wbr.a.snap_ts = w.snap_ts;
   }
-  GruSplit gs{};
-  gs.variant = split_knob;
-  const bool gsplit = split_knob != 0 && split_ok && want_rider && pp && w.gtab && m->c_table && !lz && !inner && !key_rows;
-  if (gsplit) {
-    const int d = m->d, mw = 3 * d + m->d_e;
-    GemmArgs& gi = gs.gi;  // gi = [snap[index] | snap[oth] | efeat[weid] | snap_te[index]] W_ih^T + b_ih over the winners
-    gi.m_cap = 2 * B; gi.m_dev = w.counts + 2; gi.m_hint = io->rows_hint; gi.n = 3 * d; gi.k = mw;
-    gi.a0 = ASeg{w.snap, d, d, w.index};
-    gi.a1 = ASeg{w.snap, d, d, w.oth};
-    gi.a2 = ASeg{m->efeats, m->d_e, m->d_e, w.weid};  // (no edge table: a slice of zeros)
-    gi.a3 = ASeg{w.snap_te, d, d, w.index};
-    gi.w = m->gru_w_ih; gi.ldw = mw; gi.bias = m->gru_b_ih; gi.c = w.gi; gi.ldc = 3 * d; gi.alpha = 1.f; gi.nbatch = 1;
-    GruTail& t = gs.tail;
-    t.cap = 2 * B; t.n_dev = w.counts + 2; t.d = d; t.t = w.attn.t; t.t_rows = w.index;
-    t.w = tail_w; t.b = tail_w + (size_t)4 * d * d; t.gi = w.gi;
-    t.out = m->pending_vals; t.out_rows = w.upos32; t.out2 = m->c_table; t.add2 = m->nfeats; t.rows_hint = io->rows_hint;
-    if (gs.variant == 2) {  // the tail behind fc2, reading what the reference reads: left[v] and weight_hh / bias_hh
-      t.direct = 1; t.t = m->left_vals; t.t_rows = w.upos; t.w = m->gru_w_hh; t.b = m->gru_b_hh;
-      // ... and W_ih msg over the mailbox rows the write-back rider has just stored (on fc1's launch)
-      static const int box_knob = env_int("TG_GRU_SPLIT_BOX", 1);
-      if (box_knob) {
-        gi.a0 = ASeg{m->msg_vals, mw, mw, w.upos};
-        gi.a1 = gi.a2 = gi.a3 = ASeg{};
-      }
-    }
-  }
-  // collate prefetch: TG_PREFETCH_SPLIT=1 lets the sampler half of the NEXT batch's collate share fc2's launch (it reads the
-  // graph and the stream only) and leaves the centres on the step's last launch.  Parity-green, measured SLOWER at C2 (87.2
-  // against 85.2 us per step on the same box: fc2's launch grows by more than the last launch gives back); default 0
-  static const int pfs_knob = env_int("TG_PREFETCH_SPLIT", 0);
-  CollateRider co_s{};
-  if (w.prefetch && pfs_knob != 0 && !gsplit) {
-    co_s.s = SampleBatchArgs{*g, io->B, io->src, io->dst, io->neg, io->ts, io->eids, (const int64_t*)io->offset_dev,
-                             (int)m->n_neighbors, w.nids3, w.ts3f, w.eids, w.l1n, w.l1e, w.l1t, nullptr, nullptr};
-    co_s.cr = CentresRider{*m, (const float4*)m->nfeats, nullptr, DirectArgs{}, PosArgs{}, 0u};
-    co_s.stream_len = io->stream_len;
-  }
-  w.sampler_rode = false;
   if ((rc = attn_forward(m, Q, w.nids3, w.ts3f, w.l1n, w.l1e, w.l1t, w.reprs, w.bm, w.rank, io->h, w.attn, st, pf,
                          drop, pp, w.direct ? &da : nullptr, key_rows, w.lean && io->strategy == 0 && !lz, w.gtab,
-                         want_rider ? &wbr : w.ext_rider, &w.wb_rode, gsplit ? &gs : nullptr,
-                         (w.prefetch && pfs_knob != 0 && !gsplit) ? &co_s : nullptr, &w.sampler_rode)) != TG_OK)
+                         want_rider ? &wbr : w.ext_rider, &w.wb_rode)) != TG_OK)
     return rc;
-  w.upd_done = gs.done;
-  w.tail_pending = gsplit && gs.variant == 2 && gs.gi_done;
-  if (w.tail_pending) w.tail = gs.tail;
   prof_mark(pf, ST_DEDUP, st);
   if (io->h_new) {  // h(t'+) rows of cat[src, dst]: reprs[local(node)], or the table rows themselves
     if (w.direct)
@@ -1706,8 +1518,8 @@ int step_writeback_a(const tg_model* m, const tg_step_io* io, StepWs& w, hipStre
 __global__ void __launch_bounds__(256) k_collate(CollateRider co) { co.run(blockIdx.x); }
 static void collate_blocks_standalone(CollateRider& c) {
   const int64_t Q = 3 * c.s.B;
-  c.sblocks = c.parts == 2 ? 0u : flat_grid(Q, 16);
-  c.cr.blocks = c.parts == 1 ? 0u : flat_grid(Q * (c.cr.m.d / 4), 256);
+  c.sblocks = flat_grid(Q, 16);
+  c.cr.blocks = flat_grid(Q * (c.cr.m.d / 4), 256);
   c.blocks = c.sblocks + c.cr.blocks;
 }
 
@@ -1718,7 +1530,6 @@ int step_writeback_b(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, 
   prof_mark(pf, ST_WRITE_LEFT, st);
   int rc;
   CollateRider co{};
-  SideLane* lane = nullptr;
   if (w.fused_wb) {
     wa.snap = w.snap;
     wa.snap_ts = w.snap_ts;
@@ -1744,25 +1555,12 @@ int step_writeback_b(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, 
       co.cr = CentresRider{*m, (const float4*)m->nfeats, m->c_table ? (float4*)nullptr : (float4*)w.attn.cc, w.da_args,
                            w.pos_args, 0u};
       co.stream_len = io->stream_len;
-      co.parts = w.sampler_rode ? 2u : 0u;  // (the sampler half rode on fc2's launch already)
     }
     const bool ctab = cr && m->c_table;  // ... or straight into the per-node table of centre rows
-    if (w.prefetch_side && (lane = side_lane(st)) != nullptr) {
-      // the NEXT batch's sampler (graph + stream only) beside the updater and the query rows; it writes the step's query
-      // arrays and neighbour lists, which nothing from here on reads (as with TG_PREFETCH_SPLIT)
-      if (!lane_fork(lane, 1, st)) return TG_EHIP;
-      CollateRider cs = co;
-      cs.parts = 1u;
-      collate_blocks_standalone(cs);
-      hipLaunchKernelGGL(k_collate, dim3(cs.blocks), dim3(256), 0, lane->s, cs);
-      co.parts = 2u;  // the centres half (reads the state the updater is about to finish, and the sampler's query ids)
-    }
     KSlot ks_upd(KT_UPDATER);
-    if (w.tail_pending && (rc = gru_tail_launch(w.tail, st)) != TG_OK) return rc;  // (split updater, variant 2)
-    if (!w.upd_done && !w.tail_pending &&  // (split updater: these rows were finished on fc2's launch)
-        (rc = apply_messages(m, w.upos, w.upos32, n_upos, P, m->pending_vals, io->err, w.apply_ws, w.apply_bytes, st,
-                             true, nullptr, bound, cr ? (ctab ? m->c_table : w.attn.t) : nullptr, cr ? m->nfeats : nullptr,
-                             ctab)) != TG_OK)
+    if ((rc = apply_messages(m, w.upos, w.upos32, n_upos, P, m->pending_vals, io->err, w.apply_ws, w.apply_bytes, st,
+                            true, nullptr, bound, cr ? (ctab ? m->c_table : w.attn.t) : nullptr, cr ? m->nfeats : nullptr,
+                            ctab)) != TG_OK)
       return rc;
   }
   prof_mark(pf, ST_GTAB, st);
@@ -1771,9 +1569,8 @@ int step_writeback_b(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, 
     bool rode = false;
     KSlot ks_q(KT_QROWS);
     if ((rc = gtab_rows(m, 2 * io->B, w.upos, w.upos32, n_upos, w.attn.t, st, m->upd_fn == TG_UPD_GRU,
-                        (w.prefetch && !lane) ? &co : nullptr, &rode, io->rows_hint)) != TG_OK)  // (lane: the centres half waits for the join)
+                        w.prefetch ? &co : nullptr, &rode, io->rows_hint)) != TG_OK)
       return rc;
-    if (lane && !lane_join(lane, 1, st)) return TG_EHIP;
     if (w.prefetch && !rode) {  // this product's kernel does not host riders: the same work as a launch of its own
       collate_blocks_standalone(co);
       hipLaunchKernelGGL(k_collate, dim3(co.blocks), dim3(256), 0, st, co);

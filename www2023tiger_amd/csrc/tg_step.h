@@ -72,38 +72,20 @@ struct StepWs {
   hipEvent_t collate_done;  // nullable, the caller's: recorded right behind the first-hop sampler (the batch's id list exists)
   bool collate_recorded;
   bool prefetch;    // the step runs the collate part of the NEXT batch on its last launch (tg_step_io.prefetch_state)
-  bool prefetch_side;  // ... large batch: its sampler half on the side lane beside the updater, its centres half behind the query rows
   PosArgs pos_args;   // the step's dedup arguments / direct-centres arguments (the prefetch builds the next batch's
   DirectArgs da_args; // centres rider from them at the end of the step)
   // --n_layers 2: second-hop lists of the Q*K neighbour slots, the slots' query times (the roots'), their embeddings
   int64_t *h2n, *h2e;
   float *h2t, *ts2, *emb2;
   AttnWs attn2;
-  // split updater (tg_dense.h: GruTail): time segments of the 2B snapshot positions, the winners' other-endpoint positions
-  // and edge ids, W_ih msg + b_ih of the winners
-  float *snap_te, *gi;
-  int64_t *oth, *weid;
-  bool upd_done;  // the eager updater's rows of this batch were finished inside the attention block's launches
-  bool sampler_rode;  // collate prefetch: the next batch's sampler rode on fc2's launch already (its centres follow on the last)
   const WbRider* ext_rider;  // tg_part_step: the planned write-back's first launch rides on the embedding step's fc1 / fc2
-  bool tail_pending;  // ... or their input-side product was (on fc2's launch): the tail is launched where the updater was
-  GruTail tail;
 };
-// one step's plan of the split updater: the second problem of fc1's launch and the tail on fc2's (attn_forward_fused)
-struct GruSplit {
-  GemmArgs gi;
-  GruTail tail;
-  int variant;   // 1: gi on fc1's launch + tail on fc2's (pre-multiplied W_hh W2); 2: gi on fc2's launch + the tail behind it
-  bool gi_done;  // variant 2: gi rode on fc2's launch
-  bool done;     // variant 1: the rows are finished
-};
-const float* gru_tail_weights(const tg_model* m);
 // tg_stream_step with a rider handed in by the caller (tg_part_step; *rode: whether a launch of the step hosted it)
 int stream_step_ext(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, void* ws, size_t ws_bytes, hipStream_t st,
                     const WbRider* ext_rider, bool* rode);
 // the eager updater over a list of state rows (tg_part_step): pending[rows32[i]] = updater(upd memory, mailbox)[rows[i]]
 int apply_messages_rows(const tg_model* m, const int64_t* rows, const int32_t* rows32, const int32_t* n_dev, int64_t cap,
-                        uint32_t* err, void* ws, size_t ws_bytes, hipStream_t st);  // the tail of the tg_attn_fuse blob, or nullptr (tg_fuse.hip)
+                        uint32_t* err, void* ws, size_t ws_bytes, hipStream_t st);
 
 bool carve_step(const tg_model* m, int64_t B, Carver& cv, StepWs& w, int n_layers = 1);
 int attn_dims_ok(const tg_model* m);

@@ -510,8 +510,8 @@ class TIGE(nn.Module):
         return super().train(mode)
 
     def _attn_stamp(self):
-        """versions of everything the pre-multiplied weights are made of: attention + time encoder, and - the blob's tail
-        for the split updater, W_hh W2 (csrc/tg_dense.h: GruTail) - the updater's parameters; + the parameter epoch (train())"""
+        """versions of everything the pre-multiplied weights and the per-node tables built from them are made of: attention +
+        time encoder, the updater's parameters (the table rows are updater outputs); + the parameter epoch (train())"""
         pl = self._param_lists()
         return [p._version for p in pl[1]] + [p._version for p in pl[0]] + [getattr(self, '_param_epoch', 0)]
 

@@ -28,10 +28,11 @@ def dev():
 
 
 def build(nh, d, d_e, *, nfeats=True, efeats=True, restarter='static', H=None, L=1, K=10, E=200, n_u=40, n_i=15,
-          T=5000.0, seed=0, msg_src='left', upd_src='right'):
+          T=5000.0, seed=0, msg_src='left', upd_src='right', hit='bin', strategy='recent_edges', edit=None):
     """A HIP model of the given head count and widths on a synthetic stream (bench.make_stream) and the oracle carrying
     the same weights.  nfeats: a random node-feature table (else none); efeats: an edge-feature table of width d_e (else
-    none, and the model's edge width is d)."""
+    none, and the model's edge width is d).  hit: the score head's hit features; strategy: the sampling strategy of both
+    graphs; edit(st): changes the stream in place before the graphs are built from it."""
     import bench
     from oracle import tiger_oracle as O
     from www2023tiger_amd.data.graph import Graph
@@ -39,8 +40,10 @@ def build(nh, d, d_e, *, nfeats=True, efeats=True, restarter='static', H=None, L
     from www2023tiger_amd.model.restarters import SeqRestarter, StaticRestarter
     from www2023tiger_amd.model.tiger import TIGER
     st = bench.make_stream(n_u, n_i, E, T, seed=seed, d_e=d_e, with_efeats=efeats)
+    if edit is not None:
+        edit(st)
     n_nodes = st['n_nodes']
-    g = Graph.from_arrays(st['src'], st['dst'], st['ts'], st['eids'], strategy='recent_edges', seed=0,
+    g = Graph.from_arrays(st['src'], st['dst'], st['ts'], st['eids'], strategy=strategy, seed=0,
                           max_node_id=n_nodes - 1, device=dev())
     nf = None
     if nfeats:
@@ -52,7 +55,7 @@ def build(nh, d, d_e, *, nfeats=True, efeats=True, restarter='static', H=None, L
     fg.n_nodes, fg.n_edges = n_nodes, E
     rst = (SeqRestarter(raw_feat_getter=fg, graph=g, hist_len=H, n_head=nh, dropout=0.0) if restarter == 'seq'
            else StaticRestarter(raw_feat_getter=fg, graph=g))
-    model = TIGER(raw_feat_getter=fg, graph=g, restarter=rst, n_neighbors=K, hit_type='bin', n_layers=L, n_head=nh,
+    model = TIGER(raw_feat_getter=fg, graph=g, restarter=rst, n_neighbors=K, hit_type=hit, n_layers=L, n_head=nh,
                   dropout=0.0, msg_src=msg_src, upd_src=upd_src).to(dev())
     with torch.no_grad():  # non-trivial time-encoder phase and static restarter rows
         model.time_encoder.phase.uniform_(-0.5, 0.5)
@@ -60,10 +63,10 @@ def build(nh, d, d_e, *, nfeats=True, efeats=True, restarter='static', H=None, L
             rst.left_emb.weight.normal_(0, 0.1)
             rst.right_emb.weight.normal_(0, 0.1)
     model.eval()
-    og = O.OracleGraph(st['src'], st['dst'], st['ts'], st['eids'], max_node_id=n_nodes - 1)
+    og = O.OracleGraph(st['src'], st['dst'], st['ts'], st['eids'], strategy=strategy, seed=0, max_node_id=n_nodes - 1)
     params = {k: v.detach().cpu().numpy() for k, v in model.named_parameters()}
     orc = O.OracleTIGER(params, og, n_nodes=n_nodes, dim=d, nfeats=nf, efeats=st['efeats'], n_neighbors=K,
-                        msg_src=msg_src, upd_src=upd_src, restarter=restarter, hist_len=H, n_head=nh, hit_type='bin')
+                        msg_src=msg_src, upd_src=upd_src, restarter=restarter, hist_len=H, n_head=nh, hit_type=hit)
     return model, orc, st
 
 
@@ -90,10 +93,13 @@ VARIANTS = [
 STREAM_CASES = [s + v for i, s in enumerate(SHAPES) for v in VARIANTS[:3] + [VARIANTS[3 + i % 2]]]
 
 
-def _run_stream(model, orc, st, K, form, L=1):
+def _run_stream(model, orc, st, K, form, L=1, edges=None, lists=None):
+    """edges: the batch boundaries (default: the ragged ones of the 200-event streams); lists: a list that receives the
+    oracle's collation of every batch"""
     from oracle import tiger_oracle as O
     from test_hip_parity import compare_state_with_oracle
-    edges = [0, 5, 37, 101, 130, 192, 200]   # ragged: 5, 32, 64, 29, 62, 8 events
+    if edges is None:
+        edges = [0, 5, 37, 101, 130, 192, 200]   # ragged: 5, 32, 64, 29, 62, 8 events
     for b, (lo, hi) in enumerate(zip(edges[:-1], edges[1:])):
         a = [st[k][lo:hi] for k in ('src', 'dst', 'neg', 'ts', 'eids')]
         n = hi - lo
@@ -101,6 +107,8 @@ def _run_stream(model, orc, st, K, form, L=1):
         if L == 1:
             assert (int(buf.counts[0]) == -1) == (form == 'eager-lean')   # the lean form really ran (or not)
         cg = O.collate(orc.graph, a[0], a[1], a[2], a[3], K, 'static', n_layers=L)
+        if lists is not None:
+            lists.append(cg)
         ref = orc.contrast_learning(*a, cg)['h_left'].detach().numpy()
         np.testing.assert_array_equal(buf.l1_nids.cpu().numpy()[:3 * n], cg['l1_nids'])
         np.testing.assert_array_equal(buf.l1_eids.cpu().numpy()[:3 * n], cg['l1_eids'])

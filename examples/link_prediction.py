@@ -96,14 +96,16 @@ def rank_candidates(neg_sample, n_cand, full_data, full_graph, test):
     return np.stack(cols, 1).astype(np.int64)
 
 
-def rank_pair(model, dl, ind_dl, device, cand):
-    """eval_edge_ranking over the transductive then the inductive test split from the same memory state (as
-    evaluate_pair); the inductive events keep the candidates of their events"""
+def rank_pair(model, dl, ind_dl, device, cand, restart_mode, uptodate):
+    """eval_edge_ranking over the transductive then the inductive test split from the same memory state and the same
+    up-to-date set (as evaluate_pair); the inductive events keep the candidates of their events.  In restart mode the
+    candidates' neighbourhoods are restarted lazily with the batch's own (lazy_restarts): the protocol of the AP / AUC"""
     start = model.save_memory_state()
-    out = eval_edge_ranking(model, dl, device, cand)
+    out = eval_edge_ranking(model, dl, device, cand, lazy_restarts=restart_mode, uptodate_nodes=set(uptodate))
     end = model.save_memory_state()
     model.load_memory_state(start)
-    ind = eval_edge_ranking(model, ind_dl, device, cand[np.isin(dl.dataset.eids, ind_dl.dataset.eids)])
+    ind = eval_edge_ranking(model, ind_dl, device, cand[np.isin(dl.dataset.eids, ind_dl.dataset.eids)],
+                            lazy_restarts=restart_mode, uptodate_nodes=set(uptodate))
     model.load_memory_state(end)
     return out, ind
 
@@ -159,11 +161,12 @@ def run(data, root, *, seed=0, n_epochs=1, bs=200, lr=1e-4, dim=None, n_neighbor
     before_test = model.save_memory_state() if rank > 0 else None
     test = evaluate_pair(model, test_dl, ind_test_dl, device, restart_mode, uptodate)
     out = dict(epochs=log, test_ap=test[0], test_auc=test[1], ind_test_ap=test[2], ind_test_auc=test[3])
-    if rank > 0:  # one-vs-many over the same test events, from the state the test started from (no restarts: see eval_edge_ranking)
+    if rank > 0:  # one-vs-many over the same test events, from the state and the up-to-date set the test started from: in
+        #             restart mode with lazy restarts that cover the candidates too, so both sets of numbers share a protocol
         after_test = model.save_memory_state()
         model.load_memory_state(before_test)
         cand = rank_candidates(neg_sample, rank, full_data, full_graph, test_dl.dataset)
-        r, ind_r = rank_pair(model, test_dl, ind_test_dl, device, cand)
+        r, ind_r = rank_pair(model, test_dl, ind_test_dl, device, cand, restart_mode, uptodate)
         model.load_memory_state(after_test)
         for name, m in (('test', r), ('ind_test', ind_r)):
             out.update({f'{name}_mrr': m['mrr'], **{f'{name}_hits@{k}': v for k, v in m['hits'].items()}})

@@ -13,7 +13,13 @@ only, and every batch first asks `recommend` at its own (source, time) queries a
 (the graph is extended on the device, the batch streams).  The same replay on the full graph with `stream_step` runs
 beside it, and the two lines printed - hit rate / NDCG / MRR@k - must be equal exactly (`run_online` asserts it).
 
-Only `run()` and `run_online()` matter; the few flags exist to make the file runnable.
+--cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
+Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
+its scores will read that the bitmap does not hold yet (`TIGER.restart_involved`), and is then ingested with
+`stream_step`; the number of restarted nodes is printed per batch beside the metrics.  What a serving process that has
+just loaded a checkpoint and a graph can do before it has seen the stream.
+
+Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
 import argparse
 import os
@@ -122,6 +128,49 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     return online, offline
 
 
+def run_cold(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
+             hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
+             device='cuda:0', verbose=True):
+    """-> (metrics over the test split, restarted nodes per batch).  No replay of train + validation: memories at reset, an
+    empty bitmap, `recommend(..., uptodate=bitmap)` batch by batch on the full graph."""
+    device = torch.device(device)
+    torch.manual_seed(seed)
+    basic, (train_graph, full_graph), dls = init_data(
+        data, root, seed, num_workers=0, bs=bs, warmup_steps=0, subset=1.0, strategy=strategy, n_layers=1,
+        n_neighbors=n_neighbors, restarter_type=restarter_type, hist_len=hist_len, device=device)
+    nfeats, efeats, full_data, test = basic[0], basic[1], basic[2], basic[5]
+    model = init_model(nfeats, efeats, train_graph, full_graph, full_data, device, dim=dim, n_layers=1, n_heads=n_heads,
+                       n_neighbors=n_neighbors, hit_type=hit_type, dropout=0.0, restarter_type=restarter_type,
+                       hist_len=hist_len, msg_src=msg_src, upd_src=upd_src, msg_tsfm_type='id', mem_update_type='gru')
+    model.load_state_dict(torch.load(ckpt_path, map_location=device))
+    model.eval()
+    model.graph = full_graph
+    model.reset()   # the checkpoint's memories are not used: every node the scores read is restarted on first use
+    catalogue = torch.from_numpy(np.unique(full_data.dst).astype(np.int64)).to(device)
+    col_of = hip_ops.catalogue_index(catalogue, model.n_nodes)
+    bitmap = hip_ops.new_bitmap(model.n_nodes, device)
+    restarted, pos = [], []
+    place = torch.arange(k, device=device)
+    with torch.no_grad():
+        for lo in range(0, len(test.src), bs):
+            src, dst, ts, eids = (np.ascontiguousarray(getattr(test, f)[lo:lo + bs]) for f in ('src', 'dst', 'ts', 'eids'))
+            q, d = torch.from_numpy(src).to(device), torch.from_numpy(dst).to(device)
+            t = torch.from_numpy(ts.astype(np.float64)).to(device)
+            i, _, _ = model.recommend(q, t, catalogue, k, exclude_seen=exclude_seen, col_of=col_of, uptodate=bitmap)
+            restarted.append(model.last_restarted)
+            hit = (i == d[:, None]) & (i != 0)
+            pos.append(torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1))
+            if verbose:
+                print(f'batch {lo // bs}: {restarted[-1]} nodes restarted, HitRate@{k} {float((pos[-1] >= 0).float().mean()):.4f}')
+            # the batch's own nodes are among the restarted ones (its sources are queries, its destinations in the catalogue)
+            model.stream_step(src, dst, dst, ts.astype(np.float64), eids)
+    pos = torch.cat(pos)
+    listed, p = pos >= 0, pos.clamp(min=0).double()
+    n = max(1, pos.numel())
+    return dict(hit_rate=float(listed.sum()) / n, ndcg=float((listed / torch.log2(p + 2)).sum()) / n,
+                mrr_at_k=float((listed / (p + 1)).sum()) / n, n_events=pos.numel()), restarted
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser(description='Write top-k recommendation lists for the test split of a TIGER checkpoint.')
     ap.add_argument('-d', '--data', default='wikipedia')
@@ -135,7 +184,15 @@ if __name__ == '__main__':
     ap.add_argument('--restarter_type', default='seq', choices=['seq', 'static'])
     ap.add_argument('--online', action='store_true', help='replay the test split through TIGE.observe on a graph that '
                     'starts at train + validation, beside the replay on the full graph')
+    ap.add_argument('--cold', action='store_true', help='no replay: memories at reset, lazy restarts of what each batch reads '
+                    '(recommend(..., uptodate=bitmap)); prints the restart count per batch')
     a = ap.parse_args()
+    if a.cold:
+        m, restarted = run_cold(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, seed=a.seed, bs=a.bs,
+                                restarter_type=a.restarter_type)
+        print(f"cold: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "
+              f"({m['n_events']} events, {sum(restarted)} restarts over {len(restarted)} batches)")
+        sys.exit(0)
     if a.online:
         for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
                                                               seed=a.seed, bs=a.bs, restarter_type=a.restarter_type)):

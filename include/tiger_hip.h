@@ -1041,6 +1041,43 @@ int tg_seen_mask_host(const tg_tcsr* g, int64_t B, const int64_t* src_host, cons
                       const int32_t* col_of_host, uint8_t* mask_host);
 
 /* ------------------------------------------------------------------------- */
+/* Involved list: the lazy restart's bookkeeping (eval_utils.py:37-42) over    */
+/* the set GraphCollator.collate_memory_nodes builds (data_loader.py:105-131), */
+/* for a flat list of (node, time) queries whose neighbour lists nobody wants  */
+/* yet - ranking candidates, recommendation catalogues                         */
+/* ------------------------------------------------------------------------- */
+/* involved = {nids[q]}
+ *          + hop 1: the K sampler slots of every (nids[q], ts[q]) - strategy 0 = recent_edges (graph.py:117-127), 1 =
+ *            recent_nodes (graph.py:129-143); strict '<' on float64; slots are left padded and the padding id 0 counts, as
+ *            the samplers mark it
+ *          + hop 2 (n_layers == 2): the K slots of every hop-1 slot at (slot id, slot time), padding slots - node 0 at
+ *            time 0 - included.  The slot time is the T-CSR time rounded to float32 and widened again: the collator samples
+ *            the second hop at the float32 neighbour times (data_loader.py:131).
+ * Exactly the nodes collate_memory_nodes flags for the same queries, without its [Q, K] and [Q K, K] slot arrays: the
+ * marking kernel writes nothing per slot.  Outputs: list[0 .. *count) = the ids of involved & ~uptodate, ascending;
+ * uptodate |= involved (a bitmap over g->num_node ids, tg_bitmap_words); *tmin = float32(min over q of ts[q]).  No model
+ * state is read or written.  Q == 0: *count = 0 and nothing else is written.
+ * One wavefront per query for the marks, then the flags are packed, listed and ORed into the bitmap: two launches up to
+ * 65 536 nodes, three beyond; plain launches on `stream`.
+ * ws: tg_involved_list_workspace_bytes(g->num_node, Q, K, n_layers) bytes, 16-byte aligned - at most 2 bytes per node
+ * + 64 KiB whatever Q, K and n_layers are (byte flags, one bitmap, ranks): no term in Q K or Q K^2.
+ * TG_EUNSUPPORTED for strategy 2 (uniform: the set would depend on the graph's random stream).  TG_EINVAL for any other
+ * strategy outside {0, 1}, K outside [1, TG_INVOLVED_MAX_K] (one wavefront holds a query's slots, as in
+ * tg_sample_recent_nodes), n_layers outside {1, 2}, Q < 0, a null pointer, cap < min(Q (1 + K [+ K^2]), num_node), a
+ * missing or short workspace - all before anything is launched.  nids[q] must lie in [0, num_node): the device entry
+ * cannot see the ids and treats one outside as a node without entries - its caller checks them where they are visible;
+ * the host twin returns TG_EINVAL. */
+#define TG_INVOLVED_MAX_K 64
+size_t tg_involved_list_workspace_bytes(int64_t n_nodes, int64_t Q, int32_t K, int32_t n_layers);
+int tg_involved_list(const tg_tcsr* g, int64_t Q, const int64_t* nids, const double* ts, int32_t K, int32_t n_layers,
+                     int32_t strategy, uint64_t* uptodate, int64_t cap, int64_t* list, int32_t* count, float* tmin,
+                     void* ws, size_t ws_bytes, void* stream);
+/* The same on the host (g and every array HOST pointers; plain C++ over the T-CSR arrays); identical outputs. */
+int tg_involved_list_host(const tg_tcsr* g, int64_t Q, const int64_t* nids_host, const double* ts_host, int32_t K,
+                          int32_t n_layers, int32_t strategy, uint64_t* uptodate_host, int64_t cap, int64_t* list_host,
+                          int32_t* count_host, float* tmin_host);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */
 /* the global batch, the embeddings having been computed on other ranks)      */

@@ -19,6 +19,7 @@ TG_TRAJ_LAST, TG_TRAJ_MAX, TG_TRAJ_SUM = 0, 1, 2  # tg_trajectory_accumulate mod
 TG_TRAJ_ERR_BAD_ID = 1
 TG_RANK_MAX_K = 8  # tg_rank_stats: cut-offs per call
 TG_TOPK_MAX_K = 64  # tg_topk_rows: positions per row
+TG_INVOLVED_MAX_K = 64  # tg_involved_list: sampler slots per query
 ERR_PAST_MEMORY, ERR_DUPLICATE_IDS, ERR_UNUSED_MESSAGE = 1, 2, 4
 ERR_MSG_BEFORE_MEM, ERR_MSG_TS_MISMATCH, ERR_EVENT_BEFORE_MEM = 8, 16, 32
 
@@ -270,6 +271,9 @@ SIGNATURES = {
     'tg_topk_rows_host': (C.c_int, [i64, i64, i32, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     'tg_seen_mask': (C.c_int, [P(TgTcsr), i64, vp, vp, i64, vp, vp, vp]),
     'tg_seen_mask_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i64, vp, vp]),
+    'tg_involved_list_workspace_bytes': (sz, [i64, i64, i32, i32]),
+    'tg_involved_list': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, sz, vp]),
+    'tg_involved_list_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp]),
     'tg_stream_writeback_workspace_bytes': (sz, [P(TgModel), i64]),
     'tg_stream_writeback': (C.c_int, [P(TgModel), P(TgWritebackIo), vp, sz, vp]),
 }

@@ -114,6 +114,48 @@ __device__ __forceinline__ bool bm_test(const uint64_t* __restrict__ bm, int64_t
   return (bm[id >> 6] >> (id & 63)) & 1ull;
 }
 
+// ---- flag bytes -> bitmap words -> ranks (tg_compact.hip, tg_involved.hip) ----
+constexpr int TG_SCAN_BLOCK = 256;
+// exclusive scan of one value per thread over a 256-thread block; returns the block total in *total
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave /*[4]*/, uint32_t* total) {
+  const int lane = lane_id();
+  const int wv = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < TG_WAVE; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, TG_WAVE);
+    if (lane >= o) inc += t;
+  }
+  if (lane == TG_WAVE - 1) s_wave[wv] = inc;
+  __syncthreads();
+  uint32_t base = 0;
+  uint32_t tot = 0;
+#pragma unroll
+  for (int i = 0; i < TG_SCAN_BLOCK / TG_WAVE; ++i) {
+    const uint32_t s = s_wave[i];
+    if (i < wv) base += s;
+    tot += s;
+  }
+  *total = tot;
+  __syncthreads();
+  return base + inc - v;
+}
+
+// 8 flag bytes (each 0/1) -> 8 bits
+__device__ __forceinline__ uint64_t pack8(uint64_t x) { return ((x & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56; }
+// the bitmap word of 64 flag bytes (16-byte aligned)
+__device__ __forceinline__ uint64_t pack_flag_word(const uint8_t* __restrict__ flags64) {
+  const uint4* f = reinterpret_cast<const uint4*>(flags64);
+  uint64_t a = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint4 v = f[q];
+    const uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32), hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
+    a |= (pack8(lo) | (pack8(hi) << 8)) << (16 * q);
+  }
+  return a;
+}
+
 // row of node v in this process's state tables (tiger_hip.h: tg_model.row_of; identity unless the state is physically
 // partitioned)
 __device__ __forceinline__ int64_t state_row(const tg_model& m, int64_t v) { return m.row_of ? (int64_t)m.row_of[v] : v; }

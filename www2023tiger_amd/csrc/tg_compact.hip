@@ -8,7 +8,7 @@
 
 namespace tg {
 
-constexpr int CB = 256;  // threads per block = bitmap words per block
+constexpr int CB = TG_SCAN_BLOCK;  // threads per block = bitmap words per block (block_excl_scan, pack8: tg_common.h)
 
 __global__ void k_mark(int64_t n, const int64_t* __restrict__ ids, uint64_t* __restrict__ bm, int64_t n_nodes) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -28,34 +28,6 @@ __global__ void k_mark_flags(int64_t n, const int64_t* __restrict__ ids, uint8_t
     if (id >= 0 && id < n_nodes) flags[id] = 1;
   }
 }
-
-// exclusive scan of one value per thread over a 256-thread block; returns the block total in *total
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave /*[4]*/, uint32_t* total) {
-  const int lane = lane_id();
-  const int wv = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < TG_WAVE; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, TG_WAVE);
-    if (lane >= o) inc += t;
-  }
-  if (lane == TG_WAVE - 1) s_wave[wv] = inc;
-  __syncthreads();
-  uint32_t base = 0;
-  uint32_t tot = 0;
-#pragma unroll
-  for (int i = 0; i < CB / TG_WAVE; ++i) {
-    const uint32_t s = s_wave[i];
-    if (i < wv) base += s;
-    tot += s;
-  }
-  *total = tot;
-  __syncthreads();
-  return base + inc - v;
-}
-
-// 8 flag bytes (each 0/1) -> 8 bits
-__device__ __forceinline__ uint64_t pack8(uint64_t x) { return ((x & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56; }
 
 // phase A: one thread per bitmap word.  Optionally packs 64 flag bytes into the word first
 // (the bitmap is then an OUTPUT).  Writes block-relative exclusive ranks and block totals.

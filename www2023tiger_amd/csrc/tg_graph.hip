@@ -271,9 +271,8 @@ int sample_batch_launch(const tg_tcsr* g, int64_t B, const int64_t* src, const i
   return check_launch("sample_batch");
 }
 
-// One wavefront per query.  Walk the prefix backwards 64 entries at a time; an entry
-// is kept if no more recent entry (this chunk or earlier chunks) has the same
-// neighbour.  The j-th kept entry (j = 0 most recent) lands in output slot K-1-j.
+// One wavefront per query walks the prefix backwards (tg_sample.h: recent_nodes_scan).  The j-th kept
+// entry (j = 0 most recent) lands in output slot K-1-j.
 __global__ void __launch_bounds__(256) k_sample_recent_nodes(tg_tcsr g, int64_t Q, const int64_t* __restrict__ nids,
                                                              const double* __restrict__ qts, int K,
                                                              int64_t* __restrict__ o_nbr, int64_t* __restrict__ o_eid,
@@ -285,39 +284,14 @@ __global__ void __launch_bounds__(256) k_sample_recent_nodes(tg_tcsr g, int64_t 
   for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < Q; q += (int64_t)gridDim.x * 4) {
     int64_t start;
     const int64_t end = prefix_end(g, nids[q], qts ? qts[q] : (double)qts32[q], &start);  // (second hop: float32 query times)
-    int c = 0;        // wave-uniform: number collected so far
-    int mycol = -1;   // lane j holds the neighbour id of the j-th collected entry
-    for (int64_t chunk_end = end; chunk_end > start && c < K; chunk_end -= TG_WAVE) {
-      const int64_t p = chunk_end - 1 - lane;
-      const bool valid = p >= start;
-      const int v = valid ? g.nbr[p] : -1;
-      bool isnew = valid;
-      for (int i = 0; i < TG_WAVE; ++i) {
-        const int vi = __shfl(v, i, TG_WAVE);
-        if (i < lane && vi == v) isnew = false;
-      }
-      for (int j = 0; j < c; ++j) {
-        const int cj = __shfl(mycol, j, TG_WAVE);
-        if (cj == v) isnew = false;
-      }
-      const unsigned long long m = __ballot(isnew);
-      const int slot = c + __popcll(m & ((1ull << lane) - 1ull));
-      if (isnew && slot < K) {
-        const uint32_t e = (uint32_t)g.eid[p];
-        const int64_t o = q * K + (K - 1 - slot);
-        o_nbr[o] = v;
-        o_eid[o] = (int64_t)(e & 0x7fffffffu);
-        o_ts[o] = (float)g.ts[p];
-        if (o_dir) o_dir[o] = (int64_t)(e >> 31);
-        if (slot < TG_WAVE) s_new[wv][slot] = v;
-      }
-      const int nnew = __popcll(m);
-      __builtin_amdgcn_wave_barrier();
-      if (lane >= c && lane < c + nnew && lane < K) mycol = s_new[wv][lane];
-      __builtin_amdgcn_wave_barrier();
-      c += nnew;
-    }
-    if (c > K) c = K;
+    const int c = recent_nodes_scan(g, start, end, K, s_new[wv], lane, [&](int slot, int64_t p, int v) {
+      const uint32_t e = (uint32_t)g.eid[p];
+      const int64_t o = q * K + (K - 1 - slot);
+      o_nbr[o] = v;
+      o_eid[o] = (int64_t)(e & 0x7fffffffu);
+      o_ts[o] = (float)g.ts[p];
+      if (o_dir) o_dir[o] = (int64_t)(e >> 31);
+    });
     for (int j = lane; j < K - c; j += TG_WAVE) {  // left padding
       const int64_t o = q * K + j;
       o_nbr[o] = 0;

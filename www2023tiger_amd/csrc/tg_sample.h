@@ -55,6 +55,44 @@ __device__ __forceinline__ int64_t prefix_end_group(const tg_tcsr& g, int64_t ni
   return lo;
 }
 
+// The recent-nodes rule (graph.py:129-143) by one wavefront over the entries [start, end) of a node: walk the prefix
+// backwards 64 entries at a time; an entry is kept if no more recent entry (this chunk or earlier chunks) has the same
+// neighbour.  emit(slot, p, v) runs on the lane that holds the slot-th kept entry (slot 0 most recent, slot < K): entry p,
+// neighbour v.  s_new: 64 ints of LDS of this wavefront; on return s_new[j] is the neighbour of kept entry j.  Returns the
+// number of kept entries, at most K (wave-uniform).  K <= 64.
+template <class Emit>
+__device__ __forceinline__ int recent_nodes_scan(const tg_tcsr& g, int64_t start, int64_t end, int K, int* s_new, int lane,
+                                                 Emit emit) {
+  int c = 0;        // wave-uniform: number collected so far
+  int mycol = -1;   // lane j holds the neighbour id of the j-th collected entry
+  for (int64_t chunk_end = end; chunk_end > start && c < K; chunk_end -= TG_WAVE) {
+    const int64_t p = chunk_end - 1 - lane;
+    const bool valid = p >= start;
+    const int v = valid ? g.nbr[p] : -1;
+    bool isnew = valid;
+    for (int i = 0; i < TG_WAVE; ++i) {
+      const int vi = __shfl(v, i, TG_WAVE);
+      if (i < lane && vi == v) isnew = false;
+    }
+    for (int j = 0; j < c; ++j) {
+      const int cj = __shfl(mycol, j, TG_WAVE);
+      if (cj == v) isnew = false;
+    }
+    const unsigned long long m = __ballot(isnew);
+    const int slot = c + __popcll(m & ((1ull << lane) - 1ull));
+    if (isnew && slot < K) {
+      emit(slot, p, v);
+      if (slot < TG_WAVE) s_new[slot] = v;
+    }
+    const int nnew = __popcll(m);
+    __builtin_amdgcn_wave_barrier();
+    if (lane >= c && lane < c + nnew && lane < K) mycol = s_new[lane];
+    __builtin_amdgcn_wave_barrier();
+    c += nnew;
+  }
+  return c > K ? K : c;
+}
+
 // The sampler of the fused step: query q of cat[src, dst, neg] is built on the fly from the batch arrays (at stream offset
 // `o`), written out for the later stages (ids, float32 times, edge ids), its K most recent edges before t (strict '<',
 // graph.py:94-127) are copied by G lanes per query.  Workgroup `bid` of `nblk` (256 threads each).

@@ -140,15 +140,8 @@ def _restart_listed(model, tb, graph):
           'tg_stream_step(lazy restart list)')
     n = int(cb.counts[3].item())
     if n:
-        nids = tb.sb.lazy_list[:n]
-        # a model that streams with eager updates: were its per-node tables current?  Then they follow the restart - the
-        # restarted nodes have no pending message any more and new memories: their centre / query rows are recomputed -
-        # instead of being rebuilt for every node at the next step
-        current = (model._pending is not None and model._pending_stamp == model._state_stamp()
-                   and (getattr(model, '_gtab', None) is None or getattr(model, '_gtab_stamp', None) is not None))
-        model.restart_list(nids, tb.sb.lazy_tmin)  # (one library call for the SeqRestarter, TIGER.restart otherwise)
-        if current:
-            model._tables_follow_restart(nids)
+        # (a model that streams with eager updates keeps its per-node tables current through the restart)
+        model.restart_list_keep_tables(tb.sb.lazy_list[:n], tb.sb.lazy_tmin)
     tb.sb.lazy_batch += 1
     return n
 
@@ -555,8 +548,36 @@ def eval_edge_prediction(model, dl, device: torch.device, restart_mode: bool, up
     return float(ap.mean().item()), float(auc.mean().item())
 
 
+def _uptodate_bitmap(model, uptodate_nodes: Optional[set], device):
+    """the up-to-date bitmap of a lazy-restart pass, started from the caller's set"""
+    from . import hip_ops
+    bm = hip_ops.new_bitmap(model.n_nodes, device)
+    if uptodate_nodes:
+        hip_ops.bitmap_mark(torch.tensor(sorted(uptodate_nodes), dtype=torch.int64, device=device), bm, model.n_nodes)
+    return bm
+
+
+def _uptodate_set(model, bm, uptodate_nodes: Optional[set]):
+    """the caller's set updated in place from the bitmap, as in the reference"""
+    from . import hip_ops
+    if uptodate_nodes is not None:
+        comp = hip_ops.unique_compact(bm, model.n_nodes, model.n_nodes)
+        uptodate_nodes.update(comp['ids'][:int(comp['count'].item())].tolist())
+
+
+def _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, t, cand_rows, bm, graph) -> int:
+    """the lazy restart of one batch that also scores candidates: ONE `restart_involved` over cat[src, dst, neg] at the
+    event times (what the batch's own step involves, eval_utils.py:37-42) plus every event's candidates at its time"""
+    B = len(src_ids)
+    t64 = t.double().reshape(-1)
+    nodes = torch.cat([src_ids, dst_ids, neg_dst_ids, cand_rows.reshape(-1)])
+    times = torch.cat([t64.repeat(3), t64.repeat_interleave(cand_rows.numel() // B if B else 0)])
+    return model.restart_involved(nodes, times, bm, graph=graph)
+
+
 def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 10), restart_mode: bool = False, mask=None,
-                      chunk_queries: int = 65536, return_ranks: bool = False) -> dict:
+                      chunk_queries: int = 65536, return_ranks: bool = False, lazy_restarts: bool = False,
+                      uptodate_nodes: Optional[set] = None) -> dict:
     """One-vs-many link evaluation (the DGB / TGB protocol; no counterpart in the reference's eval_utils): every event's
     true destination is ranked against its candidates by the scores of the state BEFORE its batch, then the batch runs as
     in `eval_edge_prediction` (contrast_learning), so the state advances exactly as there.  -> dict(mrr, hits {k: value},
@@ -565,14 +586,23 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
     (bool, false = leave the candidate out).  A candidate equal to the event's destination or to the padding id 0 is left
     out as well.  rank = 1 + #greater + #equal / 2 over the candidates left in; MRR = mean 1 / rank, Hits@k =
     mean [rank <= k].  Scores come from TIGE.rank_scores, counts and sums from tg_rank_stats, folded on the device with
-    one read-back at the end; a non-finite score raises ValueError.  Refused: restart_mode (lazy restarts would have to
-    cover the candidates' neighbourhoods), and whatever TIGE.rank_scores refuses (strategy 'uniform', partitioned models)."""
+    one read-back at the end; a non-finite score raises ValueError.
+    lazy_restarts=True: the restart-mode protocol of eval_edge_prediction extended to the candidates.  Per batch ONE
+    `TIGER.restart_involved` over cat[src, dst, neg] at the event times plus every candidate query restarts what is not
+    up to date yet (eval_utils.py:37-42), then the batch is scored and run as above.  uptodate_nodes (a set, optional):
+    who is up to date at the start, updated in place at the end; the bitmap lives on the device for the pass.
+    Refused: restart_mode=True (restarting only the batch's own neighbourhoods would score candidates on stale memories -
+    use lazy_restarts=True), and whatever TIGE.rank_scores refuses (strategy 'uniform', partitioned models)."""
     from . import hip_ops
     if restart_mode:
-        raise NotImplementedError('eval_edge_ranking: restart mode is not built (the lazy restarts of eval_edge_prediction '
-                                  "cover the batch's own neighbourhoods, not the candidates')")
+        raise NotImplementedError('eval_edge_ranking: restart_mode=True is not built (the lazy restarts of '
+                                  "eval_edge_prediction cover the batch's own neighbourhoods, not the candidates'); "
+                                  'use lazy_restarts=True, which restarts both')
     model._refuse_partitioned('eval_edge_ranking')
+    if lazy_restarts and getattr(model, 'restarter_fn', None) is None:
+        raise NotImplementedError('eval_edge_ranking: lazy_restarts needs a model with a restarter (TIGER)')
     model.eval()
+    bm = _uptodate_bitmap(model, uptodate_nodes, device) if lazy_restarts else None
     ks = tuple(int(k) for k in ks)
     cand = torch.as_tensor(candidates).long().to(device)
     if cand.dim() not in (1, 2):
@@ -596,6 +626,9 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
             mk = None if mask is None else (mask.unsqueeze(0).expand(B, -1) if mask.dim() == 1 else mask[row:row + B])
             ts64 = getattr(comp_graph, 'ts64', None)
             g = graph if graph is not None else getattr(comp_graph, 'graph', None)
+            if lazy_restarts:
+                _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, (ts if ts64 is None else ts64).to(device),
+                                              c, bm, g)
             scores = model.rank_scores(src_ids, dst_ids, ts if ts64 is None else ts64, c, chunk_queries=chunk_queries, graph=g)
             st = hip_ops.rank_stats(scores, torch.cat([dst_ids[:, None], c], 1), dst_ids, mask=mk, ks=ks, acc=acc)
             if return_ranks:
@@ -605,6 +638,8 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
     model._poll_train_errors()
     if cand.dim() == 2 and row != cand.shape[0]:
         raise ValueError(f'candidates has {cand.shape[0]} rows, the loader {row} events')
+    if lazy_restarts:
+        _uptodate_set(model, bm, uptodate_nodes)
     out = hip_ops.rank_metrics(acc, ks)
     if return_ranks:
         out['ranks'] = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.float64, device=device)
@@ -612,7 +647,8 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
 
 
 def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 10, exclude_seen: bool = False,
-                        chunk_queries: int = 65536, restart_mode: bool = False, return_positions: bool = False) -> dict:
+                        chunk_queries: int = 65536, restart_mode: bool = False, return_positions: bool = False,
+                        lazy_restarts: bool = False, uptodate_nodes: Optional[set] = None) -> dict:
     """Top-k recommendation quality over a loader (no counterpart in the reference's eval_utils): for every batch the k best
     items of the shared `catalogue` (int64 [C], no id twice) are listed for the batch's sources on the state BEFORE the
     batch (TIGE.recommend), then the batch runs as in `eval_edge_ranking` (contrast_learning), so the state advances
@@ -622,14 +658,20 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
     mrr_at_k = mean of 1 / (position + 1), a miss counting 0.  coverage = the share of events whose destination is in
     the catalogue and left in (not the padding id; with exclude_seen=True not an item the source has an edge with before
     the event's time - tg_seen_mask over the loader's graph): an upper bound of hit_rate.  Positions and folds are a few
-    [B, k] torch ops accumulated on the device, one read-back at the end.  Refused: restart_mode, and whatever
-    TIGE.recommend refuses."""
+    [B, k] torch ops accumulated on the device, one read-back at the end.
+    lazy_restarts=True / uptodate_nodes: as in `eval_edge_ranking` - per batch ONE `TIGER.restart_involved` over
+    cat[src, dst, neg] plus the catalogue at every event's time, before the batch is scored.
+    Refused: restart_mode=True (use lazy_restarts=True), and whatever TIGE.recommend refuses."""
     from . import hip_ops
     if restart_mode:
-        raise NotImplementedError('eval_recommendation: restart mode is not built (the lazy restarts of eval_edge_prediction '
-                                  "cover the batch's own neighbourhoods, not the catalogue's)")
+        raise NotImplementedError('eval_recommendation: restart_mode=True is not built (the lazy restarts of '
+                                  "eval_edge_prediction cover the batch's own neighbourhoods, not the catalogue's); "
+                                  'use lazy_restarts=True, which restarts both')
     model._refuse_partitioned('eval_recommendation')
+    if lazy_restarts and getattr(model, 'restarter_fn', None) is None:
+        raise NotImplementedError('eval_recommendation: lazy_restarts needs a model with a restarter (TIGER)')
     model.eval()
+    bm = _uptodate_bitmap(model, uptodate_nodes, device) if lazy_restarts else None
     k = int(k)
     cat = torch.as_tensor(catalogue).long().to(device)
     if cat.dim() != 1:
@@ -649,6 +691,9 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
             t = (ts if ts64 is None else ts64).to(device)
             g = graph if graph is not None else getattr(comp_graph, 'graph', None)
             g = model.graph if g is None else g
+            if lazy_restarts:
+                _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, t, cat.unsqueeze(0).expand(len(src_ids), -1),
+                                              bm, g)
             seen = hip_ops.seen_mask(g, src_ids, t, col_of, C) if exclude_seen else None
             ids, _, _ = model.recommend(src_ids, t, cat, k, mask=seen, graph=g, chunk_queries=chunk_queries)
             hit = (ids == dst_ids[:, None]) & (ids != 0)
@@ -666,6 +711,8 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
             model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
             n += len(src_ids)
     model._poll_train_errors()
+    if lazy_restarts:
+        _uptodate_set(model, bm, uptodate_nodes)
     a = acc.cpu().tolist()
     nan = float('nan')
     out = dict(hit_rate=a[0] / n if n else nan, ndcg=a[1] / n if n else nan, mrr_at_k=a[2] / n if n else nan, n_events=n,

@@ -305,3 +305,54 @@ def seen_mask(graph, src: Tensor, ts: Tensor, col_of: Tensor, C: int, mask: Opti
         check(lib.tg_seen_mask(C_.byref(graph.tcsr), B, ptr(src), ptr(ts), C, ptr(col_of), ptr(m8), stream_ptr(dev)),
               'tg_seen_mask')
     return m8.bool()
+
+
+# ---- involved list (tg_involved_list and its host twin) -------------------------------------------------------------------
+_STRATEGY_CODE = {'recent_edges': 0, 'recent_nodes': 1, 'uniform': 2}
+
+
+def involved_list(graph, nids: Tensor, ts: Tensor, n_neighbors: int, n_layers: int, uptodate: Tensor, *,
+                  strategy: Optional[str] = None) -> dict:
+    """The nodes the embeddings of the (nids[q], ts[q]) queries will read - the set GraphCollator.collate_memory_nodes
+    flags: the queries, their sampled neighbours and, with n_layers == 2, the neighbours' neighbours - that are not in
+    `uptodate` yet (tiger_hip.h: tg_involved_list; no slot array is written).  uptodate: a bitmap of `new_bitmap` over
+    graph.num_node ids, ORed with the whole set IN PLACE.  -> dict(ids int64 [cap]: the listed ids ascending in
+    ids[:count], count int32 [1], tmin float32 [1] = the earliest query time); nothing is read back.  strategy: the graph's
+    own by default; 'uniform' is refused.  Device tensors take the device entry over graph.tcsr, host tensors the host
+    twin over the graph's host arrays.  ValueError for an id outside [0, num_node)."""
+    import ctypes as C_
+    dev = nids.device
+    nids = _i64(nids).reshape(-1)
+    Q, K, L = nids.numel(), int(n_neighbors), int(n_layers)
+    ts = ts.to(dev).double().contiguous().reshape(-1)
+    strategy = graph.strategy if strategy is None else strategy
+    if strategy not in _STRATEGY_CODE:
+        raise NotImplementedError(strategy)
+    if strategy == 'uniform':
+        raise NotImplementedError("involved_list: strategy='uniform' would make the set depend on the graph's random stream")
+    n_nodes = graph.num_node
+    if (ts.numel() != Q or uptodate.dtype != torch.int64 or uptodate.numel() != bitmap_words(n_nodes)
+            or uptodate.device != dev or not uptodate.is_contiguous()):
+        raise ValueError(f'involved_list: {Q} queries, ts {tuple(ts.shape)}, uptodate {uptodate.dtype} {tuple(uptodate.shape)} '
+                         f'on {uptodate.device} for {n_nodes} nodes on {dev}')
+    if not 1 <= K <= _lib.TG_INVOLVED_MAX_K or L not in (1, 2):
+        raise ValueError(f'involved_list: 1 <= n_neighbors <= {_lib.TG_INVOLVED_MAX_K}, n_layers 1 or 2')
+    if Q and (int(nids.min()) < 0 or int(nids.max()) >= n_nodes):
+        raise ValueError('involved_list: a node id outside [0, num_node)')
+    cap = min(Q * (1 + K + (K * K if L == 2 else 0)), n_nodes)
+    out = dict(ids=torch.empty(max(cap, 1), dtype=torch.int64, device=dev), count=torch.zeros(1, dtype=torch.int32, device=dev),
+               tmin=torch.zeros(1, dtype=torch.float32, device=dev))
+    args = (Q, ptr(nids), ptr(ts), K, L, _STRATEGY_CODE[strategy], ptr(uptodate), cap, ptr(out['ids']), ptr(out['count']),
+            ptr(out['tmin']))
+    if dev.type == 'cpu':
+        h = graph._host_tcsr()
+        tc = _lib.TgTcsr(n_nodes, len(h[1]), *(ptr(a) for a in h))
+        check(lib.tg_involved_list_host(C_.byref(tc), *args), 'tg_involved_list_host')
+    else:
+        gd = graph.device
+        if gd.type != dev.type or (gd.index is not None and dev.index is not None and gd.index != dev.index):
+            raise ValueError(f'involved_list: the graph lives on {graph.device}, the queries on {dev}')
+        nbytes = int(lib.tg_involved_list_workspace_bytes(n_nodes, Q, K, L))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.tg_involved_list(C_.byref(graph.tcsr), *args, ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_involved_list')
+    return out

@@ -169,6 +169,16 @@ class TIGE(nn.Module):
         check(lib.tg_restart_seq_list(C.byref(m), C.byref(r.graph.tcsr), C.byref(rs), n, ptr(nids), ptr(t_dev), ptr(ws),
                                       ws.numel(), stream_ptr(self.device)), 'tg_restart_seq_list')
 
+    def restart_list_keep_tables(self, nids: Tensor, t_dev: Tensor):
+        """`restart_list` on a model that may stream with eager updates: were its per-node tables current?  Then they
+        follow the restart - the restarted nodes have no pending message any more and new memories: their centre / query
+        rows are recomputed (`_tables_follow_restart`) - instead of being rebuilt for every node at the next step."""
+        current = (self._pending is not None and self._pending_stamp == self._state_stamp()
+                   and (getattr(self, '_gtab', None) is None or getattr(self, '_gtab_stamp', None) is not None))
+        self.restart_list(nids, t_dev)  # (one library call for the SeqRestarter, TIGER.restart otherwise)
+        if current:
+            self._tables_follow_restart(nids)
+
     def restart_list_split_ok(self) -> bool:
         """Can `restart_list` be taken apart into `restart_list_forward` (reads graph / features / restarter parameters only)
         and `restart_list_apply` (the state update)?  The SeqRestarter in inference form."""
@@ -774,7 +784,7 @@ class TIGE(nn.Module):
     RANK_EMBED_ROWS = 4096
 
     def rank_scores(self, src_ids: Tensor, dst_ids: Tensor, ts: Tensor, cand: Tensor, *, chunk_queries: int = 65536,
-                    graph=None) -> Tensor:
+                    graph=None, uptodate: Optional[Tensor] = None) -> Tensor:
         """scores [B, 1 + C] of every event's true destination (column 0) and of its C candidate destinations cand[i, :]
         on the model's CURRENT state: column 0 is `pos_scores` of contrast_learning on this batch, column 1 + j its
         `neg_scores` had the negatives been cand[:, j] (tiger.py:174-288) - STEP 1-3 over the flat list of B (2 + C)
@@ -786,8 +796,13 @@ class TIGE(nn.Module):
         exactly RANK_EMBED_ROWS rows (see there).  graph: the graph neighbourhoods are sampled from
         (default: model.graph; an evaluation loop passes its collator's).  eval() mode only.  Refused before anything
         runs: strategy 'uniform' (a score would depend on the graph's random stream), a partitioned model, 'vec' hits with
-        2 (d + K) not a multiple of 4 (as the one-call evaluation step)."""
-        graph, strategy = self._pair_refusals('rank_scores', graph, chunk_queries)
+        2 (d + K) not a multiple of 4 (as the one-call evaluation step).
+        uptodate (a bitmap of hip_ops.new_bitmap; TIGER only): lazy restarts - this form WRITES MEMORIES.  Before anything
+        is embedded, ONE `restart_involved` over all B (2 + C) queries restarts every node their embeddings will read
+        that the bitmap does not hold yet, at the earliest event time, and marks it in the bitmap; the scores are then
+        those of the plain form on that state.  The restart never runs per chunk, so a score still does not depend on
+        `chunk_queries`.  A model without a restarter raises NotImplementedError."""
+        graph, strategy = self._pair_refusals('rank_scores', graph, chunk_queries, uptodate)
         dev = self.device
         src_ids, dst_ids = (x.to(dev).long().contiguous() for x in (src_ids, dst_ids))
         cand = torch.as_tensor(cand).to(dev).long()
@@ -797,11 +812,15 @@ class TIGE(nn.Module):
         if cand.dim() != 2 or cand.shape[0] != B or dst_ids.numel() != B or ts.numel() != B:
             raise ValueError(f'rank_scores: {B} events, dst {tuple(dst_ids.shape)}, ts {tuple(ts.shape)}, cand {tuple(cand.shape)}')
         ids_all = torch.cat([dst_ids[:, None], cand], 1)
+        if uptodate is not None:
+            self._restart_pairs(src_ids, ids_all, ts, uptodate, graph)
         return self._pair_scores('rank_scores', src_ids, ids_all, ts, graph, strategy, chunk_queries)
 
-    def _pair_refusals(self, what: str, graph, chunk_queries: int):
+    def _pair_refusals(self, what: str, graph, chunk_queries: int, uptodate=None):
         """what rank_scores and recommend refuse before anything runs -> (graph, its sampling strategy)"""
         self._refuse_partitioned(what)
+        if uptodate is not None and getattr(self, 'restarter_fn', None) is None:
+            raise NotImplementedError(f'{what}: lazy restarts (uptodate) need a model with a restarter (TIGER)')
         graph = self.graph if graph is None else graph
         strategy = getattr(graph, 'strategy', 'recent_edges')
         if strategy not in ('recent_edges', 'recent_nodes'):
@@ -817,6 +836,14 @@ class TIGE(nn.Module):
             raise ValueError('chunk_queries must be positive')
         self.check_graph(graph)
         return graph, strategy
+
+    def _restart_pairs(self, src_ids: Tensor, ids_all: Tensor, ts: Tensor, uptodate: Tensor, graph) -> int:
+        """the lazy restart of rank_scores / recommend: ONE `restart_involved` over the flat query list `_pair_scores`
+        embeds chunk by chunk - the sources, then ids_all [B, C1] flattened, each at its event's time"""
+        dev = self.device
+        ts64 = ts.to(dev).double().contiguous().reshape(-1)
+        nodes = torch.cat([src_ids, ids_all.reshape(-1)])
+        return self.restart_involved(nodes, torch.cat([ts64, ts64.repeat_interleave(ids_all.shape[1])]), uptodate, graph=graph)
 
     def _pair_scores(self, what: str, src_ids: Tensor, ids_all: Tensor, ts: Tensor, graph, strategy: str,
                      chunk_queries: int) -> Tensor:
@@ -894,7 +921,8 @@ class TIGE(nn.Module):
 
     # ---- top-k recommendation ------------------------------------------------------------
     def recommend(self, src_ids: Tensor, ts: Tensor, cand: Tensor, k: int, *, mask: Optional[Tensor] = None,
-                  exclude_seen: bool = False, graph=None, chunk_queries: int = 65536, col_of: Optional[Tensor] = None):
+                  exclude_seen: bool = False, graph=None, chunk_queries: int = 65536, col_of: Optional[Tensor] = None,
+                  uptodate: Optional[Tensor] = None):
         """The k best destinations of every (source, time) query among its candidates, on the model's CURRENT state,
         writing nothing -> (ids int64 [B, k], scores float32 [B, k], n_valid int32 [B]).  cand: int64 [B, C], or [C]
         shared by all queries (a catalogue).  A candidate is left out when it is the padding id 0, when mask[i, j] is false
@@ -905,8 +933,13 @@ class TIGE(nn.Module):
         (the same pair scores through `_pair_scores`, so a pair's bits do not depend on where it stands); queries run in
         chunks of at most `chunk_queries` pair scores.  A non-finite score among the candidates left in raises ValueError.
         Refused before anything runs: whatever rank_scores refuses (strategy 'uniform', a partitioned model, training
-        mode, unaligned 'vec' hits); exclude_seen with per-query candidates."""
-        graph, strategy = self._pair_refusals('recommend', graph, chunk_queries)
+        mode, unaligned 'vec' hits); exclude_seen with per-query candidates.
+        uptodate (a bitmap of hip_ops.new_bitmap; TIGER only): lazy restarts, as in rank_scores - this form WRITES
+        MEMORIES: before the first chunk is scored, ONE `restart_involved` over the B (1 + C) queries (sources, then every
+        query's candidates at its time) restarts what the bitmap does not hold yet and marks it; `last_restarted` holds
+        the count.  A process that has loaded a checkpoint and a graph can answer without replaying the stream: memories
+        at reset, an empty bitmap."""
+        graph, strategy = self._pair_refusals('recommend', graph, chunk_queries, uptodate)
         dev = self.device
         src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
         cand = torch.as_tensor(cand).to(dev).long().contiguous()
@@ -935,6 +968,8 @@ class TIGE(nn.Module):
         n_valid = torch.zeros(B, dtype=torch.int32, device=dev)
         if B == 0 or Cc == 0:
             return out_ids, out_scores, n_valid
+        if uptodate is not None:
+            self._restart_pairs(src_ids, cand.unsqueeze(0).expand(B, -1) if shared else cand, ts64, uptodate, graph)
         bad = torch.zeros(1, dtype=torch.int64, device=dev)
         step = max(1, int(chunk_queries) // (Cc + 1))
         for lo in range(0, B, step):
@@ -1390,6 +1425,36 @@ class TIGER(TIGE):
         check(lib.tg_restart_apply(C.byref(m), nids.numel(), ptr(nids), ptr(h_left.contiguous()),
                                    ptr(h_right.contiguous()), ptr(prev_ts.contiguous()), stream_ptr(dev)),
               'tg_restart_apply')
+
+    @torch.no_grad()
+    def restart_involved(self, nodes: Tensor, ts: Tensor, uptodate: Tensor, *, graph=None) -> int:
+        """The lazy restart of eval_utils.py:37-42 for a flat list of (node, time) queries that are about to be embedded:
+        every node their embeddings will read (the queries, their sampled neighbours, on a two-layer model the neighbours'
+        neighbours - the set GraphCollator.collate_memory_nodes flags) that the bitmap `uptodate` (hip_ops.new_bitmap) does
+        not hold yet is restarted at the earliest query time and marked in the bitmap -> how many were restarted (also
+        kept in `last_restarted`).  One listing call (tg_involved_list: no neighbour list is written), one read-back of the
+        count, then `restart_list` on the device-resident list (SeqRestarter: one library call; anything else: `restart`);
+        per-node tables of a model with eager updates that were current stay current.  graph: the graph the embeddings
+        will sample from (default: model.graph).  eval() mode only.  Refused before anything runs, with state and bitmap
+        untouched: a partitioned model, training mode, strategy 'uniform', a graph of another size, an id outside
+        [0, n_nodes)."""
+        self._refuse_partitioned('restart_involved')
+        if self.training:
+            raise RuntimeError('restart_involved restarts for scoring in eval() mode')
+        graph = self.graph if graph is None else graph
+        strategy = getattr(graph, 'strategy', 'recent_edges')
+        if strategy not in ('recent_edges', 'recent_nodes'):
+            raise NotImplementedError(f"restart_involved lists 'recent_edges' or 'recent_nodes' neighbourhoods; strategy="
+                                      f"{strategy!r} would make the set depend on the graph's random stream")
+        self.check_graph(graph)
+        dev = self.device
+        nodes = torch.as_tensor(nodes).to(dev).long().contiguous().reshape(-1)
+        ts64 = torch.as_tensor(ts).to(dev).double().contiguous().reshape(-1)
+        out = hip_ops.involved_list(graph, nodes, ts64, self.n_neighbors, self.n_layers, uptodate, strategy=strategy)
+        n = self.last_restarted = int(out['count'].item())
+        if n:
+            self.restart_list_keep_tables(out['ids'][:n], out['tmin'])
+        return n
 
     @property
     def graph(self):

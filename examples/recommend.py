@@ -12,6 +12,12 @@ streams as in evaluation.  Writes ids.npy [n_test, k] / scores.npy [n_test, k] a
 only, and every batch first asks `recommend` at its own (source, time) queries and is then ingested with `TIGE.observe`
 (the graph is extended on the device, the batch streams).  The same replay on the full graph with `stream_step` runs
 beside it, and the two lines printed - hit rate / NDCG / MRR@k - must be equal exactly (`run_online` asserts it).
+--window SECONDS and --keep_last M add sliding-window expiry to that replay: after every `observe` the model calls
+`TIGE.forget` (entries older than the batch's last time minus the window, and entries beyond a node's last M, leave the
+device graph) and the entries kept and dropped are printed per batch.  With --keep_last at least max(n_neighbors,
+hist_len), no window and no --exclude_seen the forgetting replay answers exactly what the replay that never forgets
+answers, so the two lines are held to the same equality; a window, a smaller cap or --exclude_seen ("seen inside the
+window") answer from less history, and the two lines may differ.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -95,9 +101,13 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest):
 
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-               device='cuda:0'):
+               device='cuda:0', window=None, keep_last=None, verbose=True, offline=True):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
-    covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`."""
+    covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
+    window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
+    metrics then carry 'forgot': (entries kept, entries dropped) per batch.  The two replays are still equal, and that is
+    asserted, when what is dropped is never read: no window, keep_last >= max(n_neighbors, hist_len), no exclude_seen.
+    offline=False: the online replay alone -> (its metrics, None)."""
     from www2023tiger_amd.data.graph import Graph
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -115,17 +125,34 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     n_seen = len(full_data.src) - len(test.src)   # the test split is the tail of the stream
     start = model.save_memory_state()
     with torch.no_grad():
-        model.graph = full_graph
-        ids_off, offline = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
-                                   lambda s, d, t, e: model.stream_step(s, d, d, t, e))
-        model.load_memory_state(start)
+        ids_off = None
+        if offline:
+            model.graph = full_graph
+            ids_off, offline = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
+                                       lambda s, d, t, e: model.stream_step(s, d, d, t, e))
+            model.load_memory_state(start)
         # the edge table already holds the rows of the test events; a live system hands them to observe(efeats=...)
         model.graph = Graph.from_arrays(full_data.src[:n_seen], full_data.dst[:n_seen], full_data.ts[:n_seen],
                                         full_data.eids[:n_seen], strategy=full_graph.strategy, seed=seed,
                                         max_node_id=full_graph.num_node - 1, device=device)
-        ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs, model.observe)
-    assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
-    return online, offline
+        forgot = []
+
+        def observe_and_forget(s, d, t, e):
+            model.observe(s, d, t, e)
+            before = model.graph.tcsr.num_entry
+            g = model.forget(before=None if window is None else float(t[-1]) - window, keep_last=keep_last)
+            forgot.append((int(g.tcsr.num_entry), int(before - g.tcsr.num_entry)))
+            if verbose:
+                print(f'batch {len(forgot) - 1}: {forgot[-1][0]} entries kept, {forgot[-1][1]} dropped')
+        forgetting = window is not None or keep_last is not None
+        ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
+                                 observe_and_forget if forgetting else model.observe)
+    need = max(n_neighbors, hist_len if restarter_type == 'seq' else 0)
+    if ids_off is not None and (not forgetting or (window is None and keep_last >= need and not exclude_seen)):
+        assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
+    if forgetting:
+        online = dict(online, forgot=forgot)
+    return online, (offline if ids_off is not None else None)
 
 
 def run_cold(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
@@ -186,6 +213,10 @@ if __name__ == '__main__':
                     'starts at train + validation, beside the replay on the full graph')
     ap.add_argument('--cold', action='store_true', help='no replay: memories at reset, lazy restarts of what each batch reads '
                     '(recommend(..., uptodate=bitmap)); prints the restart count per batch')
+    ap.add_argument('--window', type=float, default=None, help='--online: after every observe, forget the entries older '
+                    'than the batch\'s last time minus this many seconds (TIGE.forget)')
+    ap.add_argument('--keep_last', type=int, default=None, help='--online: after every observe, keep every node\'s last M '
+                    'entries (TIGE.forget)')
     a = ap.parse_args()
     if a.cold:
         m, restarted = run_cold(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, seed=a.seed, bs=a.bs,
@@ -195,7 +226,8 @@ if __name__ == '__main__':
         sys.exit(0)
     if a.online:
         for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
-                                                              seed=a.seed, bs=a.bs, restarter_type=a.restarter_type)):
+                                                              seed=a.seed, bs=a.bs, restarter_type=a.restarter_type,
+                                                              window=a.window, keep_last=a.keep_last)):
             print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "
                   f"({m['n_events']} events)")
         sys.exit(0)

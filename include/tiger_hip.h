@@ -117,6 +117,37 @@ int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_t* src_host
                         const double* ts_host, const int64_t* eid_host, int64_t* indptr_out_host, double* ts_out_host,
                         int32_t* nbr_out_host, int32_t* eid_out_host);
 
+/* Sliding-window expiry: the T-CSR of `g` without its expired entries, written to caller-owned arrays; `g` itself is only
+ * read and num_node does not change.  None of the four entries has a counterpart in the reference, which builds its
+ * adjacency lists once over the whole stream and never drops an entry (graph.py:11-42).  Per node v with old row
+ * [b, e) = [indptr[v], indptr[v+1]):
+ *   s = max(b, first p in [b, e) with ts[p] >= t_cut, e - keep_last);   kept row = [s, e)
+ * - an entry is dropped iff its time is STRICTLY below t_cut (the float64 '<' of every sampler's cut, graph.py:44-53:
+ *   trimming and sampling cannot disagree about a boundary) or it is not among its node's last keep_last entries.
+ * - t_cut = -inf switches the horizon off; keep_last < 0 (or >= the longest row) switches the cap off; both off: a copy.
+ *   keep_last = 0 or a t_cut beyond every time give a valid graph with 0 entries.  A NaN t_cut returns TG_EINVAL.
+ * - kept entries keep neighbour id, edge id, the direction flag in bit 31 and the time, bit for bit, and their order.
+ *
+ * tg_tcsr_trim_workspace_bytes (graph.py:11-42: no counterpart): bytes of `ws` for a graph of num_node nodes, 0 for a
+ * bad num_node.  The same `ws`, untouched in between, goes to plan and to apply.
+ * tg_tcsr_trim_plan (graph.py:11-42: no counterpart): two launches over the NODES.  Writes indptr_out[0 .. num_node]
+ * (final; indptr_out[num_node] = number of kept entries) and the row shifts into ws.  The caller reads back that ONE
+ * int64 - the only synchronisation of a trim - to allocate ts_out / nbr_out / eid_out exactly, then calls
+ * tg_tcsr_trim_apply (graph.py:11-42: no counterpart): one launch over the KEPT entries, num_entry_out =
+ * indptr_out[num_node]; ts_out / nbr_out / eid_out hold exactly num_entry_out entries (they may be NULL when it is 0).
+ * All pointers are DEVICE pointers, ws 16-byte aligned; asynchronous on `stream`; a short workspace returns
+ * TG_EWORKSPACE before anything is launched.  No atomics: the result does not depend on the launch geometry.
+ * TG_EINVAL for num_node outside [1, 2^31), num_entry outside [0, 2^32), num_entry_out outside [0, g->num_entry]. */
+size_t tg_tcsr_trim_workspace_bytes(int64_t num_node);
+int tg_tcsr_trim_plan(const tg_tcsr* g, double t_cut, int64_t keep_last, int64_t* indptr_out, void* ws, size_t ws_bytes,
+                      void* stream);
+int tg_tcsr_trim_apply(const tg_tcsr* g, const int64_t* indptr_out, int64_t num_entry_out, double* ts_out,
+                       int32_t* nbr_out, int32_t* eid_out, const void* ws, size_t ws_bytes, void* stream);
+/* tg_tcsr_trim_host (graph.py:11-42: no counterpart): the host twin, HOST pointers (those of `g` included), plain C++.
+ * The out arrays have capacity g->num_entry; *num_entry_out = kept entries = indptr_out_host[num_node]. */
+int tg_tcsr_trim_host(const tg_tcsr* g, double t_cut, int64_t keep_last, int64_t* indptr_out_host, double* ts_out_host,
+                      int32_t* nbr_out_host, int32_t* eid_out_host, int64_t* num_entry_out);
+
 /* Graph.sample_temporal_neighbor(strategy='recent_edges') and Graph.get_history
  * (graph.py:67-127,150-155): per query the last K entries with ts < t (strict),
  * left padded with zeros.  out_dir may be NULL.  If mark_flags != NULL every query

@@ -8,10 +8,12 @@ types, but the per-query Python loop (graph.py:94-146, "Bottleneck! Total time
 The object is immutable after construction, so the collator thread and the main
 thread may sample concurrently (each call allocates its own outputs and runs on
 the calling thread's current stream).  New events are ingested by `extended`, which
-returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was.
+returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was; old entries
+are dropped by `trimmed` (csrc/tg_trim.hip), which does the same.
 """
 import ctypes as C
 import itertools
+import operator
 from typing import Optional, Tuple
 
 import numpy as np
@@ -25,11 +27,12 @@ from ..hip_ops import stream_ptr
 class _HostRoot:
     """Host-side origin of a graph: the events of from_arrays and / or the host T-CSR arrays.  Shared by reference along a
     chain of `extended` graphs until one of them materialises its own host view."""
-    __slots__ = ('events', 'host')
+    __slots__ = ('events', 'host', 'dev')
 
     def __init__(self):
         self.events = None  # (src, dst, ts, eids) of from_arrays, the input of either builder
         self.host = None    # host T-CSR arrays (indptr, ts, nbr, eid), built on demand
+        self.dev = None     # a graph trimmed on the device: its device arrays, which `host` is downloaded from on demand
 
 
 _SERIAL = itertools.count(1)  # process-wide: next() is atomic under the GIL
@@ -113,8 +116,7 @@ class Graph:
         if old.events is not None:
             new.events = tuple(np.concatenate([a, b]) for a, b in zip(old.events, (src, dst, ts, eids)))
         if old.host is not None or old.events is None or not self._time_ordered:
-            if old.host is None:
-                old.host = self._build_host(old.events)
+            self._host_of(old)
             n = len(src)
             h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(len(old.host[1]) + 2 * n, dtype=np.float64),
                  np.empty(len(old.host[1]) + 2 * n, dtype=np.int32), np.empty(len(old.host[1]) + 2 * n, dtype=np.int32))
@@ -155,11 +157,20 @@ class Graph:
               'tg_tcsr_build_host')
         return h
 
+    def _host_of(self, root):
+        """the host T-CSR arrays of a root: built from its events, or (a graph trimmed on the device has no event list)
+        downloaded from its device arrays"""
+        if root.host is None:
+            if root.dev is not None:
+                root.host = tuple(np.ascontiguousarray(t.cpu().numpy()) for t in root.dev)
+            else:
+                root.host = self._build_host(root.events)
+        root.dev = None
+        return root.host
+
     def _host_tcsr(self):
         self._materialise()
-        if self._host is None:
-            self._host = self._build_host(self._events)
-        return self._host
+        return self._host_of(self._root)
 
     _h_indptr = property(lambda self: self._host_tcsr()[0])
     _h_ts = property(lambda self: self._host_tcsr()[1])
@@ -276,6 +287,8 @@ class Graph:
         old_entries = self._dev[1].numel() if self._dev is not None else None
         if old_entries is None:
             self._materialise()
+            if self._root.events is None:
+                self._host_tcsr()
             old_entries = len(self._host[1]) if self._host is not None else 2 * len(self._root.events[0])
         if old_entries + 2 * n >= 2 ** 32:
             raise ValueError('extended: the device T-CSR holds fewer than 2^32 entries')
@@ -301,6 +314,72 @@ class Graph:
             child._mt = self._mt_state()
         child._root, child._log = self._root, (self._log, batch)
         child.last_batch = batch
+        return child
+
+    # ---- sliding-window expiry --------------------------------------------------------
+    def trimmed(self, before: Optional[float] = None, keep_last: Optional[int] = None) -> 'Graph':
+        """A NEW Graph without this graph's expired entries (tg_tcsr_trim_*; graph.py:11-42 has no counterpart: the
+        reference builds its adjacency lists once and never drops an entry).  An entry is dropped if its time is strictly
+        below `before` (the float64 '<' of every sampler's cut) or if it is not among its node's last `keep_last` entries;
+        None switches a rule off, both None give a copy.  This graph stays valid and unchanged, and the child holds no
+        reference to it: dropping the parent releases its memory.  num_node does not change.
+        A device-resident parent is trimmed on the device, on the current stream with allocator-owned buffers: a plan
+        over the nodes, ONE int64 read back (the number of kept entries - the only synchronisation - so that the child's
+        arrays are allocated exactly), a copy over the kept entries.  A host-only parent takes the host twin at once.
+        strategy / seed / alpha / device carry over, the child shares the parent's `rng` and device MT19937 state, and it
+        keeps the parent's latest event time EVEN WHEN EVERY ENTRY WAS DROPPED: a later `extended` still refuses to go
+        back in time.  The child has a `serial` of its own.  Its host view is produced on first use (downloaded from its
+        own device arrays); a graph trimmed on the device, or with a cap, no longer corresponds to an event list and has
+        `_events` None.  `extended`, `to` and the samplers work on it as on any graph.
+        Guarantees: with `before` alone the result is what `from_arrays` over the events with ts >= before builds, bit
+        for bit.  After any trim a query (v, t) sees the parent's entries before t restricted to the kept ones, so
+        `recent_edges` with K <= keep_last and `get_history` with H <= keep_last return the parent's result at every t
+        later than the graph's latest time.  (A second hop is sampled at the neighbours' EARLIER times: no such guarantee.)
+        ValueError before anything is launched: a NaN `before`, a negative `keep_last`."""
+        t_cut = -np.inf if before is None else float(before)
+        if t_cut != t_cut:
+            raise ValueError('trimmed: `before` is NaN')
+        keep = -1 if keep_last is None else operator.index(keep_last)
+        if keep_last is not None and keep < 0:
+            raise ValueError(f'trimmed: keep_last = {keep} is negative')
+        child = Graph.__new__(Graph)
+        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
+        child._time_ordered = self._time_ordered
+        child._t_last = self._t_last
+        if self._dev is not None:  # device-resident parent: plan, one read-back, allocate exactly, apply
+            dev = self.device
+            g = self.tcsr
+            indptr = torch.empty(self.num_node + 1, dtype=torch.int64, device=dev)
+            nbytes = int(lib.tg_tcsr_trim_workspace_bytes(self.num_node))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(lib.tg_tcsr_trim_plan(C.byref(g), t_cut, keep, ptr(indptr), ptr(ws), nbytes, stream_ptr(dev)),
+                      'tg_tcsr_trim_plan')
+                P = int(indptr[-1])  # the one read-back
+                out = (indptr, torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                       torch.empty(P, dtype=torch.int32, device=dev))
+                # (parent arrays and workspace belong to the caching allocator: reused in stream order, no wait needed)
+                check(lib.tg_tcsr_trim_apply(C.byref(g), ptr(indptr), P, *(ptr(t) for t in out[1:]), ptr(ws), nbytes,
+                                             stream_ptr(dev)), 'tg_tcsr_trim_apply')
+            child._dev = out
+            child._set_struct()
+            child._mt = self._mt_state()
+            child._root.dev = out
+        else:
+            h = self._host_tcsr()
+            P0 = len(h[1])
+            out = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(P0, dtype=np.float64),
+                   np.empty(P0, dtype=np.int32), np.empty(P0, dtype=np.int32))
+            kept = C.c_int64(0)
+            gs = TgTcsr(self.num_node, P0, *(ptr(a) for a in h))
+            check(lib.tg_tcsr_trim_host(C.byref(gs), t_cut, keep, *(ptr(a) for a in out), C.byref(kept)), 'tg_tcsr_trim_host')
+            child._host = (out[0],) + tuple(a[:kept.value].copy() for a in out[1:])  # (copies: the full-size arrays die)
+            ev = self._root.events
+            if keep_last is None and ev is not None:  # a horizon alone: still the T-CSR of an event list
+                m = ev[2] >= t_cut
+                child._events = tuple(np.ascontiguousarray(a[m]) for a in ev)
+            if self._mt is not None:
+                child._mt = self._mt
         return child
 
     # ---- sampling -------------------------------------------------------------------

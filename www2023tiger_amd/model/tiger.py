@@ -1302,6 +1302,19 @@ class TIGE(nn.Module):
             src, dst, ts, eids = new_graph.last_batch
         return self.stream_step(src, dst, dst if neg is None else neg, ts, eids, want_prev=want_prev)
 
+    def forget(self, before=None, keep_last=None):
+        """Sliding-window expiry for a model that keeps observing: the graph is replaced by `graph.trimmed(before,
+        keep_last)` (entries with a time strictly below `before`, and entries that are not among their node's last
+        `keep_last`, are dropped) -> the new graph.  Only the graph changes: memories, mailbox and tables are not touched,
+        and the edge-feature table keeps its rows (eids are row indices).  A one-layer `recent_edges` model with
+        n_neighbors and hist_len <= keep_last that forgets after every `observe` stays bit-identical to one that never
+        forgets; a two-layer model does not (hop 2 is sampled at the neighbours' earlier times).  Afterwards
+        `recommend(..., exclude_seen=True)` means "seen inside the window".  Refused before anything runs: a partitioned
+        model, and what `Graph.trimmed` refuses (a NaN `before`, a negative `keep_last`)."""
+        self._refuse_partitioned('forget')
+        self.graph = self.graph.trimmed(before=before, keep_last=keep_last)
+        return self.graph
+
     # ---- remaining reference methods -----------------------------------------------------
     @torch.no_grad()
     def update_right_memory(self, node_ids: Tensor, new_vals: Tensor, ts: Tensor):

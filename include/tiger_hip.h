@@ -918,7 +918,8 @@ int tg_adam_step(const tg_adam_seg* segs_dev, int32_t n_segs, int32_t n_groups, 
  * average_precision_score and roc_auc_score of the predictions [pos | neg] with labels [1 | 0],
  * ties handled as sklearn does.  pos_pred / neg_pred: [n] probabilities (sigmoid of the logits);
  * ap / auc: double[ceil(n / chunk)] on device.  Non-finite predictions are dropped from their
- * window and counted in *n_nonfinite (nullable, device int32, not reset here). */
+ * window and counted in *n_nonfinite (nullable, device int32, not reset here).  A window's AP is
+ * 0.0 when no positive has a finite score, its AUC 0.0 when a class has no finite score. */
 int tg_ap_auc(int64_t n, int32_t chunk, const float* pos_pred, const float* neg_pred, double* ap, double* auc,
               int32_t* n_nonfinite, void* stream);
 

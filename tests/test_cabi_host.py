@@ -167,3 +167,61 @@ def test_graft_entry_module_imports_and_builds():
     importlib.reload(g)
     g.build()
     assert callable(g.smoke)
+
+
+def test_linear_bwd_refuses_bad_arguments_before_any_device_call():
+    """tg_linear_bwd: the argument and workspace checks come first - callable here, without a GPU (the pointers are host
+    arrays that are never dereferenced)"""
+    from www2023tiger_amd import _lib
+    lib, ptr = _lib.lib, _lib.ptr
+    n, in_f, out_f = 5, 8, 12
+    x, w, dy = np.zeros((n, in_f), np.float32), np.zeros((out_f, in_f), np.float32), np.zeros((n, out_f), np.float32)
+    dx, dw, db = np.zeros_like(x), np.zeros_like(w), np.zeros(out_f, np.float32)
+    need = lib.tg_linear_bwd_workspace_bytes(in_f, out_f)
+    assert need >= 16 * out_f * (in_f + 1) * 4
+    ws = np.zeros(need, np.uint8)
+
+    def call(n=n, x=x, in_f=in_f, w=w, out_f=out_f, dy=dy, dx=dx, dw=dw, db=db, ws=ws, ws_bytes=need):
+        return lib.tg_linear_bwd(n, ptr(x), in_f, ptr(w), out_f, ptr(dy), ptr(dx), ptr(dw), ptr(db), ptr(ws), ws_bytes, None)
+
+    assert call(n=-1) == _lib.TG_EINVAL
+    assert call(in_f=6) == _lib.TG_EINVAL
+    assert call(in_f=0) == _lib.TG_EINVAL
+    assert call(out_f=10) == _lib.TG_EINVAL
+    assert call(out_f=0) == _lib.TG_EINVAL
+    assert call(dy=None) == _lib.TG_EINVAL
+    assert call(x=None) == _lib.TG_EINVAL                      # dw without x
+    assert call(w=None) == _lib.TG_EINVAL                      # dx without w
+    assert call(dx=None, db=None, ws=None) == _lib.TG_EINVAL   # dw without a workspace
+    assert call(dx=None, dw=None, ws=None) == _lib.TG_EINVAL   # db without a workspace
+    assert call(n=0) == _lib.TG_OK
+    assert call(n=0, dy=None, ws=None) == _lib.TG_OK           # nothing to do: nothing is looked at
+    assert call(dx=None, ws_bytes=need - 1) == _lib.TG_EWORKSPACE
+    assert call(dx=None, db=None, ws_bytes=0) == _lib.TG_EWORKSPACE
+    assert lib.tg_linear_bwd_workspace_bytes(0, out_f) == 0 and lib.tg_linear_bwd_workspace_bytes(in_f, -4) == 0
+    for a in (dx, dw, db):
+        assert not a.any()
+
+
+def test_adam_step_and_ap_auc_refuse_bad_arguments_before_any_device_call():
+    """tg_adam_step, tg_ap_auc: argument checks come first - callable here, without a GPU"""
+    from www2023tiger_amd import _lib
+    lib, ptr = _lib.lib, _lib.ptr
+    segs = (_lib.TgAdamSeg * 2)()
+    steps = np.zeros(4, np.int32)
+    sp = ctypes.addressof(segs)
+    adam = lambda s, n_segs, n_groups, st: lib.tg_adam_step(s, n_segs, n_groups, None, st, 1e-3, 0.9, 0.999, 1e-8, 1.0, None)
+    assert adam(None, 2, 4, ptr(steps)) == _lib.TG_EINVAL
+    assert adam(sp, 2, 4, None) == _lib.TG_EINVAL
+    for bad in (0, -1):
+        assert adam(sp, bad, 4, ptr(steps)) == _lib.TG_EINVAL
+        assert adam(sp, 2, bad, ptr(steps)) == _lib.TG_EINVAL
+    assert not steps.any()
+    pos, neg = np.zeros(8, np.float32), np.zeros(8, np.float32)
+    ap, auc = np.full(2, -1.0), np.full(2, -1.0)
+    metric = lambda n, chunk: lib.tg_ap_auc(n, chunk, ptr(pos), ptr(neg), ptr(ap), ptr(auc), None, None)
+    assert metric(-1, 4) == _lib.TG_EINVAL
+    assert metric(8, 0) == _lib.TG_EINVAL
+    assert metric(8, -4) == _lib.TG_EINVAL
+    assert metric(0, 4) == _lib.TG_OK
+    assert (ap == -1.0).all() and (auc == -1.0).all()

@@ -36,6 +36,92 @@ def test_ap_auc_matches_sklearn():
     assert abs(float(ap2[1]) - average_precision_score(np.r_[np.ones(50), np.zeros(50)], sc)) < 1e-12
 
 
+def _pair_counting_ap_auc(pos, neg):
+    """the formulas of tg_metrics.hip's header comment on the finite scores of one window, in float64; 0.0 where a
+    class has no finite score (AP: no positive; AUC: no positive or no negative) - sklearn is undefined there"""
+    p = pos[np.isfinite(pos)].astype(np.float64)
+    q = neg[np.isfinite(neg)].astype(np.float64)
+    if p.size == 0:
+        return 0.0, 0.0, p.size, q.size
+    pge = (p[None, :] >= p[:, None]).sum(1)
+    nge = (q[None, :] >= p[:, None]).sum(1)
+    ngt = (q[None, :] > p[:, None]).sum(1)
+    ap = float((pge / (pge + nge)).sum() / p.size)
+    auc = float(((q.size - nge) + 0.5 * (nge - ngt)).sum() / (p.size * q.size)) if q.size else 0.0
+    return ap, auc, p.size, q.size
+
+
+def _window_scores(n, chunk, seed=0):
+    """the recipe of test_ap_auc_matches_sklearn: saturated ties within and between the classes, a run of neg == pos, and
+    non-finite runs (NaN in neg, +-inf in pos) that cross the first and the second window boundary"""
+    rs = np.random.RandomState(seed)
+    pos = rs.uniform(0, 1, n).astype(np.float32)
+    neg = rs.uniform(0, 1, n).astype(np.float32)
+    pos[::7] = np.float32(1.0)
+    neg[::11] = np.float32(1.0)
+    neg[5:40] = pos[5:40]
+    neg[max(0, chunk - 2):chunk + 2] = np.nan
+    pos[2 * chunk - 1] = np.inf
+    pos[2 * chunk] = -np.inf
+    return pos, neg
+
+
+def _check_windows(pos, neg, chunk, ap, auc):
+    from sklearn.metrics import average_precision_score, roc_auc_score
+    n = len(pos)
+    assert len(ap) == len(auc) == -(-n // chunk)
+    both = 0
+    for i in range(len(ap)):
+        pw, qw = pos[i * chunk:(i + 1) * chunk], neg[i * chunk:(i + 1) * chunk]
+        ap_f, auc_f, P, N = _pair_counting_ap_auc(pw, qw)
+        if P > 0 and N > 0:  # sklearn where it is defined
+            both += 1
+            sc = np.concatenate([pw[np.isfinite(pw)], qw[np.isfinite(qw)]])
+            lab = np.concatenate([np.ones(P), np.zeros(N)])
+            assert abs(float(ap[i]) - average_precision_score(lab, sc)) < 1e-12, (chunk, i)
+            assert abs(float(auc[i]) - roc_auc_score(lab, sc)) < 1e-12, (chunk, i)
+        assert abs(float(ap[i]) - ap_f) < 1e-12, (chunk, i, P, N)
+        assert abs(float(auc[i]) - auc_f) < 1e-12, (chunk, i, P, N)
+    return both
+
+
+@pytest.mark.parametrize('chunk', [1, 2, 255, 256, 257, 600])
+def test_ap_auc_window_sizes(chunk):
+    """windows below, at and above the kernel's 256 threads (the second pass of its strided loops), ragged last window"""
+    from www2023tiger_amd.eval_utils import ap_auc_windows
+    n = 3 * chunk + max(1, chunk // 2)
+    pos, neg = _window_scores(n, chunk)
+    ap, auc, bad = ap_auc_windows(torch.from_numpy(pos).to(dev()), torch.from_numpy(neg).to(dev()), chunk)
+    assert int(bad.item()) == int((~np.isfinite(pos)).sum() + (~np.isfinite(neg)).sum())
+    both = _check_windows(pos, neg, chunk, ap.cpu().numpy(), auc.cpu().numpy())
+    assert both >= 1 and (chunk > 2 or both < 4)  # (windows of 1 and 2 scores also lose whole classes)
+
+
+def test_ap_auc_window_without_a_finite_score():
+    """one window entirely non-finite: its AP and AUC are 0.0, its neighbours are unaffected, and the counter - which
+    tg_ap_auc does not reset - adds up over two calls"""
+    from www2023tiger_amd._lib import check, lib, ptr
+    from www2023tiger_amd.hip_ops import stream_ptr
+    chunk = 256
+    n = 3 * chunk + chunk // 2
+    pos, neg = _window_scores(n, chunk)
+    pos[chunk:2 * chunk] = np.nan
+    pos[chunk + 3:2 * chunk:5] = np.inf
+    neg[chunk:2 * chunk] = -np.inf
+    neg[chunk + 1:2 * chunk:3] = np.nan
+    total = int((~np.isfinite(pos)).sum() + (~np.isfinite(neg)).sum())
+    assert total > 2 * chunk
+    pd, nd = torch.from_numpy(pos).to(dev()), torch.from_numpy(neg).to(dev())
+    ap = torch.full((4,), -1.0, dtype=torch.float64, device=dev())
+    auc = torch.full((4,), -1.0, dtype=torch.float64, device=dev())
+    bad = torch.zeros(1, dtype=torch.int32, device=dev())
+    for call in (1, 2):
+        check(lib.tg_ap_auc(n, chunk, ptr(pd), ptr(nd), ptr(ap), ptr(auc), ptr(bad), stream_ptr(dev())), 'tg_ap_auc')
+        assert int(bad.item()) == call * total
+        assert float(ap[1]) == 0.0 and float(auc[1]) == 0.0
+        assert _check_windows(pos, neg, chunk, ap.cpu().numpy(), auc.cpu().numpy()) == 3
+
+
 @pytest.mark.parametrize('name', ['eval_seq_lr_d8', 'eval_static_ll_d16'])
 def test_eval_harness_matches_reference(name):
     from torch.utils.data import DataLoader

@@ -372,11 +372,10 @@ typedef struct tg_model {
  * `fused` receives tg_attn_fused_floats(m) floats: Wqk [n_head*kvw, d], gconst [n_head*kvw],
  * W1f [d, n_head*kvw + d], b1 [d], c1 [d]  (kvw = 2d + d_e).  Must be recomputed whenever an attention
  * parameter or the time encoder changes; training (tg_train_step) ignores it.
- * Where the attention block fits one workgroup (d, d_e <= 256, the tiles of 16 centres inside one CU's 160 KB of LDS)
- * the same weights and fc2 follow once more in FRAGMENT-MAJOR order (csrc/tg_tile.h) and the forward pass of a model
- * carrying `attn_fused` runs the whole block - G product, neighbour gather / softmax, merged value-out-fc1 product,
- * fc2 (temporal_agg_modules.py:48-81,210-235; basic_modules.py:16-19) - as ONE launch per batch with G and S in LDS
- * only (k_attn_tile).  tg_attn_tile_applies: 1 when that form will be taken for `m` (TG_ATTN_TILE=0 switches it off). */
+ * Without an edge table (m->efeats NULL) the blob is compact: the edge segment of a key row is zeros, its columns are
+ * dropped and kvw = 2d.  tg_attn_fused_floats is exactly n_head*kvw*d + n_head*kvw + d*(n_head*kvw + d) + 2d.
+ * tg_attn_tile_applies: always 0.  It told whether the one-launch attention tile would be taken; that form is retired
+ * (it measured slower, tools/experiments/README.md) and the export stays for callers that still ask. */
 size_t tg_attn_fused_floats(const tg_model* m);
 size_t tg_attn_fuse_workspace_bytes(const tg_model* m);
 int tg_attn_fuse(const tg_model* m, float* fused, void* ws, size_t ws_bytes, void* stream);

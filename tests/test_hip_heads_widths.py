@@ -2,7 +2,7 @@
 
 The kernels branch on the number of attention heads and on the widths of the node memory (d) and of the edge
 features (d_e):
-  k_attn_core<NH, NV, W, FS>  (csrc/tg_model.hip, launch_attn_core): NH = n_head; W = 2 columns per lane when
+  k_attn_core<NH, NV, W, FS>  (csrc/tg_attn.hip, launch_attn_core): NH = n_head; W = 2 columns per lane when
       max(d, d_e) <= 128, else 4; NV = float4 per lane, 2 when max(d, d_e) > 256; FS = feature streams per key
       (2: node + edge tables, 1: edge table only - no node table, or the node rows come from the per-node table of
       centre rows of the eager + pre-multiplied form - 0: no edge table and no node stream)
@@ -243,3 +243,30 @@ def test_configurations_outside_the_dispatch_refuse(nh, d, d_e, step):
             TrainBuffers(model, 20, mutual=True).launch()
     torch.cuda.synchronize()
     assert torch.equal(before[0], model.left_memory.vals) and torch.equal(before[1], model.right_memory.vals)
+
+
+# ------------------------------------------------------------------------------ the pre-multiplied weights' blob
+@pytest.mark.parametrize('efeats', [True, False], ids=['E', 'noE'])
+@pytest.mark.parametrize('nh,d,d_e', [(2, 8, 4), (1, 16, 16), (4, 32, 4)], ids=lambda v: str(v))
+def test_fused_blob_has_the_documented_size_and_is_written_whole(nh, d, d_e, efeats):
+    """tg_attn_fuse's output (include/tiger_hip.h): [Wqk [nk, d] | gconst [nk] | W1f [d, nk + d] | b1 [d] | c1 [d]] with
+    nk = n_head (2 d + d_e), or n_head 2 d without an edge table (the compact form) - tg_attn_fused_floats is exactly
+    that, every float of it is written (random weights: none stays NaN) and nothing behind it is touched.  The smallest
+    shapes that cover the three head counts, the compact path and d != d_e."""
+    import ctypes as C
+    from www2023tiger_amd._lib import check, lib, ptr
+    from www2023tiger_amd.hip_ops import stream_ptr
+    model, _, _ = build(nh, d, d_e, efeats=efeats, E=40, n_u=10, n_i=5, K=5)
+    m = model.model_struct()
+    nk = nh * (2 * d + d_e) if efeats else nh * 2 * d
+    n = int(lib.tg_attn_fused_floats(C.byref(m)))
+    assert n == nk * d + nk + d * (nk + d) + 2 * d
+    guard = 64
+    blob = torch.full((n + guard,), float('nan'), dtype=torch.float32, device=dev())
+    nbytes = int(lib.tg_attn_fuse_workspace_bytes(C.byref(m)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev())
+    check(lib.tg_attn_fuse(C.byref(m), ptr(blob), ptr(ws), nbytes, stream_ptr(dev())), 'tg_attn_fuse')
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(blob[:n]).all()), int((~torch.isfinite(blob[:n])).sum())
+    assert bool(torch.isnan(blob[n:]).all())
+    assert lib.tg_attn_tile_applies(C.byref(m)) == 0

@@ -3,9 +3,9 @@
 The library takes any n_neighbors up to one wavefront (64); K = 16 is where the samplers switch from 16 lanes per query to a
 whole wavefront (sample_batch_launch, sample_edges_f32_launch, tg_sample_recent_edges), where the collate prefetch stops
 applying (tg_stream_step: `K <= 16`) and the uniform sampler refuses, and lane 15 is the highest lane the rest of the
-suite fills in k_attn_core / k_attn_tile / k_attn_core_bwd / k_build_pairs / tg_rank_scores (one key per lane, `lane < K`).
+suite fills in k_attn_core / k_attn_core_bwd / k_build_pairs / tg_rank_scores (one key per lane, `lane < K`).
 K = 17, 20, 33, 64 are 1, 0, 1, 0 mod 4; 2, 2, 0, 1 mod 3; 5, 2, 3, 4 mod 6 and odd / even: every depth PD of
-k_attn_core's register ring (csrc/tg_model.hip: 2 / 3 / 4 / 6 by <NV, W, FS>) meets a last round that is cut short by
+k_attn_core's register ring (csrc/tg_attn.hip: 2 / 3 / 4 / 6 by <NV, W, FS>) meets a last round that is cut short by
 `min(k + PD, K - 1)`, and - but for PD = 6 - a full one.
 
 Stream: bench.make_stream(40, 6, 640, 5000.0, seed=3): 40 users on 6 items, so lists fill up fast.  Live keys per query of
@@ -89,8 +89,8 @@ STREAM_CASES = [  # (n_head, d, d_e, K, node table, edge table, form, pre-multip
     (2, 300, 300, 17, False, False, 'lazy', True),        # <2,2,4,0>  PD 3, 17 = 5 * 3 + 2
     (2, 300, 300, 33, False, False, 'lazy', True),        #            PD 3, full last round
 ]
-# the eager + lean + pre-multiplied cases the one-launch tile kernel serves (d, d_e <= 256): one per K
-TILE_CASES = [(2, 64, 20, 17, True, True, 'eager-lean', True)] + [c for c in STREAM_CASES if c[6] == 'eager-lean' and c[1] <= 256]
+# eager + lean + pre-multiplied cases (d, d_e <= 256), one per K, run once more without the query-row table (TG_GTAB=0)
+NO_GTAB_CASES = [(2, 64, 20, 17, True, True, 'eager-lean', True)] + [c for c in STREAM_CASES if c[6] == 'eager-lean' and c[1] <= 256]
 
 
 def case_id(c):
@@ -118,33 +118,29 @@ def test_stream_step_with_wide_neighbourhoods(nh, d, d_e, K, nfeats, efeats, for
     run_stream_case(nh, d, d_e, K, nfeats, efeats, form, fuse)
 
 
-def tile_child():
-    """body of the child process of test_one_launch_tile_kernel_with_wide_neighbourhoods"""
-    import ctypes as C
-    from www2023tiger_amd._lib import lib
-    assert sorted(c[3] for c in TILE_CASES) == [17, 20, 33, 64]
-    applied = 0
-    for c in TILE_CASES:
-        print('tile case', case_id(c), flush=True)
-        model = run_stream_case(*c)
-        assert lib.tg_attn_tile_applies(C.byref(model.model_struct())) == 1, case_id(c)
-        applied += 1
-    print(f'TILE CASES OK {applied}', flush=True)
+def no_gtab_child():
+    """body of the child process of test_stream_step_without_query_row_table_with_wide_neighbourhoods"""
+    assert sorted(c[3] for c in NO_GTAB_CASES) == [17, 20, 33, 64]
+    done = 0
+    for c in NO_GTAB_CASES:
+        print('no-gtab case', case_id(c), flush=True)
+        run_stream_case(*c)
+        done += 1
+    print(f'NO GTAB CASES OK {done}', flush=True)
 
 
-def test_one_launch_tile_kernel_with_wide_neighbourhoods():
-    """k_attn_tile (csrc/tg_attn_tile.hip; phase P2 is the one-key-per-lane core) serves the eager + lean + pre-multiplied
-    step where tg_attn_tile_applies - a form that is off by default and that the library selects once per process
-    (TG_ATTN_TILE=1, without the query-row table), so the cases run in a child process: one per K, the same checks as
-    above, and the tile form applied to every one of them."""
-    env = dict(os.environ, TG_GTAB='0', TG_ATTN_TILE='1')
+def test_stream_step_without_query_row_table_with_wide_neighbourhoods():
+    """Without the query-row table (TG_GTAB=0, read once per process, so the cases run in a child process) the eager + lean +
+    pre-multiplied step runs the G product per batch: k_attn_core reads G from the workspace instead of tg_model.g_table and
+    the centres launch copies the centre rows.  One case per K, the same checks as above."""
+    env = dict(os.environ, TG_GTAB='0')
     env.setdefault('OMP_NUM_THREADS', '4')
     here = os.path.dirname(os.path.abspath(__file__))
     code = (f'import sys; sys.path[:0] = [{os.path.dirname(here)!r}, {here!r}]; '
-            'import test_hip_wide_neighbourhoods as t; t.tile_child()')
+            'import test_hip_wide_neighbourhoods as t; t.no_gtab_child()')
     r = subprocess.run([sys.executable, '-c', code], env=env, cwd=os.path.dirname(here), capture_output=True, text=True,
                        timeout=600)
-    assert r.returncode == 0 and f'TILE CASES OK {len(TILE_CASES)}' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    assert r.returncode == 0 and f'NO GTAB CASES OK {len(NO_GTAB_CASES)}' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 # ------------------------------------------------------------------------------ 2. two layers, K = 17 / 20

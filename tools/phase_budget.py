@@ -4,7 +4,7 @@ s_memtime stamps per workgroup of ONE launch of the timed form - entry -> first 
 - plus the launch's own span (first entry -> last exit) and the stagger of the workgroups' entries.
 Needs a library with the stamps compiled in (they cost registers, so the production build leaves them out):
   make -C www2023tiger_amd/csrc clean && make -C www2023tiger_amd/csrc -j16 EXTRA='-DTG_PHASE_TRACE -DTG_CORE_TRACE'
-usage: python tools/phase_budget.py fc1|fc2|qrows|updater|core|tile   (one launch kind per process: the library reads its
+usage: python tools/phase_budget.py fc1|fc2|qrows|updater|core   (one launch kind per process: the library reads its
 knobs once; tools/phase_budget.sh runs them all and prints the table)"""
 import ctypes as C
 import os
@@ -21,8 +21,6 @@ elif which == 'updater':
     os.environ['TG_GRU_DBG'] = '16'
 elif which == 'core':
     os.environ['TG_CORE_DBG'] = '1'
-elif which == 'tile':
-    os.environ.update(TG_TILE_DBG='1', TG_GTAB='0', TG_ATTN_TILE='1')
 import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,7 +35,7 @@ model, _ = bench.build_models(st, c['d'], c['K'], c['msg_src'], c['upd_src'])
 model.fuse_attention()
 model.eager_updates()
 res = tuple(torch.from_numpy(st[k]).to(model.device) for k in ('src', 'dst', 'neg', 'ts', 'eids'))
-buf = model.StepBuffers(model, B, False, resident=res, prefetch=which != 'tile')
+buf = model.StepBuffers(model, B, False, resident=res, prefetch=True)
 buf.io.lean = 1
 for b in range(nb):
     model.launch_step(buf)
@@ -78,15 +76,3 @@ elif which == 'core':
     for k, nme in enumerate(['entry -> lists arrived', 'lists -> first key reduced', 'first key -> keys done', 'keys done -> exit']):
         print(stats(nme, t[:, k + 1] - t[:, k]))
     print(stats('wavefront lifetime', t[:, 4] - t[:, 0]))
-elif which == 'tile':
-    nbk = 512
-    t = np.zeros(nbk * 16 * 8, dtype=np.uint64)
-    assert raw.tg_debug_tile_trace(t.ctypes.data_as(C.c_void_p), nbk) == 0
-    t = t.reshape(nbk, 16, 8).astype(np.int64)
-    live = t[:, :, 0] > 0
-    blocks = live.any(1)
-    t, live = t[blocks], live[blocks]
-    print(f'tile (one-launch attention k_attn_tile: G product + core + fc1 + fc2 per 16 centres): {len(t)} workgroups; s_memtime ticks')
-    for i, nme in enumerate(['P0 centre rows', 'P1 G product', 'P2 core (own centres)', 'P2 wait at barrier', 'P3 fc1 product', 'P4 fc2 + store']):
-        print(stats(nme, (t[:, :, i + 1] - t[:, :, i])[live]))
-    print(stats('workgroup lifetime', (t[:, :, 6] - t[:, :, 0])[live]))

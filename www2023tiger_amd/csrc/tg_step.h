@@ -88,7 +88,17 @@ int apply_messages_rows(const tg_model* m, const int64_t* rows, const int32_t* r
                         uint32_t* err, void* ws, size_t ws_bytes, hipStream_t st);
 
 bool carve_step(const tg_model* m, int64_t B, Carver& cv, StepWs& w, int n_layers = 1);
+// ---- the temporal attention (tg_attn.hip)
 int attn_dims_ok(const tg_model* m);
+bool carve_attn(const tg_model* m, int64_t Q, Carver& cv, AttnWs& w);
+int attn_forward(const tg_model* m, int64_t Q, const int64_t* nids, const float* ts, const int64_t* l1_nids,
+                 const int64_t* l1_eids, const float* l1_ts, const float* reprs, const uint64_t* bm,
+                 const uint32_t* rank, float* out, const AttnWs& w, hipStream_t st, tg_profiler* pf = nullptr,
+                 const DropCfg* drop = nullptr, const PosArgs* pos = nullptr, const DirectArgs* da = nullptr,
+                 const float* key_rows = nullptr, bool centres_done = false, bool use_gtab = false,
+                 const WbRider* wbr = nullptr, bool* wb_rode = nullptr);
+void centre_rows_launch(const tg_model* m, int64_t n, const int64_t* nids, const float* reprs, const uint64_t* bm,
+                        const uint32_t* rank, float* out, bool direct, hipStream_t st);
 int gtab_rows(const tg_model* m, int64_t cap, const int64_t* nids, const int32_t* rows32, const int32_t* n_dev, float* crows,
               hipStream_t st, bool crows_ready, const CollateRider* collate = nullptr, bool* rode = nullptr,
               int64_t rows_hint = 0);

@@ -4,7 +4,7 @@
 // 186-235), the GRU updater (update_modules.py:30-37) and the time encoder
 // (time_encoding.py:24-26), and torch.optim.Adam (train_self_supervised.py:114,170).
 //
-// The backward pass follows the restructured forward of tg_model.hip (query folded through
+// The backward pass follows the restructured forward of tg_attn.hip (query folded through
 // Wk, softmax-weighted raw key rows projected once through Wv): every dX product re-uses the
 // forward GEMM kernel on the weight read k-major (no transposed copies), every dW product is
 // k_gemm_tn (both operands read along the batch dimension, deterministic split reduction),

@@ -25,6 +25,11 @@ its scores will read that the bitmap does not hold yet (`TIGER.restart_involved`
 `stream_step`; the number of restarted nodes is printed per batch beside the metrics.  What a serving process that has
 just loaded a checkpoint and a graph can do before it has seen the stream.
 
+--snapshot embeds the catalogue once per batch, at the batch's earliest event time, instead of once per (query, item) pair
+(`TIGE.embed_catalogue`, then `recommend` on the snapshot; `eval_recommendation(..., catalogue_at='batch')`): every item
+is scored as of the batch's start - an approximation of the exact per-pair protocol for the queries later in the batch -
+and the line printed says which protocol ran.
+
 Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
 import argparse
@@ -42,9 +47,10 @@ from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
 
 def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
         hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-        device='cuda:0'):
+        device='cuda:0', snapshot=False):
     """-> (ids [n_test, k], scores [n_test, k], the eval_recommendation dict).  The model settings must be those the
-    checkpoint was trained with (examples/link_prediction.py defaults here)."""
+    checkpoint was trained with (examples/link_prediction.py defaults here).  snapshot: one catalogue snapshot per batch
+    at the batch's earliest event time (catalogue_at='batch') instead of the exact per-pair protocol."""
     device = torch.device(device)
     torch.manual_seed(seed)
     basic, (train_graph, full_graph), dls = init_data(
@@ -66,7 +72,8 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
         for src, dst, neg, ts, eids, _, cg in test_dl:
             src, dst, neg, eids = (x.long().to(device) for x in (src, dst, neg, eids))
             cg.to(device)
-            i, s, _ = model.recommend(src, cg.ts64, catalogue, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
+            items = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else catalogue
+            i, s, _ = model.recommend(src, cg.ts64, items, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
             ids.append(i.cpu().numpy())
             scores.append(s.cpu().numpy())
             model.contrast_learning(src, dst, neg, ts.float().to(device), eids, cg)
@@ -74,7 +81,8 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     np.save(os.path.join(out_dir, 'ids.npy'), ids)
     np.save(os.path.join(out_dir, 'scores.npy'), scores)
     model.load_memory_state(start)  # the same pass once more, folded into the metrics
-    out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen)
+    out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen,
+                              catalogue_at='batch' if snapshot else None)
     return ids, scores, out
 
 
@@ -213,6 +221,8 @@ if __name__ == '__main__':
                     'starts at train + validation, beside the replay on the full graph')
     ap.add_argument('--cold', action='store_true', help='no replay: memories at reset, lazy restarts of what each batch reads '
                     '(recommend(..., uptodate=bitmap)); prints the restart count per batch')
+    ap.add_argument('--snapshot', action='store_true', help='embed the catalogue once per batch at the batch\'s earliest '
+                    'event time (eval_recommendation(..., catalogue_at=\'batch\')) instead of once per pair')
     ap.add_argument('--window', type=float, default=None, help='--online: after every observe, forget the entries older '
                     'than the batch\'s last time minus this many seconds (TIGE.forget)')
     ap.add_argument('--keep_last', type=int, default=None, help='--online: after every observe, keep every node\'s last M '
@@ -232,6 +242,8 @@ if __name__ == '__main__':
                   f"({m['n_events']} events)")
         sys.exit(0)
     ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
-                    restarter_type=a.restarter_type)
+                    restarter_type=a.restarter_type, snapshot=a.snapshot)
+    print('protocol: ' + ("one catalogue snapshot per batch at the batch's earliest event time (catalogue_at='batch')"
+                          if a.snapshot else 'exact - every (query, item) pair embedded at the query\'s time'))
     print(f"test: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "
           f"coverage {m['coverage']:.4f}  ({m['n_events']} events, {ids.shape[0]} lists written)")

@@ -1007,6 +1007,31 @@ int tg_rank_scores(int64_t B, int32_t C, int32_t d, int32_t K, const tg_score_pa
                    const float* h_cand, const int64_t* nbr_src, const int64_t* nbr_cand, const int64_t* src,
                    const int64_t* cand_ids, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* Catalogue snapshots: the same head over B x C pairs whose C items are shared by every source (no column 0).
+ * tg_rank_cand_half: P[j, n] = sum_k W1[n, W + k] h_cat[j, k], no bias (W = d, 'vec': d + K) - the candidate half of fc1,
+ * once per item.  It runs on v_mfma_f32_32x32x2_f32 with the accumulator from 0 and the operand columns in ascending
+ * order, two per instruction: the chain tg_rank_scores runs over the first d operand columns of a pair row, so P holds
+ * that accumulator's bits; a row's P does not depend on its position.  One launch.  C = 0: TG_OK, nothing launched.
+ * tg_rank_scores_shared: scores[i * ld + j] = the score of pair (src[i], cat_ids[j]) from h_src [B, d], P [C, d] and the hit
+ * features of tg_rank_scores with nbr_cand[i, j, :] replaced by nbr_cat[j, :]: src hits = (nbr_cat[j, :] == src[i]), dst
+ * hits = (nbr_src[i, :] == cat_ids[j]).  The bits are those of tg_rank_scores on the broadcast inputs (h_cand[i, j] =
+ * h_cat[j], ...): per hidden column v = a + S[i, n] with a = P[j, n] ('vec': the accumulator loaded with P[j, n] and
+ * continued through the 2K hit columns, dst hits then src hits), 'bin' / 'count' v += T_s[cs][n] + T_d[cd][n], then
+ * relu(v) * fc2.weight[n] summed in the order of tg_rank_scores's epilogue, + fc2.bias.  Work per pair: O(d) float32
+ * vector operations ('vec': + an O(K d) product); the candidate-half product is never repeated.  Launches: the class
+ * tables ('bin' / 'count'), the source half S (B rows), the pair pass - three, two without class tables; deterministic.
+ * 'none': the four id arrays may be NULL.  ws: tg_rank_scores_shared_workspace_bytes(B, d, sp) bytes; its contents on
+ * entry are not read.  Rows past the end are never stored; scores[i * ld + j] for j >= C is not touched.
+ * TG_EUNSUPPORTED (both entries): 'vec' with odd d (one two-column MFMA would be split between P and the hits) or with
+ * 2 (d + K) not a multiple of 4 (as tg_rank_scores).  TG_EINVAL before any launch: a negative size, B C >= 2^31, ld < C,
+ * a NULL pointer that the hit type needs, a workspace shorter than asked for.  B = 0 or C = 0: TG_OK, nothing launched. */
+int tg_rank_cand_half(int64_t C, int32_t d, int32_t K, const tg_score_params* sp, const float* h_cat, float* P,
+                      void* stream);
+size_t tg_rank_scores_shared_workspace_bytes(int64_t B, int32_t d, const tg_score_params* sp);
+int tg_rank_scores_shared(int64_t B, int64_t C, int32_t d, int32_t K, const tg_score_params* sp, const float* h_src,
+                          const float* P, const int64_t* nbr_src, const int64_t* nbr_cat, const int64_t* src,
+                          const int64_t* cat_ids, float* scores, int64_t ld, void* ws, size_t ws_bytes, void* stream);
+
 /* Rank of the true destination among the candidates LEFT IN: candidate j >= 1 of event i is left out when
  * cand_ids[i, j] == dst[i], when cand_ids[i, j] == 0 (the padding id) or when mask != NULL and mask[i, j - 1] == 0
  * (mask: uint8 [B, C]).  Per event (int32 [B] each, rank float64 [B]): n_greater / n_equal = candidates left in whose

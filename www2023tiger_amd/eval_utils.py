@@ -648,7 +648,8 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
 
 def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 10, exclude_seen: bool = False,
                         chunk_queries: int = 65536, restart_mode: bool = False, return_positions: bool = False,
-                        lazy_restarts: bool = False, uptodate_nodes: Optional[set] = None) -> dict:
+                        lazy_restarts: bool = False, uptodate_nodes: Optional[set] = None,
+                        catalogue_at: Optional[str] = None) -> dict:
     """Top-k recommendation quality over a loader (no counterpart in the reference's eval_utils): for every batch the k best
     items of the shared `catalogue` (int64 [C], no id twice) are listed for the batch's sources on the state BEFORE the
     batch (TIGE.recommend), then the batch runs as in `eval_edge_ranking` (contrast_learning), so the state advances
@@ -661,12 +662,22 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
     [B, k] torch ops accumulated on the device, one read-back at the end.
     lazy_restarts=True / uptodate_nodes: as in `eval_edge_ranking` - per batch ONE `TIGER.restart_involved` over
     cat[src, dst, neg] plus the catalogue at every event's time, before the batch is scored.
-    Refused: restart_mode=True (use lazy_restarts=True), and whatever TIGE.recommend refuses."""
+    catalogue_at: None is the exact protocol above - every (query, item) pair embedded at the query's own time.  'batch'
+    embeds the catalogue ONCE per batch, at the batch's earliest event time, on the state before the batch
+    (TIGE.embed_catalogue), and lists from that snapshot (TIGE.recommend on it: B + C embeddings and O(d) work per pair
+    instead of B (1 + C) embeddings).  It is an APPROXIMATION of the exact protocol: an item's embedding and neighbour
+    list are those of the batch's start for every query of the batch, so queries later in the batch see items slightly
+    in their past (never in their future).  With lazy_restarts the catalogue is restarted at that one time - C queries
+    beside cat[src, dst, neg], not B C.  Its effect on hit rate / NDCG on trained weights has not been measured.
+    Refused: restart_mode=True (use lazy_restarts=True), a catalogue_at other than None / 'batch', and whatever
+    TIGE.recommend refuses."""
     from . import hip_ops
     if restart_mode:
         raise NotImplementedError('eval_recommendation: restart_mode=True is not built (the lazy restarts of '
                                   "eval_edge_prediction cover the batch's own neighbourhoods, not the catalogue's); "
                                   'use lazy_restarts=True, which restarts both')
+    if catalogue_at not in (None, 'batch'):
+        raise ValueError(f"eval_recommendation: catalogue_at is None (exact) or 'batch', not {catalogue_at!r}")
     model._refuse_partitioned('eval_recommendation')
     if lazy_restarts and getattr(model, 'restarter_fn', None) is None:
         raise NotImplementedError('eval_recommendation: lazy_restarts needs a model with a restarter (TIGER)')
@@ -691,11 +702,20 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
             t = (ts if ts64 is None else ts64).to(device)
             g = graph if graph is not None else getattr(comp_graph, 'graph', None)
             g = model.graph if g is None else g
-            if lazy_restarts:
+            items = cat
+            if catalogue_at == 'batch' and len(src_ids) and C:
+                t0 = float(t.double().min())
+                if lazy_restarts:  # cat[src, dst, neg] at the event times, the catalogue at the batch's earliest time
+                    t64 = t.double().reshape(-1)
+                    model.restart_involved(torch.cat([src_ids, dst_ids, neg_dst_ids, cat]),
+                                           torch.cat([t64.repeat(3), torch.full((C,), t0, dtype=torch.float64, device=device)]),
+                                           bm, graph=g)
+                items = model.embed_catalogue(cat, t0, graph=g)
+            elif lazy_restarts:
                 _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, t, cat.unsqueeze(0).expand(len(src_ids), -1),
                                               bm, g)
             seen = hip_ops.seen_mask(g, src_ids, t, col_of, C) if exclude_seen else None
-            ids, _, _ = model.recommend(src_ids, t, cat, k, mask=seen, graph=g, chunk_queries=chunk_queries)
+            ids, _, _ = model.recommend(src_ids, t, items, k, mask=seen, graph=g, chunk_queries=chunk_queries)
             hit = (ids == dst_ids[:, None]) & (ids != 0)
             pos = torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1)   # the first listing (there is one at most)
             listed = pos >= 0

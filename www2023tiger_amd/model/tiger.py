@@ -20,6 +20,7 @@ from typing import Optional, Tuple, Union
 
 import numpy as np
 import os
+import weakref
 
 import torch
 from torch import Tensor, nn
@@ -45,6 +46,33 @@ class _QueryGraph:
 
     def __init__(self, layers, bitmap):
         self.layers, self.bitmap = layers, bitmap
+
+
+class CatalogueSnapshot:
+    """A shared catalogue embedded ONCE at one time t (TIGE.embed_catalogue), for TIGE.recommend in place of `cand`:
+    ids int64 [C], h float32 [C, d] (the items' embeddings at t), nb int64 [C, K] (their recent-edges neighbour ids at t,
+    None for hit_type 'none') and t.  It remembers what it is a function of - the model, its device, the graph's node
+    count and serial number, and the model's state / step / attention-parameter stamps at the time of embedding - so
+    that recommend can refuse a snapshot that no longer describes the model.  P float32 [C, d], the items' half of the
+    score head's first layer (tg_rank_cand_half), is computed on first use and again whenever the score head's
+    parameters have changed since.  A snapshot is read-only: nothing in it is updated by later calls."""
+
+    def __init__(self, model, ids: Tensor, h: Tensor, nb: Optional[Tensor], t: float, graph, stamp):
+        self._model = weakref.ref(model)
+        self.ids, self.h, self.nb, self.t = ids, h, nb, float(t)
+        self.device = ids.device
+        self.n_nodes = int(graph.num_node)
+        self.graph_serial = getattr(graph, 'serial', None)
+        self.stamp = stamp
+        self._P = None
+        self._P_stamp = None
+
+    @property
+    def model(self):
+        return self._model()
+
+    def __len__(self):
+        return int(self.ids.numel())
 
 
 class TIGE(nn.Module):
@@ -845,12 +873,55 @@ class TIGE(nn.Module):
         nodes = torch.cat([src_ids, ids_all.reshape(-1)])
         return self.restart_involved(nodes, torch.cat([ts64, ts64.repeat_interleave(ids_all.shape[1])]), uptodate, graph=graph)
 
+    def _embed_prepare(self):
+        """before a read-only embedding pass: pending invariant words are polled and pre-multiplied attention weights
+        follow the parameters, as before a streaming / evaluation step; the eager update and query-row tables are neither
+        read (the operator path consumes the mailbox itself) nor made stale (no state changes): they stay as they are"""
+        self._poll_train_errors()
+        if self._fused is not None and self._fused_stamp != self._attn_stamp():
+            self.fuse_attention()
+
+    def _embed_queries(self, nodes: Tensor, t64: Tensor, graph, strategy: str, err: Tensor):
+        """STEP 1-3 of the flat (node, time) queries on the current state, nothing written -> (h float32 [Q, d], nb int64
+        [Q, K] recent-edges neighbour ids, None for hit_type 'none').  The embedding unit of rank_scores, recommend and
+        embed_catalogue: exactly RANK_EMBED_ROWS queries per call (the last unit filled up with copies of its last query)
+        and one involved-set capacity - the products and the updater pick their kernel, K-split or not, by the row count,
+        and a K split sums in another order, so a query embedded among another number of rows could round differently.
+        Every query meets the same kernels whatever the list holds: its bits are a function of (node, time, state).
+        no_grad, after `_embed_prepare`; nodes int64 [Q] and t64 float64 [Q] on the model's device."""
+        from ..data.data_loader import GraphCollator
+        d, K, dev = self.memory_dim, self.n_neighbors, self.device
+        coll = GraphCollator(graph, K, self.n_layers)
+        hits = self.hit_type != 'none'
+        R = self.RANK_EMBED_ROWS
+        cap = min(R * (1 + K + (K * K if self.n_layers == 2 else 0)), self.n_nodes)
+        Q = nodes.numel()
+        h = torch.empty(Q, d, dtype=torch.float32, device=dev)
+        nb = torch.empty(Q, K, dtype=torch.int64, device=dev) if hits else None
+        for off in range(0, Q, R):
+            n = min(R, Q - off)
+            qn, qt = nodes[off:off + n], t64[off:off + n]
+            if n < R:
+                qn = torch.cat([qn, qn[-1:].expand(R - n)])
+                qt = torch.cat([qt, qt[-1:].expand(R - n)])
+            layers, bitmap, _ = coll.collate_memory_nodes(qn.contiguous(), qt.contiguous())
+            comp, reprs = self._consume(bitmap, cap, err)  # STEP 1-2, read-only
+            cg = _QueryGraph(layers, bitmap)
+            m = self.model_struct()
+            hq = self.temporal_embedding_fn.compute_embedding_with_computation_graph(  # STEP 3
+                reprs, qn, qt.float(), cg, m if self.n_layers == 1 else self.model_struct, comp['rank'])
+            h[off:off + n] = hq[:n]
+            if hits:  # hit windows are recent-edges lists whatever the graph's strategy (data_loader.py:61-75)
+                nbq = layers[-1][0] if strategy == 'recent_edges' else graph.sample_device(
+                    qn, qt, K, strategy='recent_edges', want_dirs=False)[0]
+                nb[off:off + n] = nbq[:n]
+        return h, nb
+
     def _pair_scores(self, what: str, src_ids: Tensor, ids_all: Tensor, ts: Tensor, graph, strategy: str,
                      chunk_queries: int) -> Tensor:
         """scores [B, C1] of the pairs (src_ids[i], ids_all[i, j]) at ts[i] on the current state, nothing written (the body
         of rank_scores, which passes [dst | cand]; recommend passes its candidates alone).  C1 >= 1; `_pair_refusals` has
         run; src_ids int64 [B] and ids_all int64 [B, C1] live on the model's device."""
-        from ..data.data_loader import GraphCollator
         from .training import score_struct
         d, K, dev = self.memory_dim, self.n_neighbors, self.device
         B = src_ids.numel()
@@ -864,50 +935,19 @@ class TIGE(nn.Module):
         if B == 0:
             return scores
         with torch.no_grad():
-            self._poll_train_errors()
-            # pre-multiplied attention weights follow the parameters, as before a streaming / evaluation step; the eager
-            # update and query-row tables are neither read (the operator path consumes the mailbox itself) nor made stale
-            # (no state changes): they are left exactly as they are
-            if self._fused is not None and self._fused_stamp != self._attn_stamp():
-                self.fuse_attention()
-            coll = GraphCollator(graph, K, self.n_layers)
+            self._embed_prepare()
             sp = score_struct(self)
             hits = self.hit_type != 'none'
             err = hip_ops.new_err(dev)
             s = stream_ptr(dev)
             step = max(1, int(chunk_queries) // (C1 + 1))
-            R = self.RANK_EMBED_ROWS
-            cap = min(R * (1 + K + (K * K if self.n_layers == 2 else 0)), self.n_nodes)
             for lo in range(0, B, step):
                 hi = min(B, lo + step)
                 b = hi - lo
                 ids = ids_all[lo:hi].contiguous()
                 nodes = torch.cat([src_ids[lo:hi], ids.reshape(-1)])
                 t64 = torch.cat([ts64[lo:hi], ts64[lo:hi].repeat_interleave(C1)])
-                # STEP 1-3 in units of exactly RANK_EMBED_ROWS queries (the last one filled up with copies of its last query)
-                # and one involved-set capacity: the products and the updater pick their kernel - K-split or not - by
-                # the row count, and a K split sums in another order, so a query embedded among another number of rows
-                # could round differently.  Every query now meets the same kernels whatever B, C and chunk_queries are
-                Q = nodes.numel()
-                h = torch.empty(Q, d, dtype=torch.float32, device=dev)
-                nb = torch.empty(Q, K, dtype=torch.int64, device=dev) if hits else None
-                for off in range(0, Q, R):
-                    n = min(R, Q - off)
-                    qn, qt = nodes[off:off + n], t64[off:off + n]
-                    if n < R:
-                        qn = torch.cat([qn, qn[-1:].expand(R - n)])
-                        qt = torch.cat([qt, qt[-1:].expand(R - n)])
-                    layers, bitmap, _ = coll.collate_memory_nodes(qn.contiguous(), qt.contiguous())
-                    comp, reprs = self._consume(bitmap, cap, err)  # STEP 1-2, read-only
-                    cg = _QueryGraph(layers, bitmap)
-                    m = self.model_struct()
-                    hq = self.temporal_embedding_fn.compute_embedding_with_computation_graph(  # STEP 3
-                        reprs, qn, qt.float(), cg, m if self.n_layers == 1 else self.model_struct, comp['rank'])
-                    h[off:off + n] = hq[:n]
-                    if hits:  # hit windows are recent-edges lists whatever the graph's strategy (data_loader.py:61-75)
-                        nbq = layers[-1][0] if strategy == 'recent_edges' else graph.sample_device(
-                            qn, qt, K, strategy='recent_edges', want_dirs=False)[0]
-                        nb[off:off + n] = nbq[:n]
+                h, nb = self._embed_queries(nodes, t64, graph, strategy, err)
                 nb_src = nb_cand = None
                 if hits:
                     nb_src, nb_cand = nb[:b], nb[b:]
@@ -920,9 +960,81 @@ class TIGE(nn.Module):
         return scores
 
     # ---- top-k recommendation ------------------------------------------------------------
-    def recommend(self, src_ids: Tensor, ts: Tensor, cand: Tensor, k: int, *, mask: Optional[Tensor] = None,
-                  exclude_seen: bool = False, graph=None, chunk_queries: int = 65536, col_of: Optional[Tensor] = None,
-                  uptodate: Optional[Tensor] = None):
+    def _snapshot_stamp(self):
+        """what a catalogue snapshot's rows are a function of, as far as the host can see it: the state (as for the eager-
+        update table), the number of steps run on this model, the attention / updater parameters"""
+        return (self._state_stamp(), getattr(self, '_step_serial', 0), tuple(self._attn_stamp()))
+
+    def _score_stamp(self):
+        w = self.score_fn.fc1.weight
+        return (w._version, w.data_ptr(), getattr(self, '_param_epoch', 0))
+
+    def _make_snapshot(self, cand: Tensor, t: float, graph, strategy: str) -> CatalogueSnapshot:
+        dev = self.device
+        with torch.no_grad():
+            self._embed_prepare()
+            err = hip_ops.new_err(dev)
+            t64 = torch.full((cand.numel(),), t, dtype=torch.float64, device=dev)
+            h, nb = self._embed_queries(cand, t64, graph, strategy, err)
+            hip_ops.raise_if_err(err)
+        return CatalogueSnapshot(self, cand, h, nb, t, graph, self._snapshot_stamp())
+
+    def embed_catalogue(self, cand: Tensor, t: float, *, graph=None, uptodate: Optional[Tensor] = None) -> CatalogueSnapshot:
+        """Embed a shared catalogue once, at ONE time t, on the model's CURRENT state -> CatalogueSnapshot (ids, h, nb, t;
+        see there).  cand: int64 [C]; duplicates and the padding id 0 are allowed as in recommend.  t: one float64 time.
+        The C queries (cand[j], t) run through the embedding unit of rank_scores / recommend (`_embed_queries`), so an
+        item's row holds the bits recommend's per-pair path computes for the query (cand[j], t).  NOTHING is written,
+        unless `uptodate` (a bitmap of hip_ops.new_bitmap; TIGER only) is given: then ONE `restart_involved` over the C
+        queries runs first, as in recommend's lazy form, and `last_restarted` holds its count.  Refused before anything
+        runs: whatever recommend refuses (strategy 'uniform', a partitioned model, training mode, unaligned 'vec' hits),
+        'vec' hits with an odd memory_dim (tg_rank_scores_shared), a NaN time, an id outside [0, n_nodes)."""
+        graph, strategy = self._pair_refusals('embed_catalogue', graph, 1, uptodate)
+        self._shared_refusals('embed_catalogue')
+        cand = torch.as_tensor(cand).to(self.device).long().contiguous()
+        if cand.dim() != 1:
+            raise ValueError(f'embed_catalogue: cand {tuple(cand.shape)}; a catalogue is int64 [C]')
+        t = float(t)
+        if t != t:
+            raise ValueError('embed_catalogue: t is NaN')
+        if cand.numel():
+            lo_id, hi_id = torch.aminmax(cand)
+            if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
+                raise ValueError('embed_catalogue: a node id outside [0, n_nodes)')
+        if uptodate is not None and cand.numel():
+            self.restart_involved(cand, torch.full((cand.numel(),), t, dtype=torch.float64, device=self.device), uptodate,
+                                  graph=graph)
+        return self._make_snapshot(cand, t, graph, strategy)
+
+    def _shared_refusals(self, what: str):
+        if self.hit_type == 'vec' and self.memory_dim % 2:
+            raise NotImplementedError(f"{what}: 'vec' hits on a catalogue snapshot need an even memory_dim")
+
+    def _check_snapshot(self, snap: CatalogueSnapshot, graph, stale_ok: bool):
+        if snap.model is not self:
+            raise ValueError('recommend: the catalogue snapshot was embedded by another model')
+        if snap.device != self.device:
+            raise ValueError(f'recommend: the catalogue snapshot lives on {snap.device}, the model on {self.device}')
+        if snap.n_nodes != self.n_nodes or snap.h.shape[1] != self.memory_dim:
+            raise ValueError(f'recommend: the catalogue snapshot covers {snap.n_nodes} node ids, the model {self.n_nodes}')
+        if not stale_ok and (snap.stamp != self._snapshot_stamp() or snap.graph_serial != getattr(graph, 'serial', None)):
+            raise RuntimeError('recommend: the catalogue snapshot is stale - the state, the parameters or the graph have '
+                               'changed since embed_catalogue (stream_step / observe / forget / a restart).  Embed it '
+                               'again, or pass stale_ok=True to score the items as of the snapshot')
+
+    def _snapshot_P(self, snap: CatalogueSnapshot, sp) -> Tensor:
+        """the items' half of fc1 (tg_rank_cand_half), computed once per state of the score head's parameters"""
+        stamp = self._score_stamp()
+        if snap._P is None or snap._P_stamp != stamp:
+            P = torch.empty_like(snap.h)
+            check(lib.tg_rank_cand_half(len(snap), self.memory_dim, self.n_neighbors, C.byref(sp), ptr(snap.h), ptr(P),
+                                        stream_ptr(self.device)), 'tg_rank_cand_half')
+            snap._P, snap._P_stamp = P, stamp
+        return snap._P
+
+    def recommend(self, src_ids: Tensor, ts: Tensor, cand: Union[Tensor, CatalogueSnapshot], k: int, *,
+                  mask: Optional[Tensor] = None, exclude_seen: bool = False, graph=None, chunk_queries: int = 65536,
+                  col_of: Optional[Tensor] = None, uptodate: Optional[Tensor] = None,
+                  catalogue_at: Optional[float] = None, stale_ok: bool = False):
         """The k best destinations of every (source, time) query among its candidates, on the model's CURRENT state,
         writing nothing -> (ids int64 [B, k], scores float32 [B, k], n_valid int32 [B]).  cand: int64 [B, C], or [C]
         shared by all queries (a catalogue).  A candidate is left out when it is the padding id 0, when mask[i, j] is false
@@ -938,9 +1050,36 @@ class TIGE(nn.Module):
         MEMORIES: before the first chunk is scored, ONE `restart_involved` over the B (1 + C) queries (sources, then every
         query's candidates at its time) restarts what the bitmap does not hold yet and marks it; `last_restarted` holds
         the count.  A process that has loaded a checkpoint and a graph can answer without replaying the stream: memories
-        at reset, an empty bitmap."""
+        at reset, an empty bitmap.
+        Catalogue snapshots.  cand may be a CatalogueSnapshot (embed_catalogue): the items were embedded once, at the
+        snapshot's time t, and are not embedded again.  Only the B sources are embedded, at their own ts[i]; the scores
+        come from tg_rank_scores_shared - the items' half of the score head once per item, O(d) work per pair - and mask,
+        exclude_seen, col_of, the chunking and the non-finite check work as above.  When every ts[i] equals t the lists
+        are those of the tensor form bit for bit; for ts[i] > t they are the serving approximation "items as of the
+        snapshot": an item's embedding and neighbour list are those of time t, never of a query's future.
+        catalogue_at=t with a tensor cand [C] is the one-shot form: a snapshot is built at t, used and dropped; with
+        `uptodate`, ONE `restart_involved` over the B + C queries [(src[i], ts[i]) ..., (cand[j], t) ...] runs before
+        anything is embedded.  stale_ok=True uses a snapshot although the state, the parameters or the graph have changed
+        since it was embedded: items as of the snapshot.  Refused before anything runs, with state and bitmap untouched:
+        ts[i] < t for some i (the snapshot would come from that query's future); a snapshot of another model, device or
+        graph size; a stale snapshot (RuntimeError) unless stale_ok; `uptodate` together with a ready snapshot (the
+        restart would make it stale); catalogue_at with per-query candidates [B, C] or with a snapshot; 'vec' hits with
+        an odd memory_dim."""
         graph, strategy = self._pair_refusals('recommend', graph, chunk_queries, uptodate)
         dev = self.device
+        snap = cand if isinstance(cand, CatalogueSnapshot) else None
+        if snap is not None:
+            if catalogue_at is not None:
+                raise ValueError('recommend: catalogue_at builds a snapshot from a tensor cand [C]; cand is a snapshot already')
+            if uptodate is not None:
+                raise ValueError('recommend: uptodate with a ready catalogue snapshot - the restart would make the snapshot '
+                                 'stale.  Either pass the catalogue as a tensor with catalogue_at=t (the one-shot form: one '
+                                 'restart over sources and items, then the snapshot), or run restart_involved on the '
+                                 'sources first and then embed_catalogue(..., uptodate=bitmap)')
+            self._check_snapshot(snap, graph, stale_ok)
+            cand = snap.ids
+        if snap is not None or catalogue_at is not None:
+            self._shared_refusals('recommend')
         src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
         cand = torch.as_tensor(cand).to(dev).long().contiguous()
         B, k = src_ids.numel(), int(k)
@@ -951,6 +1090,8 @@ class TIGE(nn.Module):
             raise ValueError(f'recommend: {B} queries, ts {tuple(ts.shape)}, cand {tuple(cand.shape)}')
         if exclude_seen and not shared:
             raise ValueError('recommend: exclude_seen needs a shared catalogue cand [C]')
+        if catalogue_at is not None and not shared:
+            raise ValueError('recommend: catalogue_at needs a shared catalogue cand [C], not per-query candidates [B, C]')
         Cc = cand.shape[-1]
         if mask is not None:
             mask = torch.as_tensor(mask).to(dev).bool()
@@ -963,19 +1104,56 @@ class TIGE(nn.Module):
         if exclude_seen and col_of is None:
             col_of = hip_ops.catalogue_index(cand, self.n_nodes)
         ts64 = ts.to(dev).double().contiguous().reshape(-1)
+        t_snap = snap.t if snap is not None else (None if catalogue_at is None else float(catalogue_at))
+        if t_snap is not None:
+            if t_snap != t_snap:
+                raise ValueError('recommend: catalogue_at is NaN')
+            if B and not bool((ts64 >= t_snap).all()):
+                raise ValueError(f'recommend: a query time before the catalogue snapshot\'s time {t_snap!r} - the snapshot '
+                                 "would come from that query's future")
         out_ids = torch.zeros(B, k, dtype=torch.int64, device=dev)
         out_scores = torch.full((B, k), float('-inf'), dtype=torch.float32, device=dev)
         n_valid = torch.zeros(B, dtype=torch.int32, device=dev)
         if B == 0 or Cc == 0:
             return out_ids, out_scores, n_valid
         if uptodate is not None:
-            self._restart_pairs(src_ids, cand.unsqueeze(0).expand(B, -1) if shared else cand, ts64, uptodate, graph)
+            if catalogue_at is not None:  # B + C queries, one call, before anything is embedded
+                self.restart_involved(torch.cat([src_ids, cand]),
+                                      torch.cat([ts64, torch.full((Cc,), t_snap, dtype=torch.float64, device=dev)]), uptodate,
+                                      graph=graph)
+            else:
+                self._restart_pairs(src_ids, cand.unsqueeze(0).expand(B, -1) if shared else cand, ts64, uptodate, graph)
+        if catalogue_at is not None:
+            snap = self._make_snapshot(cand, t_snap, graph, strategy)
         bad = torch.zeros(1, dtype=torch.int64, device=dev)
         step = max(1, int(chunk_queries) // (Cc + 1))
+        if snap is not None:
+            from .training import score_struct
+            d, K = self.memory_dim, self.n_neighbors
+            with torch.no_grad():
+                self._embed_prepare()
+                sp = score_struct(self)
+                P = self._snapshot_P(snap, sp)
+                # the B sources are embedded once for all chunks, at their own times (a query's bits do not depend on the
+                # list it is embedded in); only the [b, C] score block is chunked
+                err = hip_ops.new_err(dev)
+                h_all, nb_all = self._embed_queries(src_ids, ts64, graph, strategy, err)
+                hip_ops.raise_if_err(err)
         for lo in range(0, B, step):
             hi = min(B, lo + step)
             ids = cand.unsqueeze(0).expand(hi - lo, -1) if shared else cand[lo:hi]
-            scores = self._pair_scores('recommend', src_ids[lo:hi], ids, ts64[lo:hi], graph, strategy, chunk_queries)
+            if snap is None:
+                scores = self._pair_scores('recommend', src_ids[lo:hi], ids, ts64[lo:hi], graph, strategy, chunk_queries)
+            else:  # the items' rows are the snapshot's
+                with torch.no_grad():
+                    src_c = src_ids[lo:hi]
+                    h_src, nb_src = h_all[lo:hi], None if nb_all is None else nb_all[lo:hi]
+                    scores = torch.empty(hi - lo, Cc, dtype=torch.float32, device=dev)
+                    nbytes = int(lib.tg_rank_scores_shared_workspace_bytes(hi - lo, d, C.byref(sp)))
+                    ws = self._ws('rank', nbytes)
+                    check(lib.tg_rank_scores_shared(hi - lo, Cc, d, K, C.byref(sp), ptr(h_src), ptr(P), ptr(nb_src),
+                                                    ptr(snap.nb), ptr(src_c), ptr(snap.ids), ptr(scores), Cc, ptr(ws),
+                                                    ws.numel(), stream_ptr(dev)), 'tg_rank_scores_shared')
             mk = None
             if mask is not None:
                 mk = mask.unsqueeze(0).expand(hi - lo, -1) if mask.dim() == 1 else mask[lo:hi]

@@ -409,6 +409,34 @@ int tg_memory_scatter2(int64_t n, const int32_t* n_dev, const int64_t* ids, cons
 int tg_linear_fwd(int64_t n, const float* x, int32_t in_f, const tg_linear* lin, int32_t out_f, int32_t relu,
                   float* out, void* stream);
 
+/* Diagnostic: ONE product straight through the forward GEMM engine, with every operand / epilogue feature of a product
+ * spelled out (tests/test_hip_gemm_forms.py).  For each live row m < min(m_cap, *m_dev) and batch z < nbatch:
+ *   A[m] = [a0[a0_idx ? a0_idx[m] : m] | a1[a1_idx ? a1_idx[m] : m]]   (a0_w + a1_w = k; a0 advances by a0_bs per batch)
+ *   v = alpha * (A[m] . W[n] + bias[n] * (bias_rs ? bias_rs[m * ld_brs + z] : 1) + (bias2_valid[m] ? bias2[n] : 0))
+ *   W[n][kk] = w[n * ldw + kk], or w[kk * ldw + n] with w_kmajor (n a multiple of 4); w / bias advance by w_bs / bias_bs
+ *   then ReLU (relu), zero where row_valid[m] == 0, zero unless relu_mask[m * ld_mask + n] > 0, += the old value
+ *   (accumulate); stored at c[z * c_bs + (c_rows ? c_rows[m] : m) * ldc + n].  Nothing else is written.
+ * m_hint (0: none) is the caller's estimate of *m_dev and sizes launches only.  *form_out (nullable) receives a static
+ * string naming the kernel family and instance that ran ("direct<7,2x2>", "wstat<11,crows,idx>", ...; NULL when nothing
+ * was launched).  A product with bias2 is first offered to the K-split family directly, as the fused attention's
+ * fc1 - the one caller of that combination - does.  TG_EINVAL before anything touches the GPU: NULL p / a0 / w / c; k, a0_w, a1_w or ldw not a multiple of
+ * 4; bias2 without bias2_valid; nbatch < 1. */
+typedef struct tg_gemm_probe {
+  int64_t m_cap; const int32_t* m_dev; int64_t m_hint;
+  int32_t n, k;
+  const float* a0; int64_t a0_ld; int32_t a0_w; const int64_t* a0_idx;
+  const float* a1; int64_t a1_ld; int32_t a1_w; const int64_t* a1_idx;   /* a1 NULL: one segment */
+  const float* w; int64_t ldw; int32_t w_kmajor;
+  const float* bias; const float* bias2; const uint8_t* bias2_valid;
+  const float* bias_rs; int64_t ld_brs;
+  const uint8_t* row_valid; const float* relu_mask; int64_t ld_mask;
+  const int32_t* c_rows; int32_t accumulate;
+  float alpha; int32_t relu;
+  float* c; int64_t ldc;
+  int32_t nbatch; int64_t a0_bs, w_bs, bias_bs, c_bs;
+} tg_gemm_probe;
+int tg_debug_gemm(const tg_gemm_probe* p, const char** form_out, void* stream);
+
 /* Its backward (the operator path under autograd): dx [n, in_f] = dy W (NULL: not wanted), dw [out_f, in_f] = dy^T x and
  * db [out_f] = column sums of dy (NULL: not wanted; overwritten, not accumulated).  in_f and out_f multiples of 4. */
 size_t tg_linear_bwd_workspace_bytes(int32_t in_f, int32_t out_f);

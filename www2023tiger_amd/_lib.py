@@ -155,6 +155,21 @@ class TgAdamSeg(C.Structure):
     _fields_ = [('p', vp), ('g', vp), ('m', vp), ('v', vp), ('n', i64), ('group', i32), ('grad_scale', C.c_float)]
 
 
+class TgGemmProbe(C.Structure):
+    """tiger_hip.h: tg_gemm_probe - one product through the forward GEMM engine (tg_debug_gemm)"""
+    _fields_ = [
+        ('m_cap', i64), ('m_dev', vp), ('m_hint', i64), ('n', i32), ('k', i32),
+        ('a0', vp), ('a0_ld', i64), ('a0_w', i32), ('a0_idx', vp),
+        ('a1', vp), ('a1_ld', i64), ('a1_w', i32), ('a1_idx', vp),
+        ('w', vp), ('ldw', i64), ('w_kmajor', i32),
+        ('bias', vp), ('bias2', vp), ('bias2_valid', vp), ('bias_rs', vp), ('ld_brs', i64),
+        ('row_valid', vp), ('relu_mask', vp), ('ld_mask', i64),
+        ('c_rows', vp), ('accumulate', i32), ('alpha', C.c_float), ('relu', i32),
+        ('c', vp), ('ldc', i64),
+        ('nbatch', i32), ('a0_bs', i64), ('w_bs', i64), ('bias_bs', i64), ('c_bs', i64),
+    ]
+
+
 P = C.POINTER
 # name -> (restype, argtypes); every symbol include/tiger_hip.h declares
 SIGNATURES = {
@@ -198,6 +213,7 @@ SIGNATURES = {
     'tg_memory_scatter2': (C.c_int, [i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
     'tg_consume_update_right_rows': (C.c_int, [P(TgModel), vp, vp, i64, vp, vp, vp, vp]),
     'tg_linear_fwd': (C.c_int, [i64, vp, i32, P(TgLinear), i32, i32, vp, vp]),
+    'tg_debug_gemm': (C.c_int, [P(TgGemmProbe), P(C.c_char_p), vp]),
     'tg_linear_bwd_workspace_bytes': (sz, [i32, i32]),
     'tg_linear_bwd': (C.c_int, [i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     'tg_gru_fwd': (C.c_int, [i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),

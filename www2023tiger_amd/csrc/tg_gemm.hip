@@ -30,6 +30,11 @@ static bool phase_selected(const GemmArgs& g) {
   return sscanf(sel, "%d,%d", &n, &k) == 2 ? (g.n == n && g.k == k) : true;
 }
 
+// diagnostic (tg_debug_gemm): family and instance of the last product this thread launched - a string literal picked in
+// the branch that picks the kernel, nothing is formatted on the launch path
+static thread_local const char* t_gemm_form = nullptr;
+#define TG_FORM(lit_) (t_gemm_form = (lit_))
+
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16& acc, float bias, float bias2,
                                               int64_t m0, int64_t M, int n0, int wm, int wn, int fr, int fk, int bz);
 
@@ -1285,9 +1290,11 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
     // (rows per block: 16 when that fits the chip at once, else 32)
     const bool r1 = cdiv(g.m_cap, 16) * ntc <= 256;
     if (ct == 4) {
+      TG_FORM(r1 ? "ks16<1,4,4>" : "ks16<2,4,4>");
       if (r1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 4, 4>), dim3(256), dim3(256), 0, st, gd, nr);
       else TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 4, 4>), dim3(256), dim3(256), 0, st, gd, nr);
     } else {
+      TG_FORM(r1 ? "ks16<1,7,4>" : "ks16<2,7,4>");
       if (r1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 7, 4>), dim3(256), dim3(256), 0, st, gd, nr);
       else TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 7, 4>), dim3(256), dim3(256), 0, st, gd, nr);
     }
@@ -1308,11 +1315,13 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
       wr.blocks = rider_blocks(live, 256, 2 * wr.a.B);
       wr.last = 1u;
       const dim3 gr(256 + wr.blocks);
+      TG_FORM("ks16<3,3,4>+wb");
       TG_KLAUNCH((k_gemm_ks16<WbRider, 3, 3, 4>), gr, dim3(256), 0, st, gd, wr);
       *rode = true;
       return true;
     }
   }
+  TG_FORM(knob == 8 ? "ks16<3,3,8>" : rt == 1 ? "ks16<1,3,4>" : rt == 2 ? "ks16<2,3,4>" : "ks16<3,3,4>");
   if (knob == 8) TG_KLAUNCH((k_gemm_ks16<NoRider, 3, 3, 8>), dim3(256), dim3(512), 0, st, gd, nr);
   else if (rt == 1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr);
   else if (rt == 2) TG_KLAUNCH((k_gemm_ks16<NoRider, 2, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr);
@@ -1463,6 +1472,8 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       const int nsl = (int)cdiv(cdiv(g.k, 4), 4);
 #define TG_WSTAT(NS_)                                                                                   \
   do {                                                                                                  \
+    TG_FORM(g.c_rows && g.a0.idx ? "wstat<" #NS_ ",crows,idx>" : g.c_rows ? "wstat<" #NS_ ",crows>"     \
+            : g.a0.idx ? "wstat<" #NS_ ",idx>" : "wstat<" #NS_ ">");                                    \
     if (g.c_rows && g.a0.idx) TG_KLAUNCH((k_gemm_wstat<NS_, true, true>), gr, dim3(256), 0, st, gd);    \
     else if (g.c_rows) TG_KLAUNCH((k_gemm_wstat<NS_, true, false>), gr, dim3(256), 0, st, gd);          \
     else if (g.a0.idx) TG_KLAUNCH((k_gemm_wstat<NS_, false, true>), gr, dim3(256), 0, st, gd);          \
@@ -1478,6 +1489,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       no_ride();
       const int cpb = std::min(as8_knob, NT);
       const dim3 gr((unsigned)(8 * cdiv(cdiv(g.m_cap, 128), 8) * cdiv(NT, cpb)));
+      TG_FORM(nkt8 == 4 ? "astat8<4>" : nkt8 == 6 ? "astat8<6>" : "astat8<8>");
       if (nkt8 == 4) TG_KLAUNCH((k_gemm_astat8<4>), gr, dim3(512), 0, st, gd, cpb);
       else if (nkt8 == 6) TG_KLAUNCH((k_gemm_astat8<6>), gr, dim3(512), 0, st, gd, cpb);
       else TG_KLAUNCH((k_gemm_astat8<8>), gr, dim3(512), 0, st, gd, cpb);
@@ -1489,8 +1501,10 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
     // (128 x 128 blocks - four 32 x 32 accumulators per wavefront, twice the MFMAs between barriers - where N is a multiple
     // of 128 and K long: 196 608 x 1 280 -> 256 1 072 -> 1 041 us; K = 256: no difference)
     if ((rb_knob == 2 && g.n >= 512) || (rb_knob == 1 && g.n % 128 == 0 && g.k >= 512) || (rb_knob == 3 && g.n >= 128)) {
+      TG_FORM("rb<2,2>");
       TG_KLAUNCH((k_gemm_rb<2, 2>), dim3((unsigned)(8 * cdiv(cdiv(g.m_cap, 128), 8) * cdiv(g.n, 128))), dim3(256), 0, st, gd);
     } else {
+      TG_FORM("rb<2,1>");
       TG_KLAUNCH((k_gemm_rb<2, 1>), dim3((unsigned)(8 * cdiv(cdiv(g.m_cap, 128), 8) * NT)), dim3(256), 0, st, gd);
     }
     return check_launch("gemm(rb)");
@@ -1520,6 +1534,9 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       const dim3 gr(own + co.blocks + wr.blocks);
 #define TG_DIRECT(NS_)                                                                                                  \
   do {                                                                                                                  \
+    TG_FORM(wr.blocks ? (wide ? "direct<" #NS_ ",2x3>+wb" : "direct<" #NS_ ",2x2>+wb")                                  \
+            : co.blocks ? (wide ? "direct<" #NS_ ",2x3>+collate" : "direct<" #NS_ ",2x2>+collate")                      \
+            : (wide ? "direct<" #NS_ ",2x3>" : "direct<" #NS_ ",2x2>"));                                                \
     if (wr.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<WbRider, NS_, 2, 3>), gr, dim3(256), 0, st, gd, wr);      \
     else if (wr.blocks) TG_KLAUNCH((k_gemm_direct_r<WbRider, NS_, 2, 2>), gr, dim3(256), 0, st, gd, wr);        \
     else if (co.blocks && wide) TG_KLAUNCH((k_gemm_direct_r<CollateRider, NS_, 2, 3>), gr, dim3(256), 0, st, gd, co); \
@@ -1529,7 +1546,10 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
   } while (0)
       if (nsl <= 7) TG_DIRECT(7);
       else if (nsl <= 11) TG_DIRECT(11);
-      else TG_KLAUNCH((k_gemm_direct<12, 2, 2>), dim3(own), dim3(256), 0, st, gd);
+      else {
+        TG_FORM("direct<12,2x2>");
+        TG_KLAUNCH((k_gemm_direct<12, 2, 2>), dim3(own), dim3(256), 0, st, gd);
+      }
 #undef TG_DIRECT
       if ((collate || rider) && ride) *rode = true;
       return check_launch("gemm(direct)");
@@ -1551,6 +1571,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
         CollateRider co = *collate;
         collate_blocks(co);
         const dim3 grid_r((unsigned)(gb + co.blocks));
+        TG_FORM(nkt == 4 ? "astat<4>+collate" : nkt == 6 ? "astat<6>+collate" : "astat<8>+collate");
         if (nkt == 4) TG_KLAUNCH((k_gemm_astat_r<CollateRider, 4>), grid_r, dim3(256), 0, st, gd, cpb, co);
         else if (nkt == 6) TG_KLAUNCH((k_gemm_astat_r<CollateRider, 6>), grid_r, dim3(256), 0, st, gd, cpb, co);
         else TG_KLAUNCH((k_gemm_astat_r<CollateRider, 8>), grid_r, dim3(256), 0, st, gd, cpb, co);
@@ -1559,6 +1580,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       }
       no_ride();
       const dim3 grid_as((unsigned)gb);
+      TG_FORM(nkt == 4 ? "astat<4>" : nkt == 6 ? "astat<6>" : "astat<8>");
       if (nkt == 4) TG_KLAUNCH((k_gemm_astat<4>), grid_as, dim3(256), 0, st, gd, cpb);
       else if (nkt == 6) TG_KLAUNCH((k_gemm_astat<6>), grid_as, dim3(256), 0, st, gd, cpb);
       else TG_KLAUNCH((k_gemm_astat<8>), grid_as, dim3(256), 0, st, gd, cpb);
@@ -1574,6 +1596,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
     if (rider && (g.ask_pieces > 3 || ask_ks == 2)) {  // (stream-K consumers: the producer had fewer tiles than CUs)
       wr.blocks = rider_blocks(grid, 512, 2 * wr.a.B);
       wr.last = 1u;
+      TG_FORM("gemm<ask,ks2>+wb");
       if (g.ask_pieces > 3)
         TG_KLAUNCH((k_gemm_r<WbRider, 2, 2, 2, 2, true, 8>), dim3((unsigned)grid + wr.blocks), dim3(512), 0, st, gd, wr);
       else
@@ -1581,6 +1604,7 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
       *rode = true;
     } else {
       no_ride();
+      TG_FORM(g.ask_pieces > 3 || ask_ks == 2 ? "gemm<ask,ks2>" : ask_depth == 4 ? "gemm<ask,ks1,d4>" : "gemm<ask,ks1,d2>");
       if (g.ask_pieces > 3) TG_KLAUNCH((k_gemm<2, 2, 2, 2, true, 8>), dim3((unsigned)grid), dim3(512), 0, st, gd);
       else if (ask_ks == 2) TG_KLAUNCH((k_gemm<2, 2, 2, 2, true>), dim3((unsigned)grid), dim3(512), 0, st, gd);
       else if (ask_depth == 4) TG_KLAUNCH((k_gemm<2, 2, 1, 4, true>), dim3((unsigned)grid), dim3(256), 0, st, gd);
@@ -1588,26 +1612,65 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
     }
   } else if (split) {
     no_ride();
+    TG_FORM("gemm<ks2>");
     TG_KLAUNCH((k_gemm<2, 2, 2, 2>), dim3((unsigned)grid), dim3(512), 0, st, gd);
   } else if (depth_knob == 2 && rider && live_blocks(g, grid, 64) <= RIDER_MAX_LIVE) {
     WbRider wr = *rider;
     wr.blocks = rider_blocks(live_blocks(g, grid, 64), 256, 2 * wr.a.B);
     wr.last = 1u;
+    TG_FORM("gemm<ks1,d2>+wb");
     TG_KLAUNCH((k_gemm_r<WbRider, 2, 2, 1, 2>), dim3((unsigned)grid + wr.blocks), dim3(256), 0, st, gd, wr);
     *rode = true;
   } else if (depth_knob == 2 && collate && live_blocks(g, grid, 64) <= RIDER_MAX_LIVE) {
     CollateRider co = *collate;
     collate_blocks(co);
+    TG_FORM("gemm<ks1,d2>+collate");
     TG_KLAUNCH((k_gemm_r<CollateRider, 2, 2, 1, 2>), dim3((unsigned)grid + co.blocks), dim3(256), 0, st, gd, co);
     *rode = true;
   } else if (depth_knob == 2) {
     no_ride();
+    TG_FORM("gemm<ks1,d2>");
     TG_KLAUNCH((k_gemm<2, 2, 1, 2>), dim3((unsigned)grid), dim3(256), 0, st, gd);
   } else {
     no_ride();
+    TG_FORM("gemm<ks1,d4>");
     TG_KLAUNCH((k_gemm<2, 2, 1, 4>), dim3((unsigned)grid), dim3(256), 0, st, gd);
   }
   return check_launch("gemm");
 }
 
 }  // namespace tg
+
+// diagnostic: one product straight through gemm_launch (no riders, no second destination, no stream-K operand), and
+// which kernel it picked.  Every argument check runs before anything touches the GPU.
+extern "C" int tg_debug_gemm(const tg_gemm_probe* p, const char** form_out, void* stream) {
+  using namespace tg;
+  if (form_out) *form_out = nullptr;
+  if (!p || !p->a0 || !p->w || !p->c) return TG_EINVAL;
+  if (p->k <= 0 || p->n <= 0 || (p->k % 4) || (p->a0_w % 4) || (p->ldw % 4) || p->nbatch < 1) return TG_EINVAL;
+  if (p->a1 && (p->a1_w % 4)) return TG_EINVAL;
+  if (p->bias2 && !p->bias2_valid) return TG_EINVAL;
+  GemmArgs g{};
+  g.m_cap = p->m_cap; g.m_dev = p->m_dev; g.m_hint = p->m_hint;
+  g.n = p->n; g.k = p->k;
+  g.a0 = ASeg{p->a0, p->a0_ld, p->a0_w, p->a0_idx};
+  if (p->a1) g.a1 = ASeg{p->a1, p->a1_ld, p->a1_w, p->a1_idx};
+  g.w = p->w; g.ldw = p->ldw; g.w_kmajor = p->w_kmajor;
+  g.bias = p->bias; g.bias2 = p->bias2; g.bias2_valid = p->bias2_valid;
+  g.bias_rs = p->bias_rs; g.ld_brs = p->ld_brs;
+  g.row_valid = p->row_valid; g.relu_mask = p->relu_mask; g.ld_mask = p->ld_mask;
+  g.c_rows = p->c_rows; g.accumulate = p->accumulate;
+  g.alpha = p->alpha; g.relu = p->relu;
+  g.c = p->c; g.ldc = p->ldc;
+  g.nbatch = p->nbatch; g.a0_bs = p->a0_bs; g.w_bs = p->w_bs; g.bias_bs = p->bias_bs; g.c_bs = p->c_bs;
+  t_gemm_form = nullptr;
+  // gemm_launch never hands a product with a second bias to the K-split family; the fused attention's fc1 (tg_attn.hip), the
+  // one caller with such a product, offers it to gemm_ks16_launch itself first - and so does the probe
+  int rc;
+  if (g.bias2 && g.m_cap > 0 && g.a0.w + (g.a1.p ? g.a1.w : 0) == g.k && gemm_ks16_launch(g, as_stream(stream)))
+    rc = check_launch("gemm(ks16)");
+  else
+    rc = gemm_launch(g, as_stream(stream));
+  if (form_out) *form_out = t_gemm_form;
+  return rc;
+}

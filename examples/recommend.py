@@ -30,6 +30,12 @@ just loaded a checkpoint and a graph can do before it has seen the stream.
 is scored as of the batch's start - an approximation of the exact per-pair protocol for the queries later in the batch -
 and the line printed says which protocol ran.
 
+--walk C [--fanout 10,10,10] retrieves before it ranks: instead of all destination nodes, every event's candidates are the
+C best-connected ends of walks over the graph from its source at its own time (`TIGE.recommend_walk`: `hip_ops.
+walk_candidates`, levels 1 and 3 of a three-level walk by default, then `recommend` over those ids; with --exclude_seen the
+walk drops what the source has met).  Same outputs; the line printed adds recall@C, the share of events whose true
+destination was among the candidates at all (`eval_recommendation(walk=...)`'s coverage: it bounds the hit rate).
+
 Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
 import argparse
@@ -47,10 +53,16 @@ from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
 
 def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
         hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-        device='cuda:0', snapshot=False):
+        device='cuda:0', snapshot=False, walk=None, fanout=(10, 10, 10)):
     """-> (ids [n_test, k], scores [n_test, k], the eval_recommendation dict).  The model settings must be those the
     checkpoint was trained with (examples/link_prediction.py defaults here).  snapshot: one catalogue snapshot per batch
-    at the batch's earliest event time (catalogue_at='batch') instead of the exact per-pair protocol."""
+    at the batch's earliest event time (catalogue_at='batch') instead of the exact per-pair protocol.  walk=C: per-event
+    walk candidates (C per event over `fanout`, the last level and, with three levels, the first one taken) instead of
+    the catalogue of all destinations; the dict's coverage is then the generator's recall@C."""
+    if walk is not None and snapshot:
+        raise ValueError('--walk generates per-event candidates; a catalogue snapshot does not apply')
+    fanout = tuple(int(f) for f in fanout)
+    wk = dict(fanout=fanout, take=tuple(l == len(fanout) - 1 or (l == 0 and len(fanout) == 3) for l in range(len(fanout))))
     device = torch.device(device)
     torch.manual_seed(seed)
     basic, (train_graph, full_graph), dls = init_data(
@@ -72,8 +84,11 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
         for src, dst, neg, ts, eids, _, cg in test_dl:
             src, dst, neg, eids = (x.long().to(device) for x in (src, dst, neg, eids))
             cg.to(device)
-            items = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else catalogue
-            i, s, _ = model.recommend(src, cg.ts64, items, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
+            if walk is not None:
+                i, s, _, _ = model.recommend_walk(src, cg.ts64, k, C=walk, graph=full_graph, exclude_seen=exclude_seen, **wk)
+            else:
+                items = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else catalogue
+                i, s, _ = model.recommend(src, cg.ts64, items, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
             ids.append(i.cpu().numpy())
             scores.append(s.cpu().numpy())
             model.contrast_learning(src, dst, neg, ts.float().to(device), eids, cg)
@@ -81,8 +96,11 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     np.save(os.path.join(out_dir, 'ids.npy'), ids)
     np.save(os.path.join(out_dir, 'scores.npy'), scores)
     model.load_memory_state(start)  # the same pass once more, folded into the metrics
-    out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen,
-                              catalogue_at='batch' if snapshot else None)
+    if walk is not None:
+        out = eval_recommendation(model, test_dl, device, walk=dict(wk, C=walk), k=k, exclude_seen=exclude_seen)
+    else:
+        out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen,
+                                  catalogue_at='batch' if snapshot else None)
     return ids, scores, out
 
 
@@ -227,6 +245,9 @@ if __name__ == '__main__':
                     'than the batch\'s last time minus this many seconds (TIGE.forget)')
     ap.add_argument('--keep_last', type=int, default=None, help='--online: after every observe, keep every node\'s last M '
                     'entries (TIGE.forget)')
+    ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
+                    '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
+    ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
     a = ap.parse_args()
     if a.cold:
         m, restarted = run_cold(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, seed=a.seed, bs=a.bs,
@@ -242,8 +263,11 @@ if __name__ == '__main__':
                   f"({m['n_events']} events)")
         sys.exit(0)
     ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
-                    restarter_type=a.restarter_type, snapshot=a.snapshot)
-    print('protocol: ' + ("one catalogue snapshot per batch at the batch's earliest event time (catalogue_at='batch')"
+                    restarter_type=a.restarter_type, snapshot=a.snapshot, walk=a.walk, fanout=a.fanout.split(','))
+    print('protocol: ' + (f'{a.walk} walk candidates per event (fanout {a.fanout}), each pair embedded at the query\'s time'
+                          if a.walk is not None else
+                          "one catalogue snapshot per batch at the batch's earliest event time (catalogue_at='batch')"
                           if a.snapshot else 'exact - every (query, item) pair embedded at the query\'s time'))
+    cov = f"recall@{a.walk} {m['coverage']:.4f}" if a.walk is not None else f"coverage {m['coverage']:.4f}"
     print(f"test: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "
-          f"coverage {m['coverage']:.4f}  ({m['n_events']} events, {ids.shape[0]} lists written)")
+          f"{cov}  ({m['n_events']} events, {ids.shape[0]} lists written)")

@@ -1162,6 +1162,48 @@ int tg_involved_list_host(const tg_tcsr* g, int64_t Q, const int64_t* nids_host,
                           int32_t* count_host, float* tmin_host);
 
 /* ------------------------------------------------------------------------- */
+/* Walk candidates (no reference counterpart): per-query candidate generation */
+/* over the T-CSR - a source's own recent neighbours and the ends of its       */
+/* src -> nbr -> nbr -> nbr walks, counted, filtered, ordered and truncated    */
+/* ------------------------------------------------------------------------- */
+/* last(v, t, F) = the neighbour ids of the last F entries of node v whose time is < t: strict float64, the cut of every
+ * sampler; the recent-edges rule whatever the graph's strategy is; duplicates kept (multi-edges count); nothing for a
+ * node outside [0, num_node) or without entries before t.
+ * For query i, t = ts[i]: N1 = last(src[i], t, fanout[0]); N(l+1) = the concatenation of last(v, t, fanout[l]) over every
+ * element v of N(l), with multiplicity - every hop is cut at the ROOT's time, nothing comes from the query's future.
+ * w(v) = the sum over the levels l with bit l - 1 of `take` set of the multiplicity of v in N(l): the number of walks
+ * ending in v.  Candidates = {v : w(v) > 0} without node 0 (the padding id), without src[i] unless flags & 2 (keep_self),
+ * and - flags & 1 (exclude_seen) - without every node src[i] has ANY entry with before t (its whole prefix, not only its
+ * last fanout[0] entries), removed BEFORE ordering and truncation.  Order (total): higher w first, equal w by ascending
+ * id.  Outputs: ids int64 [B, C] and counts int32 [B, C], the first min(C, n) candidates and their w, padded with 0;
+ * n_valid int32 [B] = min(C, n); n_distinct int32 [B] = n, the number of candidates before truncation.  Nothing else is
+ * written; no model state is involved.  fanout: HOST array [n_levels].
+ * One 256-thread workgroup per query (capped grid), one launch, no workspace, no global atomics: the searches of a
+ * level run side by side, the ids are counted in an open-addressing table in LDS and selected by a sort in LDS -
+ * tg_walk_candidates_lds_bytes(n_levels, fanout, take) bytes of dynamic LDS (0 for a refused fan-out), at most 64 KiB.
+ * Integer work only: the result does not depend on the order in which the ids are counted.
+ * Caps: a fan-out in [1, TG_WALK_MAX_FANOUT]; the expanded frontiers fanout[0] and fanout[0] fanout[1] (two levels or
+ * three) at most TG_WALK_MAX_FRONTIER; the sizes of the TAKEN levels (fanout[0], fanout[0] fanout[1], fanout[0] fanout[1]
+ * fanout[2]) sum to at most TG_WALK_MAX_ENDPOINTS; 1 <= C <= TG_WALK_MAX_ENDPOINTS.
+ * TG_EINVAL before anything is launched: n_levels outside [1, 3]; take == 0, a bit of take at or above n_levels, or its
+ * highest set bit not n_levels - 1 (a level walked for nothing); a cap exceeded; flags outside [0, 3]; B < 0; a null
+ * pointer.  B == 0 is valid and touches nothing.  src[i] outside [0, num_node) gives an empty row in both entries; the
+ * Python wrapper refuses it where the ids are visible. */
+#define TG_WALK_MAX_FANOUT 64
+#define TG_WALK_MAX_FRONTIER 1024
+#define TG_WALK_MAX_ENDPOINTS 2048
+#define TG_WALK_EXCLUDE_SEEN 1
+#define TG_WALK_KEEP_SELF 2
+size_t tg_walk_candidates_lds_bytes(int32_t n_levels, const int32_t* fanout, int32_t take);
+int tg_walk_candidates(const tg_tcsr* g, int64_t B, const int64_t* src, const double* ts, int32_t n_levels,
+                       const int32_t* fanout, int32_t take, int32_t C, int32_t flags, int64_t* ids, int32_t* counts,
+                       int32_t* n_valid, int32_t* n_distinct, void* stream);
+/* The same on the host (g and every array HOST pointers; plain C++ over the T-CSR arrays); identical outputs. */
+int tg_walk_candidates_host(const tg_tcsr* g, int64_t B, const int64_t* src_host, const double* ts_host, int32_t n_levels,
+                            const int32_t* fanout, int32_t take, int32_t C, int32_t flags, int64_t* ids_host,
+                            int32_t* counts_host, int32_t* n_valid_host, int32_t* n_distinct_host);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */
 /* the global batch, the embeddings having been computed on other ranks)      */

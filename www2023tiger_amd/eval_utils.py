@@ -646,9 +646,9 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
     return out
 
 
-def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 10, exclude_seen: bool = False,
-                        chunk_queries: int = 65536, restart_mode: bool = False, return_positions: bool = False,
-                        lazy_restarts: bool = False, uptodate_nodes: Optional[set] = None,
+def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk: Optional[dict] = None, k: int = 10,
+                        exclude_seen: bool = False, chunk_queries: int = 65536, restart_mode: bool = False,
+                        return_positions: bool = False, lazy_restarts: bool = False, uptodate_nodes: Optional[set] = None,
                         catalogue_at: Optional[str] = None) -> dict:
     """Top-k recommendation quality over a loader (no counterpart in the reference's eval_utils): for every batch the k best
     items of the shared `catalogue` (int64 [C], no id twice) are listed for the batch's sources on the state BEFORE the
@@ -669,8 +669,14 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
     list are those of the batch's start for every query of the batch, so queries later in the batch see items slightly
     in their past (never in their future).  With lazy_restarts the catalogue is restarted at that one time - C queries
     beside cat[src, dst, neg], not B C.  Its effect on hit rate / NDCG on trained weights has not been measured.
-    Refused: restart_mode=True (use lazy_restarts=True), a catalogue_at other than None / 'batch', and whatever
-    TIGE.recommend refuses."""
+    walk (a dict of `hip_ops.walk_candidates` keywords plus `C`; instead of a catalogue): every event's candidates are
+    generated from the loader's graph at the event's own time - walk['C'] per event, [B, C] per batch - and ranked by
+    TIGE.recommend's per-query form.  exclude_seen=True is passed into the walk (recommend refuses it for per-query
+    candidates).  coverage is then the share of events whose true destination is in its candidate row: the generator's
+    recall@C, which depends on the graph alone, not on the weights.  lazy_restarts restarts cat[src, dst, neg] plus the
+    [B, C] candidate ids at the events' times.
+    Refused: restart_mode=True (use lazy_restarts=True), a catalogue_at other than None / 'batch', walk together with a
+    catalogue or with catalogue_at, neither a catalogue nor a walk, and whatever TIGE.recommend refuses."""
     from . import hip_ops
     if restart_mode:
         raise NotImplementedError('eval_recommendation: restart_mode=True is not built (the lazy restarts of '
@@ -678,6 +684,13 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
                                   'use lazy_restarts=True, which restarts both')
     if catalogue_at not in (None, 'batch'):
         raise ValueError(f"eval_recommendation: catalogue_at is None (exact) or 'batch', not {catalogue_at!r}")
+    if walk is not None and (catalogue is not None or catalogue_at is not None):
+        raise ValueError('eval_recommendation: walk generates per-event candidates; it takes neither a catalogue nor catalogue_at')
+    if walk is None and catalogue is None:
+        raise ValueError('eval_recommendation: give a shared catalogue, or walk=dict(C=..., ...) for per-event walk candidates')
+    if walk is not None:
+        return _eval_recommendation_walk(model, dl, device, dict(walk), k, exclude_seen, chunk_queries, return_positions,
+                                         lazy_restarts, uptodate_nodes)
     model._refuse_partitioned('eval_recommendation')
     if lazy_restarts and getattr(model, 'restarter_fn', None) is None:
         raise NotImplementedError('eval_recommendation: lazy_restarts needs a model with a restarter (TIGER)')
@@ -724,6 +737,62 @@ def eval_recommendation(model, dl, device: torch.device, catalogue, *, k: int = 
             covered = (col >= 0) & (dst_ids != 0)
             if seen is not None and C:
                 covered &= seen[torch.arange(len(src_ids), device=device), col.clamp(min=0)]
+            acc += torch.stack([listed.sum().double(), (listed / torch.log2(p64 + 2.0)).sum(), (listed / (p64 + 1.0)).sum(),
+                                covered.sum().double()])
+            if return_positions:
+                positions.append(pos)
+            model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
+            n += len(src_ids)
+    model._poll_train_errors()
+    if lazy_restarts:
+        _uptodate_set(model, bm, uptodate_nodes)
+    a = acc.cpu().tolist()
+    nan = float('nan')
+    out = dict(hit_rate=a[0] / n if n else nan, ndcg=a[1] / n if n else nan, mrr_at_k=a[2] / n if n else nan, n_events=n,
+               coverage=a[3] / n if n else nan)
+    if return_positions:
+        out['positions'] = torch.cat(positions) if positions else torch.zeros(0, dtype=torch.int64, device=device)
+    return out
+
+
+def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_seen: bool, chunk_queries: int,
+                              return_positions: bool, lazy_restarts: bool, uptodate_nodes: Optional[set]) -> dict:
+    """eval_recommendation(walk=...): the same loop and folds with per-batch walk candidates in place of the catalogue"""
+    from . import hip_ops
+    if 'C' not in walk:
+        raise ValueError("eval_recommendation: walk needs 'C', the candidates per event")
+    C = int(walk.pop('C'))
+    if 'exclude_seen' in walk:
+        raise ValueError('eval_recommendation: exclude_seen is the function\'s own keyword; it is passed into the walk')
+    hip_ops._walk_plan('eval_recommendation(walk)', C, walk.get('fanout', (10, 10, 10)), walk.get('take', (True, False, True)))
+    model._refuse_partitioned('eval_recommendation')
+    if lazy_restarts and getattr(model, 'restarter_fn', None) is None:
+        raise NotImplementedError('eval_recommendation: lazy_restarts needs a model with a restarter (TIGER)')
+    model.eval()
+    bm = _uptodate_bitmap(model, uptodate_nodes, device) if lazy_restarts else None
+    k = int(k)
+    graph = getattr(getattr(dl, 'collate_fn', None), 'graph', None)
+    acc = torch.zeros(4, dtype=torch.float64, device=device)  # hits, sum of gains, sum of reciprocal places, covered
+    place = torch.arange(k, dtype=torch.int64, device=device)
+    positions, n = [], 0
+    with torch.no_grad():
+        for src_ids, dst_ids, neg_dst_ids, ts, eids, _, comp_graph in BackgroundThreadGenerator(dl):
+            src_ids, dst_ids, neg_dst_ids = (x.long().to(device) for x in (src_ids, dst_ids, neg_dst_ids))
+            ts, eids = ts.float().to(device), eids.long().to(device)
+            comp_graph.to(device)
+            ts64 = getattr(comp_graph, 'ts64', None)
+            t = (ts if ts64 is None else ts64).to(device)
+            g = graph if graph is not None else getattr(comp_graph, 'graph', None)
+            g = model.graph if g is None else g
+            cand = hip_ops.walk_candidates(g, src_ids, t, C, exclude_seen=exclude_seen, **walk)['ids']
+            if lazy_restarts:
+                _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, t, cand, bm, g)
+            ids, _, _ = model.recommend(src_ids, t, cand, k, graph=g, chunk_queries=chunk_queries)
+            hit = (ids == dst_ids[:, None]) & (ids != 0)
+            pos = torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1)   # the first listing (there is one at most)
+            listed = pos >= 0
+            p64 = pos.clamp(min=0).double()
+            covered = ((cand == dst_ids[:, None]) & (cand != 0)).any(1)             # the generator's recall@C
             acc += torch.stack([listed.sum().double(), (listed / torch.log2(p64 + 2.0)).sum(), (listed / (p64 + 1.0)).sum(),
                                 covered.sum().double()])
             if return_positions:

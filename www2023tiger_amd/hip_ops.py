@@ -356,3 +356,74 @@ def involved_list(graph, nids: Tensor, ts: Tensor, n_neighbors: int, n_layers: i
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         check(lib.tg_involved_list(C_.byref(graph.tcsr), *args, ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_involved_list')
     return out
+
+
+# ---- walk candidates (tg_walk_candidates and its host twin) ----------------------------------------------------------------
+def _walk_plan(what: str, C: int, fanout, take) -> Tuple[Tensor, int]:
+    """the refusals of tg_walk_candidates that need no tensor, each with the cap it names -> (fanout int32 host, take bits)"""
+    fanout = tuple(int(f) for f in fanout)
+    take = tuple(bool(b) for b in take)
+    L = len(fanout)
+    if not 1 <= L <= 3:
+        raise ValueError(f'{what}: fanout has 1 to 3 levels, not {L}')
+    if len(take) != L:
+        raise ValueError(f'{what}: take {take} does not match the {L} levels of fanout {fanout}')
+    if not any(take):
+        raise ValueError(f'{what}: take selects no level')
+    if not take[-1]:
+        raise ValueError(f'{what}: the last level of fanout {fanout} is not taken - a level walked for nothing')
+    if any(not 1 <= f <= _lib.TG_WALK_MAX_FANOUT for f in fanout):
+        raise ValueError(f'{what}: every fan-out lies in [1, TG_WALK_MAX_FANOUT = {_lib.TG_WALK_MAX_FANOUT}], not {fanout}')
+    sizes = [fanout[0]]
+    for f in fanout[1:]:
+        sizes.append(sizes[-1] * f)
+    if max(sizes[:2]) > _lib.TG_WALK_MAX_FRONTIER:
+        raise ValueError(f'{what}: the expanded frontier of fanout {fanout} has {max(sizes[:2])} entries, above '
+                         f'TG_WALK_MAX_FRONTIER = {_lib.TG_WALK_MAX_FRONTIER}')
+    endpoints = sum(s for s, b in zip(sizes, take) if b)
+    if endpoints > _lib.TG_WALK_MAX_ENDPOINTS:
+        raise ValueError(f'{what}: the taken levels of fanout {fanout} hold {endpoints} endpoints, above '
+                         f'TG_WALK_MAX_ENDPOINTS = {_lib.TG_WALK_MAX_ENDPOINTS}')
+    if not 1 <= C <= _lib.TG_WALK_MAX_ENDPOINTS:
+        raise ValueError(f'{what}: 1 <= C <= TG_WALK_MAX_ENDPOINTS = {_lib.TG_WALK_MAX_ENDPOINTS}, not {C}')
+    return torch.tensor(fanout, dtype=torch.int32), sum(1 << l for l, b in enumerate(take) if b)
+
+
+def walk_candidates(graph, src: Tensor, ts: Tensor, C: int, *, fanout=(10, 10, 10), take=(True, False, True),
+                    exclude_seen: bool = False, keep_self: bool = False) -> dict:
+    """Per-query candidates from the graph itself (tiger_hip.h: tg_walk_candidates): the nodes reached from src[i] by walks
+    over each node's last fanout[l] entries before ts[i] - every hop cut at the query's own time, strict float64 -,
+    weighted by the number of walks that end in them at the levels `take` selects (one bool per level of fanout).  Left
+    out: node 0, the source itself unless keep_self, and with exclude_seen every node the source has any entry with
+    before ts[i].  Order: higher weight first, equal weights by ascending id; the first C.  -> dict(ids int64 [B, C] and
+    counts int32 [B, C], padded with 0; n_valid int32 [B] = min(C, n_distinct); n_distinct int32 [B], the candidates
+    before truncation).  The default walks src -> item -> co-user -> item and takes levels 1 and 3.  `ids` is the
+    per-query `cand` of TIGE.recommend.  Works on any Graph (the recent-edges rule whatever graph.strategy is).  Device
+    tensors take the device entry over graph.tcsr, host tensors the host twin over the graph's host arrays.  ValueError,
+    with the cap named, for what the C entry refuses; for a source outside [0, num_node); for tensors on a device other
+    than the graph's."""
+    import ctypes as C_
+    dev = src.device
+    src = _i64(src).reshape(-1)
+    B, C = src.numel(), int(C)
+    ts = ts.to(dev).double().contiguous().reshape(-1)
+    fan, bits = _walk_plan('walk_candidates', C, fanout, take)
+    if ts.numel() != B:
+        raise ValueError(f'walk_candidates: {B} sources, ts {tuple(ts.shape)}')
+    if B and (int(src.min()) < 0 or int(src.max()) >= graph.num_node):
+        raise ValueError('walk_candidates: a source id outside [0, num_node)')
+    flags = (_lib.TG_WALK_EXCLUDE_SEEN if exclude_seen else 0) | (_lib.TG_WALK_KEEP_SELF if keep_self else 0)
+    out = dict(ids=torch.zeros(B, C, dtype=torch.int64, device=dev), counts=torch.zeros(B, C, dtype=torch.int32, device=dev),
+               n_valid=torch.zeros(B, dtype=torch.int32, device=dev), n_distinct=torch.zeros(B, dtype=torch.int32, device=dev))
+    args = (B, ptr(src), ptr(ts), len(fan), ptr(fan), bits, C, flags, ptr(out['ids']), ptr(out['counts']), ptr(out['n_valid']),
+            ptr(out['n_distinct']))
+    if dev.type == 'cpu':
+        h = graph._host_tcsr()
+        tc = _lib.TgTcsr(graph.num_node, len(h[1]), *(ptr(a) for a in h))
+        check(lib.tg_walk_candidates_host(C_.byref(tc), *args), 'tg_walk_candidates_host')
+    else:
+        gd = graph.device
+        if gd.type != dev.type or (gd.index is not None and dev.index is not None and gd.index != dev.index):
+            raise ValueError(f'walk_candidates: the graph lives on {graph.device}, the queries on {dev}')
+        check(lib.tg_walk_candidates(C_.byref(graph.tcsr), *args, stream_ptr(dev)), 'tg_walk_candidates')
+    return out

@@ -1166,6 +1166,25 @@ class TIGE(nn.Module):
             raise ValueError(f'Input contains {n_bad} non-finite scores.')
         return out_ids, out_scores, n_valid
 
+    def recommend_walk(self, src_ids: Tensor, ts: Tensor, k: int, *, C: int = 256, graph=None,
+                       uptodate: Optional[Tensor] = None, chunk_queries: int = 65536, **walk):
+        """Retrieve, then rank: every query's candidates come from the graph itself - `hip_ops.walk_candidates` over the
+        graph `recommend` would use, at the query's own time, C per query (**walk: its fanout / take / exclude_seen /
+        keep_self) - and `recommend` lists the k best of them -> (ids int64 [B, k], scores float32 [B, k], n_valid int32
+        [B], cand: the dict of walk_candidates).  Exactly `recommend(src_ids, ts, cand['ids'], k, ...)`: the per-query form
+        drops the padding id 0, `uptodate` restarts what the B (1 + C) queries involve, and whatever `recommend` refuses
+        is refused here before the walk runs.  The walk's own exclude_seen is the seen-item filter of this form."""
+        graph, _ = self._pair_refusals('recommend_walk', graph, chunk_queries, uptodate)
+        if not 1 <= int(k) <= TG_TOPK_MAX_K:
+            raise ValueError(f'recommend_walk: 1 <= k <= {TG_TOPK_MAX_K}')
+        dev = self.device
+        src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
+        ts64 = ts.to(dev).double().contiguous().reshape(-1)
+        cand = hip_ops.walk_candidates(graph, src_ids, ts64, C, **walk)
+        ids, scores, n_valid = self.recommend(src_ids, ts64, cand['ids'], k, graph=graph, chunk_queries=chunk_queries,
+                                              uptodate=uptodate)
+        return ids, scores, n_valid, cand
+
     # ---- fused path ---------------------------------------------------------------------
     class StepBuffers:
         """Static device buffers of one batch size: inputs, outputs and the workspace of

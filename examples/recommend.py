@@ -35,6 +35,10 @@ C best-connected ends of walks over the graph from its source at its own time (`
 walk_candidates`, levels 1 and 3 of a three-level walk by default, then `recommend` over those ids; with --exclude_seen the
 walk drops what the source has met).  Same outputs; the line printed adds recall@C, the share of events whose true
 destination was among the candidates at all (`eval_recommendation(walk=...)`'s coverage: it bounds the hit rate).
+--walk C --snapshot does both: the catalogue is embedded once per batch and every event's walk candidates are ranked on
+the snapshot's rows (`TIGE.recommend_walk(..., snapshot=snap)`: only the sources are embedded; a candidate that is not a
+destination node of the dataset is left out; `eval_recommendation(walk=dict(C=..., catalogue=...))`).  The line printed
+adds in_catalogue, the share of generated candidates that the catalogue lists.
 
 Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
@@ -58,9 +62,8 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     checkpoint was trained with (examples/link_prediction.py defaults here).  snapshot: one catalogue snapshot per batch
     at the batch's earliest event time (catalogue_at='batch') instead of the exact per-pair protocol.  walk=C: per-event
     walk candidates (C per event over `fanout`, the last level and, with three levels, the first one taken) instead of
-    the catalogue of all destinations; the dict's coverage is then the generator's recall@C."""
-    if walk is not None and snapshot:
-        raise ValueError('--walk generates per-event candidates; a catalogue snapshot does not apply')
+    the catalogue of all destinations; the dict's coverage is then the generator's recall@C.  walk with snapshot: the
+    walk's candidates ranked on the per-batch snapshot of all destinations; the dict gains in_catalogue."""
     fanout = tuple(int(f) for f in fanout)
     wk = dict(fanout=fanout, take=tuple(l == len(fanout) - 1 or (l == 0 and len(fanout) == 3) for l in range(len(fanout))))
     device = torch.device(device)
@@ -85,7 +88,9 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
             src, dst, neg, eids = (x.long().to(device) for x in (src, dst, neg, eids))
             cg.to(device)
             if walk is not None:
-                i, s, _, _ = model.recommend_walk(src, cg.ts64, k, C=walk, graph=full_graph, exclude_seen=exclude_seen, **wk)
+                snap = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else None
+                i, s, _, _ = model.recommend_walk(src, cg.ts64, k, C=walk, graph=full_graph, exclude_seen=exclude_seen,
+                                                  snapshot=snap, **wk)
             else:
                 items = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else catalogue
                 i, s, _ = model.recommend(src, cg.ts64, items, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
@@ -97,7 +102,8 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     np.save(os.path.join(out_dir, 'scores.npy'), scores)
     model.load_memory_state(start)  # the same pass once more, folded into the metrics
     if walk is not None:
-        out = eval_recommendation(model, test_dl, device, walk=dict(wk, C=walk), k=k, exclude_seen=exclude_seen)
+        out = eval_recommendation(model, test_dl, device, walk=dict(wk, C=walk, **(dict(catalogue=catalogue) if snapshot else {})),
+                                  k=k, exclude_seen=exclude_seen)
     else:
         out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen,
                                   catalogue_at='batch' if snapshot else None)
@@ -264,10 +270,15 @@ if __name__ == '__main__':
         sys.exit(0)
     ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
                     restarter_type=a.restarter_type, snapshot=a.snapshot, walk=a.walk, fanout=a.fanout.split(','))
-    print('protocol: ' + (f'{a.walk} walk candidates per event (fanout {a.fanout}), each pair embedded at the query\'s time'
+    print('protocol: ' + (f'{a.walk} walk candidates per event (fanout {a.fanout}), ranked on one catalogue snapshot per batch '
+                          "at the batch's earliest event time"
+                          if a.walk is not None and a.snapshot else
+                          f'{a.walk} walk candidates per event (fanout {a.fanout}), each pair embedded at the query\'s time'
                           if a.walk is not None else
                           "one catalogue snapshot per batch at the batch's earliest event time (catalogue_at='batch')"
                           if a.snapshot else 'exact - every (query, item) pair embedded at the query\'s time'))
     cov = f"recall@{a.walk} {m['coverage']:.4f}" if a.walk is not None else f"coverage {m['coverage']:.4f}"
+    if 'in_catalogue' in m:
+        cov += f"  in_catalogue {m['in_catalogue']:.4f}"
     print(f"test: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "
           f"{cov}  ({m['n_events']} events, {ids.shape[0]} lists written)")

@@ -1060,6 +1060,28 @@ int tg_rank_scores_shared(int64_t B, int64_t C, int32_t d, int32_t K, const tg_s
                           const float* P, const int64_t* nbr_src, const int64_t* nbr_cat, const int64_t* src,
                           const int64_t* cat_ids, float* scores, int64_t ld, void* ws, size_t ws_bytes, void* stream);
 
+/* Retrieve, then rank on a snapshot: every source scores a PER-QUERY subset of the snapshot's rows.  col int32 [B, Cq]:
+ * col[i, q] = j in [0, C) is the row of h_cat / P / nbr_cat / cat_ids that pair (i, q) takes; a negative value means "not
+ * in the catalogue".  tg_rank_scores_gathered: for col[i, q] = j >= 0, scores[i * ld + q] holds exactly the bits
+ * tg_rank_scores_shared writes at [i, j] for the same h_src, P, nbr_* and ids (so tg_rank_scores's on the broadcast inputs:
+ * the order contract above is inherited - S, T_s and T_d come from the same loops, the hidden columns are summed in the same
+ * order); for col[i, q] < 0 it holds 0.0f, defined so that whole arrays compare - the caller masks it out.  Columns q >= Cq
+ * of a row are not touched; a row may name an item more than once.  A col value >= C is the caller's error and is NOT
+ * checked.  Work per pair: one gathered P row (4 d bytes, coalesced) and the O(d) float32 vector operations of
+ * tg_rank_scores_shared ('vec': + the O(K d) product over the hit columns); nothing is embedded or multiplied per item.
+ * Launches: the class tables ('bin' / 'count'), the source half S (B rows), the pair pass - three, two without class
+ * tables; deterministic, no atomics.  'none': the four id arrays may be NULL.  ws:
+ * tg_rank_scores_gathered_workspace_bytes(B, d, sp) bytes (= tg_rank_scores_shared_workspace_bytes); its contents on entry
+ * are not read.  TG_EUNSUPPORTED: as tg_rank_scores_shared ('vec' with odd d or with 2 (d + K) not a multiple of 4).
+ * TG_EINVAL before any launch: a negative size, C >= 2^31 - 1, B Cq >= 2^31, ld < Cq, col == NULL, a NULL pointer that the
+ * hit type needs, a workspace shorter than asked for.  B = 0 or Cq = 0: TG_OK, nothing launched.  C = 0 with Cq > 0: every
+ * col must be negative; the scores are all 0.0f (one fill launch; h_src, P and ws are not read). */
+size_t tg_rank_scores_gathered_workspace_bytes(int64_t B, int32_t d, const tg_score_params* sp);
+int tg_rank_scores_gathered(int64_t B, int64_t C, int64_t Cq, int32_t d, int32_t K, const tg_score_params* sp,
+                            const float* h_src, const float* P, const int64_t* nbr_src, const int64_t* nbr_cat,
+                            const int64_t* src, const int64_t* cat_ids, const int32_t* col /* [B, Cq] */,
+                            float* scores /* [B, ld], ld >= Cq */, int64_t ld, void* ws, size_t ws_bytes, void* stream);
+
 /* Rank of the true destination among the candidates LEFT IN: candidate j >= 1 of event i is left out when
  * cand_ids[i, j] == dst[i], when cand_ids[i, j] == 0 (the padding id) or when mask != NULL and mask[i, j - 1] == 0
  * (mask: uint8 [B, C]).  Per event (int32 [B] each, rank float64 [B]): n_greater / n_equal = candidates left in whose

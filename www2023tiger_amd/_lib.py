@@ -289,6 +289,9 @@ SIGNATURES = {
     'tg_rank_cand_half': (C.c_int, [i64, i32, i32, P(TgScoreParams), vp, vp, vp]),
     'tg_rank_scores_shared_workspace_bytes': (sz, [i64, i32, P(TgScoreParams)]),
     'tg_rank_scores_shared': (C.c_int, [i64, i64, i32, i32, P(TgScoreParams), vp, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+    'tg_rank_scores_gathered_workspace_bytes': (sz, [i64, i32, P(TgScoreParams)]),
+    'tg_rank_scores_gathered': (C.c_int, [i64, i64, i64, i32, i32, P(TgScoreParams), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, sz,
+                                          vp]),
     'tg_rank_stats': (C.c_int, [i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'tg_rank_stats_host': (C.c_int, [i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     'tg_topk_rows_workspace_bytes': (sz, [i64, i64, i32, i32]),

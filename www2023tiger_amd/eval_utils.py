@@ -675,6 +675,14 @@ def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk
     candidates).  coverage is then the share of events whose true destination is in its candidate row: the generator's
     recall@C, which depends on the graph alone, not on the weights.  lazy_restarts restarts cat[src, dst, neg] plus the
     [B, C] candidate ids at the events' times.
+    walk with a 'catalogue' key (int64 [C], no id twice): retrieve, then rank on a snapshot - per batch ONE snapshot of that
+    catalogue at the batch's earliest event time on the state before the batch (the catalogue_at='batch' rule), the walk
+    at every event's own time, and the walk's ids ranked on the snapshot's rows (TIGE.recommend_subset(..., snap, ids):
+    B + C embeddings and one gathered pair score per candidate; a candidate outside the catalogue is left out).
+    coverage is still the generator's recall@C; `in_catalogue` is added, the share of generated candidates that the
+    catalogue lists.  lazy_restarts restarts cat[src, dst, neg] at the events' times plus the catalogue at the batch's
+    earliest time, in one call.  An APPROXIMATION in the same sense as catalogue_at='batch' (items as of the batch's
+    start); its effect on hit rate / NDCG on trained weights has not been measured.
     Refused: restart_mode=True (use lazy_restarts=True), a catalogue_at other than None / 'batch', walk together with a
     catalogue or with catalogue_at, neither a catalogue nor a walk, and whatever TIGE.recommend refuses."""
     from . import hip_ops
@@ -762,6 +770,7 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
     if 'C' not in walk:
         raise ValueError("eval_recommendation: walk needs 'C', the candidates per event")
     C = int(walk.pop('C'))
+    cat = walk.pop('catalogue', None)
     if 'exclude_seen' in walk:
         raise ValueError('eval_recommendation: exclude_seen is the function\'s own keyword; it is passed into the walk')
     hip_ops._walk_plan('eval_recommendation(walk)', C, walk.get('fanout', (10, 10, 10)), walk.get('take', (True, False, True)))
@@ -771,8 +780,14 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
     model.eval()
     bm = _uptodate_bitmap(model, uptodate_nodes, device) if lazy_restarts else None
     k = int(k)
+    if cat is not None:
+        cat = torch.as_tensor(cat).long().to(device)
+        if cat.dim() != 1 or cat.numel() == 0:
+            raise ValueError("eval_recommendation: walk['catalogue'] is int64 [C], C >= 1, shared by all events")
+        hip_ops.catalogue_index(cat, model.n_nodes)  # no id twice, every id a node: refused before the first batch
     graph = getattr(getattr(dl, 'collate_fn', None), 'graph', None)
     acc = torch.zeros(4, dtype=torch.float64, device=device)  # hits, sum of gains, sum of reciprocal places, covered
+    gen = torch.zeros(2, dtype=torch.float64, device=device)  # candidates generated, of them in the catalogue
     place = torch.arange(k, dtype=torch.int64, device=device)
     positions, n = [], 0
     with torch.no_grad():
@@ -785,9 +800,21 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
             g = graph if graph is not None else getattr(comp_graph, 'graph', None)
             g = model.graph if g is None else g
             cand = hip_ops.walk_candidates(g, src_ids, t, C, exclude_seen=exclude_seen, **walk)['ids']
-            if lazy_restarts:
-                _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, t, cand, bm, g)
-            ids, _, _ = model.recommend(src_ids, t, cand, k, graph=g, chunk_queries=chunk_queries)
+            if cat is not None and len(src_ids):
+                t0 = float(t.double().min())
+                if lazy_restarts:  # cat[src, dst, neg] at the event times, the catalogue at the batch's earliest time
+                    t64 = t.double().reshape(-1)
+                    model.restart_involved(torch.cat([src_ids, dst_ids, neg_dst_ids, cat]),
+                                           torch.cat([t64.repeat(3), torch.full((cat.numel(),), t0, dtype=torch.float64,
+                                                                                device=device)]), bm, graph=g)
+                snap = model.embed_catalogue(cat, t0, graph=g)
+                ids, _, _ = model.recommend_subset(src_ids, t, snap, k, cand, graph=g, chunk_queries=chunk_queries)
+                real = cand != 0
+                gen += torch.stack([real.sum().double(), (real & (snap.col_of[cand] >= 0)).sum().double()])
+            else:
+                if lazy_restarts:
+                    _restart_batch_and_candidates(model, src_ids, dst_ids, neg_dst_ids, t, cand, bm, g)
+                ids, _, _ = model.recommend(src_ids, t, cand, k, graph=g, chunk_queries=chunk_queries)
             hit = (ids == dst_ids[:, None]) & (ids != 0)
             pos = torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1)   # the first listing (there is one at most)
             listed = pos >= 0
@@ -806,6 +833,9 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
     nan = float('nan')
     out = dict(hit_rate=a[0] / n if n else nan, ndcg=a[1] / n if n else nan, mrr_at_k=a[2] / n if n else nan, n_events=n,
                coverage=a[3] / n if n else nan)
+    if cat is not None:
+        n_gen, n_in = gen.cpu().tolist()
+        out['in_catalogue'] = n_in / n_gen if n_gen else nan
     if return_positions:
         out['positions'] = torch.cat(positions) if positions else torch.zeros(0, dtype=torch.int64, device=device)
     return out

@@ -55,7 +55,10 @@ class CatalogueSnapshot:
     count and serial number, and the model's state / step / attention-parameter stamps at the time of embedding - so
     that recommend can refuse a snapshot that no longer describes the model.  P float32 [C, d], the items' half of the
     score head's first layer (tg_rank_cand_half), is computed on first use and again whenever the score head's
-    parameters have changed since.  A snapshot is read-only: nothing in it is updated by later calls."""
+    parameters have changed since.  col_of int32 [n_nodes], the row of every node id in the snapshot and -1 for a node
+    that is not in it (`hip_ops.catalogue_index(ids, n_nodes)`), is built on first use - recommend_subset gathers
+    through it - and raises ValueError for a snapshot that lists an id twice.  A snapshot is read-only: nothing in it is
+    updated by later calls."""
 
     def __init__(self, model, ids: Tensor, h: Tensor, nb: Optional[Tensor], t: float, graph, stamp):
         self._model = weakref.ref(model)
@@ -66,10 +69,17 @@ class CatalogueSnapshot:
         self.stamp = stamp
         self._P = None
         self._P_stamp = None
+        self._col_of = None
 
     @property
     def model(self):
         return self._model()
+
+    @property
+    def col_of(self) -> Tensor:
+        if self._col_of is None:
+            self._col_of = hip_ops.catalogue_index(self.ids, self.n_nodes)
+        return self._col_of
 
     def __len__(self):
         return int(self.ids.numel())
@@ -1064,7 +1074,36 @@ class TIGE(nn.Module):
         ts[i] < t for some i (the snapshot would come from that query's future); a snapshot of another model, device or
         graph size; a stale snapshot (RuntimeError) unless stale_ok; `uptodate` together with a ready snapshot (the
         restart would make it stale); catalogue_at with per-query candidates [B, C] or with a snapshot; 'vec' hits with
-        an odd memory_dim."""
+        an odd memory_dim.
+        `recommend_subset` ranks per-query candidates on a snapshot's rows."""
+        return self._recommend(src_ids, ts, cand, k, mask, exclude_seen, graph, chunk_queries, col_of, uptodate, catalogue_at,
+                               stale_ok, None)
+
+    def recommend_subset(self, src_ids: Tensor, ts: Tensor, cand: Union[Tensor, CatalogueSnapshot], k: int, subset: Tensor, *,
+                         mask: Optional[Tensor] = None, graph=None, chunk_queries: int = 65536,
+                         uptodate: Optional[Tensor] = None, catalogue_at: Optional[float] = None, stale_ok: bool = False):
+        """Retrieve, then rank on a catalogue snapshot: `recommend` with every query ranking its OWN candidates `subset`
+        (int64 [B, Cq] node ids, e.g. the ids of `hip_ops.walk_candidates`) on the snapshot's rows -> the 3-tuple of
+        recommend.  cand: a CatalogueSnapshot, or a tensor catalogue [C] with catalogue_at=t (the one-shot form; with
+        `uptodate` ONE `restart_involved` over the B + C queries, as in recommend).  col = snapshot.col_of[subset] names
+        each candidate's row; a candidate is left out when it is not in the catalogue (col < 0), when it is the padding
+        id 0 or when mask[i, q] is false (mask: bool [B, Cq]).  Only the B sources are embedded; the scores come from
+        tg_rank_scores_gathered - one gathered row of P and O(d) work per pair, the bits of tg_rank_scores_shared at
+        [i, col] - in chunks of chunk_queries // (Cq + 1) queries, and the returned ids are subset's.  With every
+        ts[i] == t and every id in the catalogue the lists are those of recommend(src, ts, subset, k) bit for bit.
+        There is no exclude_seen: that filter works on catalogue columns and would rebuild [B, C]; filter where the subset
+        is generated (walk_candidates(exclude_seen=True)), as for per-query candidates.  Refused before anything runs,
+        with state and bitmap untouched: a cand that is neither a snapshot nor a catalogue with catalogue_at, a subset of
+        another shape than [B, Cq], an id outside [0, n_nodes), a catalogue that lists an id twice (its rows cannot be
+        named by id), and everything recommend on a snapshot refuses."""
+        if subset is None:
+            raise ValueError('recommend_subset: subset is int64 [B, Cq]; without one, call recommend')
+        return self._recommend(src_ids, ts, cand, k, mask, False, graph, chunk_queries, None, uptodate, catalogue_at, stale_ok,
+                               subset)
+
+    def _recommend(self, src_ids, ts, cand, k, mask, exclude_seen, graph, chunk_queries, col_of, uptodate, catalogue_at,
+                   stale_ok, subset):
+        """the body of recommend (subset None) and recommend_subset"""
         graph, strategy = self._pair_refusals('recommend', graph, chunk_queries, uptodate)
         dev = self.device
         snap = cand if isinstance(cand, CatalogueSnapshot) else None
@@ -1093,14 +1132,35 @@ class TIGE(nn.Module):
         if catalogue_at is not None and not shared:
             raise ValueError('recommend: catalogue_at needs a shared catalogue cand [C], not per-query candidates [B, C]')
         Cc = cand.shape[-1]
+        if subset is not None:
+            if snap is None and catalogue_at is None:
+                raise ValueError('recommend: subset ranks per-query candidates on the rows of a catalogue snapshot; give a '
+                                 'snapshot, or a catalogue cand [C] with catalogue_at=t')
+            subset = torch.as_tensor(subset).to(dev).long().contiguous()
+            if subset.dim() != 2 or subset.shape[0] != B:
+                raise ValueError(f'recommend: subset {tuple(subset.shape)} for {B} queries; per-query candidates are int64 [B, Cq]')
+            if subset.numel():
+                lo_id, hi_id = torch.aminmax(subset)
+                if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
+                    raise ValueError('recommend: a node id outside [0, n_nodes) in subset')
+        Cq = Cc if subset is None else subset.shape[1]  # score columns per query
         if mask is not None:
             mask = torch.as_tensor(mask).to(dev).bool()
-            if mask.shape != ((Cc,) if mask.dim() == 1 and shared else (B, Cc)):
+            if subset is not None:
+                if mask.shape != (B, Cq):
+                    raise ValueError(f'recommend: mask {tuple(mask.shape)} for subset {tuple(subset.shape)}')
+            elif mask.shape != ((Cc,) if mask.dim() == 1 and shared else (B, Cc)):
                 raise ValueError(f'recommend: mask {tuple(mask.shape)} for cand {tuple(cand.shape)} of {B} queries')
         if B and Cc:
             lo_id, hi_id = torch.aminmax(torch.cat([src_ids, cand.reshape(-1)]))
             if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
                 raise ValueError('recommend: a node id outside [0, n_nodes)')
+        sub_col = None
+        if subset is not None:  # the snapshot row of every candidate, -1: not in the catalogue
+            try:
+                sub_col = (snap.col_of if snap is not None else hip_ops.catalogue_index(cand, self.n_nodes))[subset]
+            except ValueError as e:
+                raise ValueError(f'recommend: subset names the rows of the catalogue by node id ({e})') from None
         if exclude_seen and col_of is None:
             col_of = hip_ops.catalogue_index(cand, self.n_nodes)
         ts64 = ts.to(dev).double().contiguous().reshape(-1)
@@ -1114,7 +1174,7 @@ class TIGE(nn.Module):
         out_ids = torch.zeros(B, k, dtype=torch.int64, device=dev)
         out_scores = torch.full((B, k), float('-inf'), dtype=torch.float32, device=dev)
         n_valid = torch.zeros(B, dtype=torch.int32, device=dev)
-        if B == 0 or Cc == 0:
+        if B == 0 or Cc == 0 or Cq == 0:
             return out_ids, out_scores, n_valid
         if uptodate is not None:
             if catalogue_at is not None:  # B + C queries, one call, before anything is embedded
@@ -1126,7 +1186,7 @@ class TIGE(nn.Module):
         if catalogue_at is not None:
             snap = self._make_snapshot(cand, t_snap, graph, strategy)
         bad = torch.zeros(1, dtype=torch.int64, device=dev)
-        step = max(1, int(chunk_queries) // (Cc + 1))
+        step = max(1, int(chunk_queries) // (Cq + 1))
         if snap is not None:
             from .training import score_struct
             d, K = self.memory_dim, self.n_neighbors
@@ -1141,6 +1201,22 @@ class TIGE(nn.Module):
                 hip_ops.raise_if_err(err)
         for lo in range(0, B, step):
             hi = min(B, lo + step)
+            if subset is not None:  # a per-query subset of the snapshot's rows
+                with torch.no_grad():
+                    src_c, col_c = src_ids[lo:hi], sub_col[lo:hi]
+                    h_src, nb_src = h_all[lo:hi], None if nb_all is None else nb_all[lo:hi]
+                    scores = torch.empty(hi - lo, Cq, dtype=torch.float32, device=dev)
+                    nbytes = int(lib.tg_rank_scores_gathered_workspace_bytes(hi - lo, d, C.byref(sp)))
+                    ws = self._ws('rank', nbytes)
+                    check(lib.tg_rank_scores_gathered(hi - lo, Cc, Cq, d, K, C.byref(sp), ptr(h_src), ptr(P), ptr(nb_src),
+                                                      ptr(snap.nb), ptr(src_c), ptr(snap.ids), ptr(col_c), ptr(scores), Cq,
+                                                      ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_rank_scores_gathered')
+                mk = col_c >= 0
+                if mask is not None:
+                    mk = mk & mask[lo:hi]
+                top = hip_ops.topk_rows(scores, subset[lo:hi], k, mask=mk, acc=bad)
+                out_ids[lo:hi], out_scores[lo:hi], n_valid[lo:hi] = top['ids'], top['scores'], top['n_valid']
+                continue
             ids = cand.unsqueeze(0).expand(hi - lo, -1) if shared else cand[lo:hi]
             if snap is None:
                 scores = self._pair_scores('recommend', src_ids[lo:hi], ids, ts64[lo:hi], graph, strategy, chunk_queries)
@@ -1167,22 +1243,42 @@ class TIGE(nn.Module):
         return out_ids, out_scores, n_valid
 
     def recommend_walk(self, src_ids: Tensor, ts: Tensor, k: int, *, C: int = 256, graph=None,
-                       uptodate: Optional[Tensor] = None, chunk_queries: int = 65536, **walk):
+                       uptodate: Optional[Tensor] = None, chunk_queries: int = 65536,
+                       snapshot: Optional[CatalogueSnapshot] = None, **walk):
         """Retrieve, then rank: every query's candidates come from the graph itself - `hip_ops.walk_candidates` over the
         graph `recommend` would use, at the query's own time, C per query (**walk: its fanout / take / exclude_seen /
         keep_self) - and `recommend` lists the k best of them -> (ids int64 [B, k], scores float32 [B, k], n_valid int32
         [B], cand: the dict of walk_candidates).  Exactly `recommend(src_ids, ts, cand['ids'], k, ...)`: the per-query form
         drops the padding id 0, `uptodate` restarts what the B (1 + C) queries involve, and whatever `recommend` refuses
-        is refused here before the walk runs.  The walk's own exclude_seen is the seen-item filter of this form."""
+        is refused here before the walk runs.  The walk's own exclude_seen is the seen-item filter of this form.
+        snapshot (a CatalogueSnapshot of embed_catalogue): the candidates are ranked on the snapshot's rows instead of
+        being embedded - exactly `recommend_subset(src_ids, ts, snapshot, k, cand['ids'])`: B source
+        embeddings and one gathered pair score per candidate; a candidate that is not in the catalogue is left out.
+        cand then also holds n_in_catalogue int32 [B], the valid candidates of each query that the catalogue lists.
+        `uptodate` together with a snapshot is refused as in recommend."""
         graph, _ = self._pair_refusals('recommend_walk', graph, chunk_queries, uptodate)
         if not 1 <= int(k) <= TG_TOPK_MAX_K:
             raise ValueError(f'recommend_walk: 1 <= k <= {TG_TOPK_MAX_K}')
+        if snapshot is not None:
+            if not isinstance(snapshot, CatalogueSnapshot):
+                raise ValueError('recommend_walk: snapshot is a CatalogueSnapshot of embed_catalogue')
+            if uptodate is not None:
+                raise ValueError('recommend_walk: uptodate with a ready catalogue snapshot - the restart would make the '
+                                 'snapshot stale.  Run restart_involved on the sources first, then '
+                                 'embed_catalogue(..., uptodate=bitmap)')
+            self._check_snapshot(snapshot, graph, False)
         dev = self.device
         src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
         ts64 = ts.to(dev).double().contiguous().reshape(-1)
         cand = hip_ops.walk_candidates(graph, src_ids, ts64, C, **walk)
-        ids, scores, n_valid = self.recommend(src_ids, ts64, cand['ids'], k, graph=graph, chunk_queries=chunk_queries,
-                                              uptodate=uptodate)
+        if snapshot is None:
+            ids, scores, n_valid = self.recommend(src_ids, ts64, cand['ids'], k, graph=graph, chunk_queries=chunk_queries,
+                                                  uptodate=uptodate)
+        else:
+            ids, scores, n_valid = self.recommend_subset(src_ids, ts64, snapshot, k, cand['ids'], graph=graph,
+                                                         chunk_queries=chunk_queries)
+            found = (snapshot.col_of[cand['ids']] >= 0) & (cand['ids'] != 0)
+            cand['n_in_catalogue'] = found.sum(1).to(torch.int32)
         return ids, scores, n_valid, cand
 
     # ---- fused path ---------------------------------------------------------------------

@@ -39,6 +39,12 @@ destination was among the candidates at all (`eval_recommendation(walk=...)`'s c
 the snapshot's rows (`TIGE.recommend_walk(..., snapshot=snap)`: only the sources are embedded; a candidate that is not a
 destination node of the dataset is left out; `eval_recommendation(walk=dict(C=..., catalogue=...))`).  The line printed
 adds in_catalogue, the share of generated candidates that the catalogue lists.
+--walk C --fill T [--fill_window SECONDS] back-fills: once per batch the T most active destination nodes of the window
+before the batch's earliest event time (`hip_ops.trending`; without --fill_window: of everything before it) are appended
+to every row the walk leaves short, under the walk's own rules (`hip_ops.fill_candidates`; `TIGE.recommend_walk(...,
+fill=dict(T=..., window=..., among=destinations))`), so a source without history gets the popular items instead of an
+empty list.  The line printed reads recall@C coverage_walk -> coverage and adds `filled`, the filled share of all
+candidates.
 
 Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
@@ -57,13 +63,17 @@ from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
 
 def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
         hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-        device='cuda:0', snapshot=False, walk=None, fanout=(10, 10, 10)):
+        device='cuda:0', snapshot=False, walk=None, fanout=(10, 10, 10), fill=None, fill_window=None):
     """-> (ids [n_test, k], scores [n_test, k], the eval_recommendation dict).  The model settings must be those the
     checkpoint was trained with (examples/link_prediction.py defaults here).  snapshot: one catalogue snapshot per batch
     at the batch's earliest event time (catalogue_at='batch') instead of the exact per-pair protocol.  walk=C: per-event
     walk candidates (C per event over `fanout`, the last level and, with three levels, the first one taken) instead of
     the catalogue of all destinations; the dict's coverage is then the generator's recall@C.  walk with snapshot: the
-    walk's candidates ranked on the per-batch snapshot of all destinations; the dict gains in_catalogue."""
+    walk's candidates ranked on the per-batch snapshot of all destinations; the dict gains in_catalogue.  fill=T (with
+    walk): rows back-filled from the T most active destinations of the fill_window seconds (None: everything) before the
+    batch's earliest event time; the dict gains coverage_walk and filled."""
+    if fill is not None and walk is None:
+        raise ValueError('fill back-fills walk candidates: give walk=C as well')
     fanout = tuple(int(f) for f in fanout)
     wk = dict(fanout=fanout, take=tuple(l == len(fanout) - 1 or (l == 0 and len(fanout) == 3) for l in range(len(fanout))))
     device = torch.device(device)
@@ -81,6 +91,7 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     model.graph = full_graph
     catalogue = torch.from_numpy(np.unique(full_data.dst).astype(np.int64)).to(device)
     col_of = hip_ops.catalogue_index(catalogue, model.n_nodes)
+    fl = None if fill is None else dict(T=int(fill), window=fill_window, among=catalogue)
     start = model.save_memory_state()
     ids, scores = [], []
     with torch.no_grad():  # the lists themselves: the loop of eval_recommendation, keeping what recommend returns
@@ -90,7 +101,7 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
             if walk is not None:
                 snap = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else None
                 i, s, _, _ = model.recommend_walk(src, cg.ts64, k, C=walk, graph=full_graph, exclude_seen=exclude_seen,
-                                                  snapshot=snap, **wk)
+                                                  snapshot=snap, fill=fl, **wk)
             else:
                 items = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else catalogue
                 i, s, _ = model.recommend(src, cg.ts64, items, k, exclude_seen=exclude_seen, graph=full_graph, col_of=col_of)
@@ -102,7 +113,8 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     np.save(os.path.join(out_dir, 'scores.npy'), scores)
     model.load_memory_state(start)  # the same pass once more, folded into the metrics
     if walk is not None:
-        out = eval_recommendation(model, test_dl, device, walk=dict(wk, C=walk, **(dict(catalogue=catalogue) if snapshot else {})),
+        out = eval_recommendation(model, test_dl, device, walk=dict(wk, C=walk, **(dict(catalogue=catalogue) if snapshot else {}),
+                                                                    **(dict(fill=fl) if fl is not None else {})),
                                   k=k, exclude_seen=exclude_seen)
     else:
         out = eval_recommendation(model, test_dl, device, catalogue, k=k, exclude_seen=exclude_seen,
@@ -254,6 +266,10 @@ if __name__ == '__main__':
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
+    ap.add_argument('--fill', type=int, default=None, metavar='T', help='--walk: back-fill short rows from the T most active '
+                    'destination nodes before the batch (hip_ops.trending, hip_ops.fill_candidates)')
+    ap.add_argument('--fill_window', type=float, default=None, metavar='SECONDS', help='--fill: count activity in this many '
+                    'seconds before the batch\'s earliest event time (default: everything before it)')
     a = ap.parse_args()
     if a.cold:
         m, restarted = run_cold(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, seed=a.seed, bs=a.bs,
@@ -269,7 +285,8 @@ if __name__ == '__main__':
                   f"({m['n_events']} events)")
         sys.exit(0)
     ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
-                    restarter_type=a.restarter_type, snapshot=a.snapshot, walk=a.walk, fanout=a.fanout.split(','))
+                    restarter_type=a.restarter_type, snapshot=a.snapshot, walk=a.walk, fanout=a.fanout.split(','),
+                    fill=a.fill, fill_window=a.fill_window)
     print('protocol: ' + (f'{a.walk} walk candidates per event (fanout {a.fanout}), ranked on one catalogue snapshot per batch '
                           "at the batch's earliest event time"
                           if a.walk is not None and a.snapshot else
@@ -278,6 +295,8 @@ if __name__ == '__main__':
                           "one catalogue snapshot per batch at the batch's earliest event time (catalogue_at='batch')"
                           if a.snapshot else 'exact - every (query, item) pair embedded at the query\'s time'))
     cov = f"recall@{a.walk} {m['coverage']:.4f}" if a.walk is not None else f"coverage {m['coverage']:.4f}"
+    if 'coverage_walk' in m:
+        cov = f"recall@{a.walk} {m['coverage_walk']:.4f} -> {m['coverage']:.4f}  filled {m['filled']:.4f}"
     if 'in_catalogue' in m:
         cov += f"  in_catalogue {m['in_catalogue']:.4f}"
     print(f"test: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "

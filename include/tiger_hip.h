@@ -1226,6 +1226,61 @@ int tg_walk_candidates_host(const tg_tcsr* g, int64_t B, const int64_t* src_host
                             int32_t* counts_host, int32_t* n_valid_host, int32_t* n_distinct_host);
 
 /* ------------------------------------------------------------------------- */
+/* Trending candidates (no reference counterpart): the most active nodes of a */
+/* time window, and a shared list appended to per-query candidate rows - the   */
+/* back-fill of a retrieve-then-rank line whose personal source runs dry       */
+/* ------------------------------------------------------------------------- */
+/* c(v) = the number of T-CSR entries of node v with t_lo <= time < t_hi = prefix_end(v, t_hi) - prefix_end(v, t_lo), both
+ * with the samplers' strict float64 '<'; both edge directions count, as the T-CSR stores them, and so do multi-edges; a node
+ * outside [0, num_node) has c = 0.  t_lo = -inf: everything before t_hi.
+ * Eligible: the ids of among (int64 [M]; distinct - the caller's contract, the Python front checks it), or with among ==
+ * NULL every node 1 .. num_node - 1 (M is then unused).  Candidates = the eligible ids with c > 0, never node 0.  Order
+ * (total): higher c first, equal c by ascending id - the order of `among` does not influence the result.
+ * Outputs (device; nothing is read back): ids int64 [T] and counts int32 [T], the first min(T, n) candidates and their c,
+ * padded with 0; n_valid int32 [1] = min(T, n); n_distinct int32 [1] = n.  M == 0 is valid and gives all zeros.
+ * Launches: the window counts (one 16-lane group per eligible node, a capped grid that loops) as 64-bit keys
+ * (c << 32) | (0xFFFFFFFF - id) into the workspace; tiles of 2 048 keys sorted in LDS; then rounds that merge sixteen runs
+ * of T keys per workgroup until one is left.  Two launches up to 2 048 eligible nodes, three up to 32 768, four up to
+ * 524 288, five up to 8 388 608: the number depends on M (or num_node) alone.  Integer work, no atomics: bit-exact and
+ * independent of scheduling.
+ * ws: tg_trending_workspace_bytes(M or num_node, T) bytes, 16-byte aligned: 8 bytes per eligible node (rounded up to
+ * whole tiles, one tile at least) plus the merge buffers, (T / 2 048) (17 / 256) of that, and 4 bytes per tile.
+ * TG_EINVAL before anything is launched: T outside [1, TG_TREND_MAX]; M < 0; t_lo > t_hi; a NaN bound; a null pointer
+ * (among may be NULL); a misaligned workspace.  TG_EWORKSPACE for a missing or short workspace. */
+#define TG_TREND_MAX 2048
+size_t tg_trending_workspace_bytes(int64_t M_or_num_node, int32_t T);
+int tg_trending(const tg_tcsr* g, double t_lo, double t_hi, const int64_t* among, int64_t M, int32_t T, int64_t* ids,
+                int32_t* counts, int32_t* n_valid, int32_t* n_distinct, void* ws, size_t ws_bytes, void* stream);
+/* The same on the host (g and every array HOST pointers; plain C++ over the T-CSR arrays); identical outputs. */
+int tg_trending_host(const tg_tcsr* g, double t_lo, double t_hi, const int64_t* among_host, int64_t M, int32_t T,
+                     int64_t* ids_host, int32_t* counts_host, int32_t* n_valid_host, int32_t* n_distinct_host);
+
+/* Append a shared list to per-query candidate rows.  ids int64 [B, C], counts int32 [B, C], n_valid int32 [B]: rows as
+ * tg_walk_candidates leaves them, all three in AND out.  fill_ids int64 [T]; n_fill int32 [1], a DEVICE pointer the kernel
+ * reads (normally tg_trending's n_valid: the chain has no host synchronisation).  For query i the ids fill_ids[p], p = 0 ..
+ * min(*n_fill, T) - 1, are taken in order; one is skipped when it is 0 (or outside [1, 2^31): no node), src[i] unless
+ * flags & TG_WALK_KEEP_SELF, already in the row - ids[i, :n_valid[i]] or an id this call appended - or, with flags &
+ * TG_WALK_EXCLUDE_SEEN, a neighbour of ANY entry of src[i] with time < ts[i] (the whole prefix, strict float64).  The
+ * others are appended until the row holds C, with counts = 0: a walk candidate has weight >= 1, so weight 0 marks a filled
+ * column.  n_filled int32 [B] (out) = the number appended; n_valid[i] += n_filled[i].  Columns at and beyond the new
+ * n_valid[i] are not written; a row that is already full (n_valid[i] >= C) is left untouched.  src[i] outside
+ * [0, num_node) counts as a node without entries; the Python front refuses it.
+ * One 256-thread workgroup per query (capped grid), one launch, no workspace, no global atomics: the workgroup hashes the
+ * fill list into an LDS table once and reuses it for every query it serves; per query a flag per list position and a block
+ * prefix scan in position order.  tg_fill_candidates_lds_bytes(T) bytes of dynamic LDS (0 for a refused T), a multiple of
+ * 16, at most 64 KiB.
+ * TG_EINVAL before anything is launched: C outside [1, TG_WALK_MAX_ENDPOINTS]; T outside [1, TG_TREND_MAX]; flags outside
+ * [0, 3]; B < 0; a null pointer.  B == 0 is valid and touches nothing. */
+size_t tg_fill_candidates_lds_bytes(int32_t T);
+int tg_fill_candidates(const tg_tcsr* g, int64_t B, const int64_t* src, const double* ts, int32_t C, int64_t* ids,
+                       int32_t* counts, int32_t* n_valid, const int64_t* fill_ids, const int32_t* n_fill, int32_t T,
+                       int32_t flags, int32_t* n_filled, void* stream);
+/* The same on the host (every pointer a HOST pointer, n_fill included); identical outputs. */
+int tg_fill_candidates_host(const tg_tcsr* g, int64_t B, const int64_t* src_host, const double* ts_host, int32_t C,
+                            int64_t* ids_host, int32_t* counts_host, int32_t* n_valid_host, const int64_t* fill_ids_host,
+                            const int32_t* n_fill_host, int32_t T, int32_t flags, int32_t* n_filled_host);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: replicated write-back of a GLOBAL batch from all-gathered rows  */
 /* (www2023tiger_amd/dist.py; STEP 4-6 of tiger.py:229-255 for every event of */
 /* the global batch, the embeddings having been computed on other ranks)      */

@@ -22,6 +22,7 @@ TG_TOPK_MAX_K = 64  # tg_topk_rows: positions per row
 TG_INVOLVED_MAX_K = 64  # tg_involved_list: sampler slots per query
 TG_WALK_MAX_FANOUT, TG_WALK_MAX_FRONTIER, TG_WALK_MAX_ENDPOINTS = 64, 1024, 2048  # tg_walk_candidates: the caps
 TG_WALK_EXCLUDE_SEEN, TG_WALK_KEEP_SELF = 1, 2  # tg_walk_candidates: flags
+TG_TREND_MAX = 2048  # tg_trending, tg_fill_candidates: positions of the shared list
 ERR_PAST_MEMORY, ERR_DUPLICATE_IDS, ERR_UNUSED_MESSAGE = 1, 2, 4
 ERR_MSG_BEFORE_MEM, ERR_MSG_TS_MISMATCH, ERR_EVENT_BEFORE_MEM = 8, 16, 32
 
@@ -305,6 +306,12 @@ SIGNATURES = {
     'tg_walk_candidates_lds_bytes': (sz, [i32, vp, i32]),
     'tg_walk_candidates': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     'tg_walk_candidates_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+    'tg_trending_workspace_bytes': (sz, [i64, i32]),
+    'tg_trending': (C.c_int, [P(TgTcsr), C.c_double, C.c_double, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_trending_host': (C.c_int, [P(TgTcsr), C.c_double, C.c_double, vp, i64, i32, vp, vp, vp, vp]),
+    'tg_fill_candidates_lds_bytes': (sz, [i32]),
+    'tg_fill_candidates': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    'tg_fill_candidates_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
     'tg_stream_writeback_workspace_bytes': (sz, [P(TgModel), i64]),
     'tg_stream_writeback': (C.c_int, [P(TgModel), P(TgWritebackIo), vp, sz, vp]),
 }

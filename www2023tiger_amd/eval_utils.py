@@ -683,6 +683,12 @@ def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk
     catalogue lists.  lazy_restarts restarts cat[src, dst, neg] at the events' times plus the catalogue at the batch's
     earliest time, in one call.  An APPROXIMATION in the same sense as catalogue_at='batch' (items as of the batch's
     start); its effect on hit rate / NDCG on trained weights has not been measured.
+    walk with a 'fill' key (dict(T=..., window=None, among=None)): back-fill - per batch ONE `hip_ops.trending` list on the
+    loader's graph at the batch's earliest event time (among defaults to walk['catalogue'], else all nodes), appended to
+    every event's row at the event's own time under the walk's rules (`hip_ops.fill_candidates`); the filled rows are
+    ranked.  coverage is then the recall of the FILLED rows; `coverage_walk`, the recall before filling, and `filled`, the
+    filled candidates divided by all valid candidates, are added.  Its effect on hit rate / NDCG on trained weights has
+    not been measured.
     Refused: restart_mode=True (use lazy_restarts=True), a catalogue_at other than None / 'batch', walk together with a
     catalogue or with catalogue_at, neither a catalogue nor a walk, and whatever TIGE.recommend refuses."""
     from . import hip_ops
@@ -771,6 +777,12 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
         raise ValueError("eval_recommendation: walk needs 'C', the candidates per event")
     C = int(walk.pop('C'))
     cat = walk.pop('catalogue', None)
+    fill = walk.pop('fill', None)
+    if fill is not None:
+        fill = hip_ops._fill_plan('eval_recommendation(walk)', fill)
+        if fill['t'] is not None:
+            raise ValueError("eval_recommendation: fill takes no 't' - the trending list is taken at every batch's earliest "
+                             'event time')
     if 'exclude_seen' in walk:
         raise ValueError('eval_recommendation: exclude_seen is the function\'s own keyword; it is passed into the walk')
     hip_ops._walk_plan('eval_recommendation(walk)', C, walk.get('fanout', (10, 10, 10)), walk.get('take', (True, False, True)))
@@ -788,6 +800,7 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
     graph = getattr(getattr(dl, 'collate_fn', None), 'graph', None)
     acc = torch.zeros(4, dtype=torch.float64, device=device)  # hits, sum of gains, sum of reciprocal places, covered
     gen = torch.zeros(2, dtype=torch.float64, device=device)  # candidates generated, of them in the catalogue
+    filled = torch.zeros(3, dtype=torch.float64, device=device)  # covered before filling, candidates filled, all valid ones
     place = torch.arange(k, dtype=torch.int64, device=device)
     positions, n = [], 0
     with torch.no_grad():
@@ -799,7 +812,17 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
             t = (ts if ts64 is None else ts64).to(device)
             g = graph if graph is not None else getattr(comp_graph, 'graph', None)
             g = model.graph if g is None else g
-            cand = hip_ops.walk_candidates(g, src_ids, t, C, exclude_seen=exclude_seen, **walk)['ids']
+            rows = hip_ops.walk_candidates(g, src_ids, t, C, exclude_seen=exclude_seen, **walk)
+            cand = rows['ids']
+            if fill is not None and len(src_ids):   # the trending list once per batch, at its earliest event time
+                among = fill['among'] if fill['among'] is not None else cat
+                trend = hip_ops.trending(g, float(t.double().min()), fill['T'], window=fill['window'],
+                                         among=None if among is None else torch.as_tensor(among).to(device))
+                rows = hip_ops.fill_candidates(g, src_ids, t, rows, trend, exclude_seen=exclude_seen,
+                                               keep_self=bool(walk.get('keep_self', False)))
+                walked = ((cand == dst_ids[:, None]) & (cand != 0)).any(1)                 # the recall before filling
+                cand = rows['ids']
+                filled += torch.stack([walked.sum().double(), rows['n_filled'].sum().double(), rows['n_valid'].sum().double()])
             if cat is not None and len(src_ids):
                 t0 = float(t.double().min())
                 if lazy_restarts:  # cat[src, dst, neg] at the event times, the catalogue at the batch's earliest time
@@ -836,6 +859,10 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
     if cat is not None:
         n_gen, n_in = gen.cpu().tolist()
         out['in_catalogue'] = n_in / n_gen if n_gen else nan
+    if fill is not None:
+        n_walked, n_filled, n_all = filled.cpu().tolist()
+        out['coverage_walk'] = n_walked / n if n else nan
+        out['filled'] = n_filled / n_all if n_all else nan
     if return_positions:
         out['positions'] = torch.cat(positions) if positions else torch.zeros(0, dtype=torch.int64, device=device)
     return out

@@ -427,3 +427,142 @@ def walk_candidates(graph, src: Tensor, ts: Tensor, C: int, *, fanout=(10, 10, 1
             raise ValueError(f'walk_candidates: the graph lives on {graph.device}, the queries on {dev}')
         check(lib.tg_walk_candidates(C_.byref(graph.tcsr), *args, stream_ptr(dev)), 'tg_walk_candidates')
     return out
+
+
+# ---- trending candidates (tg_trending, tg_fill_candidates and their host twins) ---------------------------------------------
+def _graph_struct(what: str, graph, dev):
+    """the tg_tcsr a call on `dev` runs over: the host arrays for host tensors, graph.tcsr for tensors on the graph's device
+    -> (struct, whatever keeps its arrays alive)"""
+    if dev.type == 'cpu':
+        h = graph._host_tcsr()
+        return _lib.TgTcsr(graph.num_node, len(h[1]), *(ptr(a) for a in h)), h
+    gd = graph.device
+    if gd.type != dev.type or (gd.index is not None and dev.index is not None and gd.index != dev.index):
+        raise ValueError(f'{what}: the graph lives on {graph.device}, the tensors on {dev}')
+    return graph.tcsr, None
+
+
+def trending(graph, t, T: int, *, window=None, among: Optional[Tensor] = None) -> dict:
+    """The T most active nodes of a time window (tiger_hip.h: tg_trending): c(v) = the T-CSR entries of v with
+    t - window <= time < t - strict float64 cuts, both edge directions, multi-edges counted; window=None: everything before
+    t - over the ids of `among` (int64 [M], no id twice), or every node but 0.  Order: higher c first, equal c by ascending
+    id; node 0 and nodes with c == 0 are never listed.  -> dict(ids int64 [T] and counts int32 [T], padded with 0; n_valid
+    int32 [1] = min(T, n_distinct); n_distinct int32 [1]), on the device of `among` (the graph's without one); nothing is
+    read back.  t_lo = t - window is computed in float64 on the host.  Device tensors take the device entry over graph.tcsr,
+    host tensors the host twin over the graph's host arrays.  ValueError for T outside [1, TG_TREND_MAX], a window that is
+    not positive, a NaN, an id of `among` listed twice or outside [0, num_node)."""
+    import ctypes as C_
+    import math
+    T = int(T)
+    if not 1 <= T <= _lib.TG_TREND_MAX:
+        raise ValueError(f'trending: 1 <= T <= TG_TREND_MAX = {_lib.TG_TREND_MAX}, not {T}')
+    t_hi = float(t)
+    if math.isnan(t_hi):
+        raise ValueError('trending: t is NaN')
+    if window is None:
+        t_lo = -math.inf
+    else:
+        window = float(window)
+        if math.isnan(window) or not window > 0:
+            raise ValueError(f'trending: window is positive (or None: everything before t), not {window}')
+        t_lo = t_hi - window
+    if among is None:
+        dev, M = torch.device(graph.device), 0
+    else:
+        among = _i64(torch.as_tensor(among)).reshape(-1)
+        dev, M = among.device, among.numel()
+        try:
+            catalogue_index(among, graph.num_node)   # no id twice, every id a node
+        except ValueError as e:
+            raise ValueError(str(e).replace('catalogue_index', 'trending: among').replace('the catalogue', 'among')) from None
+        if M == 0:   # (an empty tensor has no address, and NULL means every node)
+            among = torch.zeros(1, dtype=torch.int64, device=dev)
+    tc, _keep = _graph_struct('trending', graph, dev)
+    out = dict(ids=torch.zeros(T, dtype=torch.int64, device=dev), counts=torch.zeros(T, dtype=torch.int32, device=dev),
+               n_valid=torch.zeros(1, dtype=torch.int32, device=dev), n_distinct=torch.zeros(1, dtype=torch.int32, device=dev))
+    args = (C_.byref(tc), t_lo, t_hi, ptr(among), M, T, ptr(out['ids']), ptr(out['counts']), ptr(out['n_valid']),
+            ptr(out['n_distinct']))
+    if dev.type == 'cpu':
+        check(lib.tg_trending_host(*args), 'tg_trending_host')
+    else:
+        nbytes = int(lib.tg_trending_workspace_bytes(graph.num_node if among is None else M, T))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.tg_trending(*args, ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_trending')
+    return out
+
+
+def fill_candidates(graph, src: Tensor, ts: Tensor, cand: dict, trend: dict, *, exclude_seen: bool = False,
+                    keep_self: bool = False) -> dict:
+    """Back-fill per-query candidate rows from a shared list (tiger_hip.h: tg_fill_candidates).  cand: a `walk_candidates`
+    dict (ids / counts [B, C], n_valid [B]); trend: a `trending` dict (ids [T], n_valid [1]).  For every query the ids of
+    trend['ids'][:n_valid] are appended in order behind the row's n_valid candidates until it holds C, leaving out id 0,
+    the source unless keep_self, what the row already holds and, with exclude_seen, every node the source has any entry
+    with before ts[i] - the walk's own rules; pass the walk's flags.  Appended columns get counts == 0 (a walk candidate
+    has weight >= 1).  -> dict(ids, counts, n_valid: fresh tensors, the caller's are not written; n_distinct: cand's own,
+    unchanged; n_filled int32 [B], the ids appended per query).  The list's length is read on the device: no
+    synchronisation.  Device tensors take the device entry, host tensors the host twin.  ValueError for shapes or dtypes that
+    do not fit, a source outside [0, num_node), tensors on different devices."""
+    import ctypes as C_
+    dev = src.device
+    src = _i64(src).reshape(-1)
+    B = src.numel()
+    ts = ts.to(dev).double().contiguous().reshape(-1)
+    for name in ('ids', 'counts', 'n_valid'):
+        if name not in cand:
+            raise ValueError(f"fill_candidates: cand is a walk_candidates dict; it has no '{name}'")
+    if 'ids' not in trend or 'n_valid' not in trend:
+        raise ValueError("fill_candidates: trend is a trending dict with 'ids' and 'n_valid'")
+    ids, counts, n_valid = cand['ids'], cand['counts'], cand['n_valid']
+    fill, n_fill = trend['ids'].contiguous(), trend['n_valid'].contiguous()
+    if ids.dim() != 2 or ids.dtype != torch.int64 or counts.dtype != torch.int32 or n_valid.dtype != torch.int32:
+        raise ValueError('fill_candidates: cand holds ids int64 [B, C], counts int32 [B, C], n_valid int32 [B]')
+    C = ids.shape[1]
+    if ts.numel() != B or ids.shape[0] != B or counts.shape != ids.shape or n_valid.shape != (B,):
+        raise ValueError(f'fill_candidates: {B} sources, ts {tuple(ts.shape)}, ids {tuple(ids.shape)}, counts '
+                         f'{tuple(counts.shape)}, n_valid {tuple(n_valid.shape)}')
+    if not 1 <= C <= _lib.TG_WALK_MAX_ENDPOINTS:
+        raise ValueError(f'fill_candidates: 1 <= C <= TG_WALK_MAX_ENDPOINTS = {_lib.TG_WALK_MAX_ENDPOINTS}, not {C}')
+    if fill.dim() != 1 or fill.dtype != torch.int64 or n_fill.dtype != torch.int32 or n_fill.numel() != 1:
+        raise ValueError('fill_candidates: trend holds ids int64 [T] and n_valid int32 [1]')
+    T = fill.numel()
+    if not 1 <= T <= _lib.TG_TREND_MAX:
+        raise ValueError(f'fill_candidates: 1 <= T <= TG_TREND_MAX = {_lib.TG_TREND_MAX}, not {T}')
+    if any(x.device != dev for x in (ids, counts, n_valid, fill, n_fill)):
+        raise ValueError(f'fill_candidates: the sources live on {dev}, cand on {ids.device}, trend on {fill.device}')
+    if B and (int(src.min()) < 0 or int(src.max()) >= graph.num_node):
+        raise ValueError('fill_candidates: a source id outside [0, num_node)')
+    flags = (_lib.TG_WALK_EXCLUDE_SEEN if exclude_seen else 0) | (_lib.TG_WALK_KEEP_SELF if keep_self else 0)
+    tc, _keep = _graph_struct('fill_candidates', graph, dev)
+    out = dict(ids=ids.clone(memory_format=torch.contiguous_format), counts=counts.clone(memory_format=torch.contiguous_format),
+               n_valid=n_valid.clone(memory_format=torch.contiguous_format), n_filled=torch.zeros(B, dtype=torch.int32, device=dev))
+    if 'n_distinct' in cand:
+        out['n_distinct'] = cand['n_distinct']
+    args = (C_.byref(tc), B, ptr(src), ptr(ts), C, ptr(out['ids']), ptr(out['counts']), ptr(out['n_valid']),
+            ptr(fill), ptr(n_fill), T, flags, ptr(out['n_filled']))
+    if dev.type == 'cpu':
+        check(lib.tg_fill_candidates_host(*args), 'tg_fill_candidates_host')
+    else:
+        check(lib.tg_fill_candidates(*args, stream_ptr(dev)), 'tg_fill_candidates')
+    return out
+
+
+def _fill_plan(what: str, fill: dict) -> dict:
+    """the refusals of a `fill=dict(T=..., window=..., among=..., t=...)` argument that need no tensor -> a checked copy"""
+    import math
+    if not isinstance(fill, dict):
+        raise ValueError(f'{what}: fill is a dict(T=..., window=..., among=..., t=...)')
+    fill = dict(fill)
+    unknown = set(fill) - {'T', 'window', 'among', 't'}
+    if unknown:
+        raise ValueError(f'{what}: fill takes T, window, among and t, not {sorted(unknown)}')
+    if 'T' not in fill:
+        raise ValueError(f"{what}: fill needs 'T', the length of the trending list")
+    T = int(fill['T'])
+    if not 1 <= T <= _lib.TG_TREND_MAX:
+        raise ValueError(f'{what}: fill: 1 <= T <= TG_TREND_MAX = {_lib.TG_TREND_MAX}, not {T}')
+    window = fill.get('window')
+    if window is not None:
+        window = float(window)
+        if math.isnan(window) or not window > 0:
+            raise ValueError(f'{what}: fill: window is positive (or None: everything before t), not {window}')
+    return dict(T=T, window=window, among=fill.get('among'), t=fill.get('t'))

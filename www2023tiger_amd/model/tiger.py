@@ -1244,7 +1244,7 @@ class TIGE(nn.Module):
 
     def recommend_walk(self, src_ids: Tensor, ts: Tensor, k: int, *, C: int = 256, graph=None,
                        uptodate: Optional[Tensor] = None, chunk_queries: int = 65536,
-                       snapshot: Optional[CatalogueSnapshot] = None, **walk):
+                       snapshot: Optional[CatalogueSnapshot] = None, fill: Optional[dict] = None, **walk):
         """Retrieve, then rank: every query's candidates come from the graph itself - `hip_ops.walk_candidates` over the
         graph `recommend` would use, at the query's own time, C per query (**walk: its fanout / take / exclude_seen /
         keep_self) - and `recommend` lists the k best of them -> (ids int64 [B, k], scores float32 [B, k], n_valid int32
@@ -1255,8 +1255,16 @@ class TIGE(nn.Module):
         being embedded - exactly `recommend_subset(src_ids, ts, snapshot, k, cand['ids'])`: B source
         embeddings and one gathered pair score per candidate; a candidate that is not in the catalogue is left out.
         cand then also holds n_in_catalogue int32 [B], the valid candidates of each query that the catalogue lists.
-        `uptodate` together with a snapshot is refused as in recommend."""
+        `uptodate` together with a snapshot is refused as in recommend.
+        fill=dict(T=..., window=None, among=None, t=None): back-fill the rows the walk leaves short with what is popular
+        right now - `hip_ops.trending` ONCE per call (the T most active nodes of [t - window, t); t defaults to the earliest
+        query time, so nothing comes from any query's future; among defaults to snapshot.ids with a snapshot, else to all
+        nodes), then `hip_ops.fill_candidates` under the walk's own exclude_seen / keep_self, then the ranking above on the
+        filled rows.  cand is then the filled dict: its counts are 0 in the filled columns and it gains n_filled int32 [B].
+        A source without entries gets the trending list.  fill=None is the path above, unchanged."""
         graph, _ = self._pair_refusals('recommend_walk', graph, chunk_queries, uptodate)
+        if fill is not None:
+            fill = hip_ops._fill_plan('recommend_walk', fill)
         if not 1 <= int(k) <= TG_TOPK_MAX_K:
             raise ValueError(f'recommend_walk: 1 <= k <= {TG_TOPK_MAX_K}')
         if snapshot is not None:
@@ -1271,6 +1279,16 @@ class TIGE(nn.Module):
         src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
         ts64 = ts.to(dev).double().contiguous().reshape(-1)
         cand = hip_ops.walk_candidates(graph, src_ids, ts64, C, **walk)
+        if fill is not None and src_ids.numel():
+            among = fill['among'] if fill['among'] is not None else (snapshot.ids if snapshot is not None else None)
+            if among is not None:
+                among = torch.as_tensor(among).to(dev)
+            t0 = float(ts64.min()) if fill['t'] is None else float(fill['t'])
+            trend = hip_ops.trending(graph, t0, fill['T'], window=fill['window'], among=among)
+            cand = hip_ops.fill_candidates(graph, src_ids, ts64, cand, trend, exclude_seen=bool(walk.get('exclude_seen', False)),
+                                           keep_self=bool(walk.get('keep_self', False)))
+        elif fill is not None:
+            cand['n_filled'] = torch.zeros(0, dtype=torch.int32, device=dev)
         if snapshot is None:
             ids, scores, n_valid = self.recommend(src_ids, ts64, cand['ids'], k, graph=graph, chunk_queries=chunk_queries,
                                                   uptodate=uptodate)

@@ -18,6 +18,10 @@ device graph) and the entries kept and dropped are printed per batch.  With --ke
 hist_len), no window and no --exclude_seen the forgetting replay answers exactly what the replay that never forgets
 answers, so the two lines are held to the same equality; a window, a smaller cap or --exclude_seen ("seen inside the
 window") answer from less history, and the two lines may differ.
+--release_rows lets the edge-feature table shrink with the graph: every forget also releases the rows that no kept entry
+names (`TIGE.forget(..., release_edge_rows=True, keep_from=first eid not observed yet)`), the eids of the events still
+to come are shifted by the returned `shift`, and the table's rows before and after are printed per batch.  The model
+computes what it would have computed, so the equality of the two lines holds under the same conditions.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -145,12 +149,16 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest):
 
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-               device='cuda:0', window=None, keep_last=None, verbose=True, offline=True):
+               device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
     metrics then carry 'forgot': (entries kept, entries dropped) per batch.  The two replays are still equal, and that is
     asserted, when what is dropped is never read: no window, keep_last >= max(n_neighbors, hist_len), no exclude_seen.
+    release_rows: every forget also releases the edge-table rows that no kept entry names (`forget(...,
+    release_edge_rows=True, keep_from=first eid not observed yet)`); the eids of the events still to come are shifted by
+    the returned `shift`, and the online metrics carry 'rows': (table rows before, after) per batch.  What the model
+    computes does not change, so the equality above holds under the same conditions.
     offline=False: the online replay alone -> (its metrics, None)."""
     from www2023tiger_amd.data.graph import Graph
     device = torch.device(device)
@@ -180,14 +188,24 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                                         full_data.eids[:n_seen], strategy=full_graph.strategy, seed=seed,
                                         max_node_id=full_graph.num_node - 1, device=device)
         forgot = []
+        shifted = [0]   # rows released so far: the eids of the events still to come moved down by as much
+        rows = []
 
         def observe_and_forget(s, d, t, e):
+            e = e - shifted[0]
             model.observe(s, d, t, e)
             before = model.graph.tcsr.num_entry
-            g = model.forget(before=None if window is None else float(t[-1]) - window, keep_last=keep_last)
+            g = model.forget(before=None if window is None else float(t[-1]) - window, keep_last=keep_last,
+                             release_edge_rows=release_rows, keep_from=int(e[-1]) + 1 if release_rows else None)
             forgot.append((int(g.tcsr.num_entry), int(before - g.tcsr.num_entry)))
             if verbose:
                 print(f'batch {len(forgot) - 1}: {forgot[-1][0]} entries kept, {forgot[-1][1]} dropped')
+            rel = model.last_release if release_rows else None
+            if rel is not None:
+                shifted[0] += rel.shift
+                rows.append((rel.rows_before, rel.rows))
+                if verbose:
+                    print(f'batch {len(forgot) - 1}: edge table {rel.rows_before} rows -> {rel.rows}')
         forgetting = window is not None or keep_last is not None
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
                                  observe_and_forget if forgetting else model.observe)
@@ -196,6 +214,8 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
     if forgetting:
         online = dict(online, forgot=forgot)
+        if release_rows:
+            online['rows'] = rows
     return online, (offline if ids_off is not None else None)
 
 
@@ -263,6 +283,9 @@ if __name__ == '__main__':
                     'than the batch\'s last time minus this many seconds (TIGE.forget)')
     ap.add_argument('--keep_last', type=int, default=None, help='--online: after every observe, keep every node\'s last M '
                     'entries (TIGE.forget)')
+    ap.add_argument('--release_rows', action='store_true', help='--online with --keep_last / --window: every forget also '
+                    'releases the edge-table rows of the forgotten events (TIGE.forget(..., release_edge_rows=True)) and the '
+                    'eids still to come are shifted; prints the table\'s rows before and after per batch')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -280,7 +303,8 @@ if __name__ == '__main__':
     if a.online:
         for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
                                                               seed=a.seed, bs=a.bs, restarter_type=a.restarter_type,
-                                                              window=a.window, keep_last=a.keep_last)):
+                                                              window=a.window, keep_last=a.keep_last,
+                                                              release_rows=a.release_rows)):
             print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "
                   f"({m['n_events']} events)")
         sys.exit(0)

@@ -148,6 +148,38 @@ int tg_tcsr_trim_apply(const tg_tcsr* g, const int64_t* indptr_out, int64_t num_
 int tg_tcsr_trim_host(const tg_tcsr* g, double t_cut, int64_t keep_last, int64_t* indptr_out_host, double* ts_out_host,
                       int32_t* nbr_out_host, int32_t* eid_out_host, int64_t* num_entry_out);
 
+/* Releasing edge-feature rows (tg_edge_rows.hip; online serving after a trim).  The reference never drops a row of its
+ * tables (feature_getter.py:41-47, graph.py:11-42: built once over the whole stream).  A row r of the table
+ * T [n_rows, d_e] (float32, d_e % 4 == 0) is LIVE iff r == 0 (the padding row), some entry of g has
+ * eid & 0x7FFFFFFF == r, r >= keep_from (0 <= keep_from <= n_rows: rows of events not observed yet), or r is one of the
+ * n_pin ids of `pin`.  Results:
+ *   remap [n_rows] int32: the number of live rows below r if r is live, else -1 (monotone: kept rows keep their order,
+ *     rows at and beyond keep_from move as one block by n_rows - n_live);
+ *   table_out [n_live, d_e]: table_out[remap[r]] = table[r], bit for bit;
+ *   eid_out [num_entry]: remap[eid & 0x7FFFFFFF] | (eid & 0x80000000);  indptr / ts / nbr of g are not read.
+ * An entry or a pin that names no row of the table is an error: nothing is written to remap / table_out / eid_out.
+ *
+ * tg_edge_rows_workspace_bytes (no counterpart): bytes of `ws`, 0 for n_rows outside [1, 2^31) or num_entry outside
+ * [0, 2^32).  The same `ws`, untouched in between, goes to plan and to apply.
+ * tg_edge_rows_plan (no counterpart): a memset, one launch over the entries (byte marks), two over the rows (scan).
+ * Writes remap, the inverse list into ws and *n_live_dev (int64; -1 for the error above, remap then unwritten).  The
+ * caller reads back that ONE int64 - the only synchronisation - to allocate table_out exactly, then calls
+ * tg_edge_rows_apply (no counterpart): one launch over the rows of table_out (16-byte loads and stores, contiguous
+ * stores), one over the entries.  table == NULL renumbers the graph alone.  table and table_out must not overlap.
+ * All pointers are DEVICE pointers; ws, remap, table and table_out 16-byte aligned; asynchronous on `stream`; a short
+ * workspace returns TG_EWORKSPACE before anything is launched.  No atomics: the result does not depend on the launch
+ * geometry.  TG_EINVAL: a keep_from outside [0, n_rows], a negative count, d_e % 4 != 0, n_live outside [1, n_rows]. */
+size_t tg_edge_rows_workspace_bytes(int64_t n_rows, int64_t num_entry);
+int tg_edge_rows_plan(const tg_tcsr* g, int64_t n_rows, int64_t keep_from, const int64_t* pin, int64_t n_pin,
+                      int32_t* remap, int64_t* n_live_dev, void* ws, size_t ws_bytes, void* stream);
+int tg_edge_rows_apply(const tg_tcsr* g, const float* table, int64_t n_rows, int32_t d_e, const int32_t* remap,
+                       int64_t n_live, float* table_out, int32_t* eid_out, const void* ws, size_t ws_bytes, void* stream);
+/* tg_edge_rows_host (no counterpart): the host twin, HOST pointers (g->eid included), plain C++.  table_out has room for
+ * n_rows rows; *n_live_out = live rows.  TG_EINVAL for an entry or a pin that names no row, before anything is written. */
+int tg_edge_rows_host(const tg_tcsr* g, const float* table, int64_t n_rows, int32_t d_e, int64_t keep_from,
+                      const int64_t* pin, int64_t n_pin, int32_t* remap, float* table_out, int32_t* eid_out,
+                      int64_t* n_live_out);
+
 /* Graph.sample_temporal_neighbor(strategy='recent_edges') and Graph.get_history
  * (graph.py:67-127,150-155): per query the last K entries with ts < t (strict),
  * left padded with zeros.  out_dir may be NULL.  If mark_flags != NULL every query

@@ -9,7 +9,8 @@ The object is immutable after construction, so the collator thread and the main
 thread may sample concurrently (each call allocates its own outputs and runs on
 the calling thread's current stream).  New events are ingested by `extended`, which
 returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was; old entries
-are dropped by `trimmed` (csrc/tg_trim.hip), which does the same.
+are dropped by `trimmed` (csrc/tg_trim.hip), which does the same, and `renumbered` gives the entries the row numbers of
+a packed edge table (csrc/tg_edge_rows.hip).
 """
 import ctypes as C
 import itertools
@@ -378,6 +379,47 @@ class Graph:
             if keep_last is None and ev is not None:  # a horizon alone: still the T-CSR of an event list
                 m = ev[2] >= t_cut
                 child._events = tuple(np.ascontiguousarray(a[m]) for a in ev)
+            if self._mt is not None:
+                child._mt = self._mt
+        return child
+
+    # ---- renumbered edge ids ---------------------------------------------------------
+    def renumbered(self, remap, eid_out) -> 'Graph':
+        """A NEW Graph whose entries name the rows of a packed edge table (tg_edge_rows_*: hip_ops.edge_rows_plan / _apply /
+        _host; graph.py:11-42 has no counterpart: the reference never drops a table row).  `eid_out` is this graph's eid
+        array pushed through `remap` (old row -> new row, -1: released), bit 31 - the direction flag - carried over.  The
+        child SHARES indptr, ts and nbr with this graph (the same tensors / arrays) and owns `eid_out`; this graph stays
+        valid and unchanged.  strategy / seed / alpha / device, `rng` and device MT19937 state, the latest event time and
+        the time-ordered flag carry over; the child has a `serial` and a host origin of its own, as a trimmed child has.
+        A device-resident parent keeps eid_out on its device, a host-only parent as a numpy array (either is moved there
+        if it is not); the event list is pushed through `remap` on the host path and dropped on the device path
+        (`_events` None).  ValueError: eid_out is no int32 array of num_entry entries."""
+        child = Graph.__new__(Graph)
+        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
+        child._time_ordered = self._time_ordered
+        child._t_last = self._t_last
+        if self._dev is not None:
+            d = self._dev
+            eid_out = torch.as_tensor(eid_out)
+            if eid_out.dtype != torch.int32 or eid_out.dim() != 1 or eid_out.numel() != d[3].numel():
+                raise ValueError(f'renumbered: eid_out must be an int32 array of {d[3].numel()} entries')
+            eid_out = eid_out.to(d[3].device).contiguous()  # (a host twin's result for a device-resident graph is uploaded)
+            child._dev = (d[0], d[1], d[2], eid_out)
+            child._set_struct()
+            child._mt = self._mt_state()
+            child._root.dev = child._dev
+        else:
+            h = self._host_tcsr()
+            e = np.ascontiguousarray(eid_out.cpu().numpy() if torch.is_tensor(eid_out) else eid_out)
+            if e.dtype != np.int32 or e.shape != h[3].shape:
+                raise ValueError(f'renumbered: eid_out must be an int32 array of {len(h[3])} entries')
+            child._host = (h[0], h[1], h[2], e)
+            ev = self._root.events
+            if ev is not None and remap is not None:
+                r = np.asarray(remap.cpu().numpy() if torch.is_tensor(remap) else remap)
+                new = r[ev[3]].astype(np.int64) if len(ev[3]) == 0 or int(ev[3].max()) < len(r) else None
+                if new is not None and (len(new) == 0 or new.min() >= 0):  # (every event's row survived: still an event list)
+                    child._events = (ev[0], ev[1], ev[2], new)
             if self._mt is not None:
                 child._mt = self._mt
         return child

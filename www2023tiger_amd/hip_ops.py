@@ -566,3 +566,101 @@ def _fill_plan(what: str, fill: dict) -> dict:
         if math.isnan(window) or not window > 0:
             raise ValueError(f'{what}: fill: window is positive (or None: everything before t), not {window}')
     return dict(T=T, window=window, among=fill.get('among'), t=fill.get('t'))
+
+
+# ---- releasing edge-feature rows (tg_edge_rows_plan / _apply and their host twin) -------------------------------------------
+def _pin_ids(pin, dev) -> Optional[Tensor]:
+    if pin is None:
+        return None
+    p = torch.as_tensor(pin).to(dev, torch.int64).contiguous().reshape(-1)
+    return p if p.numel() else None
+
+
+def edge_rows_plan(graph, n_rows: int, keep_from: Optional[int] = None, pin=None, device=None):
+    """Which rows of an edge table of `n_rows` rows does `graph` still need (tiger_hip.h: tg_edge_rows_plan)?  Live: row 0,
+    every row an entry names, rows >= keep_from (default n_rows: none), the ids of `pin`.  -> (remap int32 [n_rows]: the new
+    row or -1, n_live, ws - the workspace `edge_rows_apply` wants back).  Reads ONE int64 back (n_live: what the packed
+    table is allocated by); ValueError if an entry or a pin names no row of the table, or for a keep_from outside
+    [0, n_rows]."""
+    import ctypes as C_
+    dev = torch.device(graph.device if device is None else device)
+    if dev.type == 'cpu':
+        raise ValueError('edge_rows_plan runs on the device (host arrays: edge_rows_host)')
+    n_rows = int(n_rows)
+    keep = n_rows if keep_from is None else int(keep_from)
+    if n_rows < 1 or not 0 <= keep <= n_rows:
+        raise ValueError(f'edge_rows_plan: keep_from = {keep} for a table of {n_rows} rows')
+    g, _ = _graph_struct('edge_rows_plan', graph, dev)
+    p = _pin_ids(pin, dev)
+    remap = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    n_live = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = int(lib.tg_edge_rows_workspace_bytes(n_rows, g.num_entry))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tg_edge_rows_plan(C_.byref(g), n_rows, keep, ptr(p), 0 if p is None else p.numel(), ptr(remap), ptr(n_live),
+                                    ptr(ws), nbytes, stream_ptr(dev)), 'tg_edge_rows_plan')
+        n = int(n_live)  # the one read-back
+    if n < 0:
+        raise ValueError(f'edge_rows_plan: an entry of the graph or a pinned id names no row of the table ({n_rows} rows)')
+    return remap, n, ws
+
+
+def edge_rows_apply(graph, table: Optional[Tensor], remap: Tensor, n_live: int, ws: Tensor,
+                    table_out: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor]:
+    """Pack the live rows of `table` and renumber the graph's eids (tiger_hip.h: tg_edge_rows_apply) with the remap and the
+    workspace of `edge_rows_plan` -> (table_out [n_live, d_e], eid_out int32 [num_entry]).  table_out: a caller's buffer of
+    at least n_live rows (a backing store with head-room) whose leading rows are written; allocated exactly otherwise.
+    table=None renumbers the graph alone."""
+    import ctypes as C_
+    dev = remap.device
+    g, _ = _graph_struct('edge_rows_apply', graph, dev)
+    n_rows, n_live = remap.numel(), int(n_live)
+    d_e = 0
+    if table is not None:
+        if (table.dim() != 2 or table.dtype != torch.float32 or not table.is_contiguous() or table.shape[0] != n_rows
+                or table.device != dev or table.shape[1] % 4):
+            raise ValueError(f'edge_rows_apply: table {table.dtype} {tuple(table.shape)} on {table.device} for a remap of '
+                             f'{n_rows} rows on {dev} (float32, contiguous, d_e % 4 == 0)')
+        d_e = table.shape[1]
+        if table_out is None:
+            table_out = torch.empty(n_live, d_e, dtype=torch.float32, device=dev)
+        elif (table_out.dim() != 2 or table_out.dtype != torch.float32 or not table_out.is_contiguous()
+              or table_out.shape[0] < n_live or table_out.shape[1] != d_e or table_out.device != dev):
+            raise ValueError(f'edge_rows_apply: table_out {table_out.dtype} {tuple(table_out.shape)} for {n_live} rows of {d_e}')
+    eid_out = torch.empty(g.num_entry, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tg_edge_rows_apply(C_.byref(g), ptr(table), n_rows, d_e, ptr(remap), n_live,
+                                     ptr(table_out) if table is not None else None, ptr(eid_out), ptr(ws), ws.numel(),
+                                     stream_ptr(dev)), 'tg_edge_rows_apply')
+    return (table_out[:n_live] if table is not None else None), eid_out
+
+
+def edge_rows_host(graph, table, n_rows: int, keep_from: Optional[int] = None, pin=None):
+    """The host twin of plan + apply (tiger_hip.h: tg_edge_rows_host) over the graph's host arrays and a numpy table
+    [n_rows, d_e] (or None) -> (remap int32 [n_rows], table_out [n_live, d_e] or None, eid_out int32 [num_entry]).
+    ValueError as `edge_rows_plan`."""
+    import ctypes as C_
+    import numpy as np
+    n_rows = int(n_rows)
+    keep = n_rows if keep_from is None else int(keep_from)
+    if n_rows < 1 or not 0 <= keep <= n_rows:
+        raise ValueError(f'edge_rows_host: keep_from = {keep} for a table of {n_rows} rows')
+    h = graph._host_tcsr()
+    g = _lib.TgTcsr(graph.num_node, len(h[1]), *(ptr(a) for a in h))
+    p = None if pin is None else np.ascontiguousarray(np.asarray(pin, dtype=np.int64).reshape(-1))
+    d_e, t_out = 0, None
+    if table is not None:
+        table = np.ascontiguousarray(table, dtype=np.float32)
+        if table.ndim != 2 or table.shape[0] != n_rows or table.shape[1] % 4 or table.shape[1] == 0:
+            raise ValueError(f'edge_rows_host: table {table.shape} for {n_rows} rows (d_e % 4 == 0)')
+        d_e = table.shape[1]
+        t_out = np.empty((n_rows, d_e), dtype=np.float32)
+    remap = np.empty(n_rows, dtype=np.int32)
+    eid_out = np.empty(len(h[1]), dtype=np.int32)
+    n_live = C_.c_int64(0)
+    rc = lib.tg_edge_rows_host(C_.byref(g), ptr(table), n_rows, d_e, keep, ptr(p), 0 if p is None else len(p), ptr(remap),
+                               ptr(t_out), ptr(eid_out), C_.byref(n_live))
+    if rc == _lib.TG_EINVAL:
+        raise ValueError(f'edge_rows_host: an entry of the graph or a pinned id names no row of the table ({n_rows} rows)')
+    check(rc, 'tg_edge_rows_host')
+    return remap, (None if t_out is None else t_out[:n_live.value].copy()), eid_out

@@ -7,6 +7,23 @@ from torch import Tensor, nn
 from .. import hip_ops
 
 
+class EdgeRowsRelease:
+    """What a release of edge-table rows did (NumericalFeature.compact_edge_rows, TIGE.release_edge_rows).
+    remap: int32 [rows_before], old row -> new row, -1 for a released row; monotone, so rows at and beyond the call's
+    keep_from moved as one block: new = old - shift.  eid_out: the graph's renumbered eid array (int32, bit 31 = direction).
+    rows_before / rows: table rows before and after; shift = rows_before - rows."""
+    __slots__ = ('remap', 'eid_out', 'rows_before', 'rows', 'shift', '_store')
+
+    def __init__(self, remap, eid_out, rows_before: int, rows: int, store):
+        self.remap, self.eid_out = remap, eid_out
+        self.rows_before, self.rows = int(rows_before), int(rows)
+        self.shift = self.rows_before - self.rows
+        self._store = store
+
+    def __repr__(self):
+        return f'EdgeRowsRelease(rows_before={self.rows_before}, rows={self.rows}, shift={self.shift})'
+
+
 class NumericalFeature(nn.Module):
     """Raw node / edge feature tables.  A missing table means zeros of width `dim`
     (feature_getter.py:81-85,95-99).  The HIP engine reads the tables in place; the
@@ -76,6 +93,49 @@ class NumericalFeature(nn.Module):
         self.efeats = store[:n1]
         self.n_edges = n1
         return self.efeats.data_ptr() != cur.data_ptr()
+
+    def compact_edge_rows(self, graph, keep_from: Optional[int] = None, pin=None, *, slack: Optional[int] = None,
+                          swap: bool = True) -> Optional['EdgeRowsRelease']:
+        """Release the rows of the edge table that `graph` no longer names (tg_edge_rows_*): the live rows - row 0, every
+        row an entry of `graph` names, rows >= keep_from (default: none; rows of events not observed yet), the ids of
+        `pin` - are packed in their old order into a NEW table -> EdgeRowsRelease(remap, eid_out, rows_before, rows,
+        shift), or None without an edge table (nothing to do).  `eid_out` is what `graph.renumbered(remap, eid_out)`
+        takes: the CALLER swaps the graph.  The new backing store has n_live + max(16, n_live // 4) rows (slack=: that many
+        spare rows instead) and `efeats` is its leading n_live-row view, so the next `append_edge_rows` copies the new rows
+        and nothing else.  Old and new table exist side by side until the old one is dropped (no in-place compaction).
+        A device table is packed on the device (plan, ONE int64 read back, allocate, apply), a CPU table by the host twin.
+        swap=False leaves this object as it was; `adopt_edge_rows(result)` swaps later (TIGE.release_edge_rows: graph and
+        table change together).  Nothing has changed if it raises: NotImplementedError for a table in pinned host memory
+        (register_buffer=False), ValueError for a bad keep_from / slack or an entry or pin that names no row."""
+        if self.efeats is None:
+            return None
+        if not self.pin_mem:
+            raise NotImplementedError('compact_edge_rows: the edge table lives in pinned host memory (register_buffer=False)')
+        cur = self.efeats
+        n_rows, d_e = cur.shape
+        if slack is not None and int(slack) < 0:
+            raise ValueError(f'compact_edge_rows: slack = {slack} is negative')
+        spare = lambda n: max(16, n // 4) if slack is None else int(slack)
+        if cur.device.type == 'cpu':
+            remap, packed, eid_out = hip_ops.edge_rows_host(graph, cur.numpy(), n_rows, keep_from, pin)
+            n_live = packed.shape[0]
+            store = torch.empty(n_live + spare(n_live), d_e, dtype=cur.dtype)
+            store[:n_live] = torch.from_numpy(packed)
+            remap = torch.from_numpy(remap)
+        else:
+            remap, n_live, ws = hip_ops.edge_rows_plan(graph, n_rows, keep_from, pin, device=cur.device)
+            store = torch.empty(n_live + spare(n_live), d_e, dtype=cur.dtype, device=cur.device)
+            _, eid_out = hip_ops.edge_rows_apply(graph, cur, remap, n_live, ws, table_out=store)
+        res = EdgeRowsRelease(remap, eid_out, n_rows, n_live, store)
+        if swap:
+            self.adopt_edge_rows(res)
+        return res
+
+    def adopt_edge_rows(self, res: 'EdgeRowsRelease'):
+        """swap in the packed table of a `compact_edge_rows(..., swap=False)`"""
+        self._ef_store = res._store
+        self.efeats = res._store[:res.rows]
+        self.n_edges = res.rows
 
     def _lookup(self, table, ids, width):
         if table is None:

@@ -1613,18 +1613,63 @@ class TIGE(nn.Module):
             src, dst, ts, eids = new_graph.last_batch
         return self.stream_step(src, dst, dst if neg is None else neg, ts, eids, want_prev=want_prev)
 
-    def forget(self, before=None, keep_last=None):
+    def forget(self, before=None, keep_last=None, release_edge_rows: bool = False, keep_from=None):
         """Sliding-window expiry for a model that keeps observing: the graph is replaced by `graph.trimmed(before,
         keep_last)` (entries with a time strictly below `before`, and entries that are not among their node's last
         `keep_last`, are dropped) -> the new graph.  Only the graph changes: memories, mailbox and tables are not touched,
-        and the edge-feature table keeps its rows (eids are row indices).  A one-layer `recent_edges` model with
+        and by default the edge-feature table keeps its rows (eids are row indices).  A one-layer `recent_edges` model with
         n_neighbors and hist_len <= keep_last that forgets after every `observe` stays bit-identical to one that never
         forgets; a two-layer model does not (hop 2 is sampled at the neighbours' earlier times).  Afterwards
-        `recommend(..., exclude_seen=True)` means "seen inside the window".  Refused before anything runs: a partitioned
-        model, and what `Graph.trimmed` refuses (a NaN `before`, a negative `keep_last`)."""
+        `recommend(..., exclude_seen=True)` means "seen inside the window".
+        release_edge_rows=True: the trim is followed by `release_edge_rows(keep_from)` - the rows that no kept entry names
+        leave the table and the eids are renumbered; the result is `model.last_release` (None without an edge table) and
+        the caller translates the eids it holds as that method says.  The model still computes what it would have.
+        Refused before anything runs: a partitioned model, and what `Graph.trimmed` refuses (a NaN `before`, a negative
+        `keep_last`); with the flag also what `release_edge_rows` refuses, and then nothing at all has changed."""
         self._refuse_partitioned('forget')
-        self.graph = self.graph.trimmed(before=before, keep_last=keep_last)
+        if not release_edge_rows:
+            self.graph = self.graph.trimmed(before=before, keep_last=keep_last)
+            return self.graph
+        trimmed = self.graph.trimmed(before=before, keep_last=keep_last)
+        self.release_edge_rows(keep_from=keep_from, _graph=trimmed)  # (swaps graph and table together, or raises)
         return self.graph
+
+    last_release = None  # the EdgeRowsRelease of the latest release_edge_rows / forget(release_edge_rows=True)
+
+    def release_edge_rows(self, keep_from=None, pin=None, *, slack=None, _graph=None):
+        """Release the edge-table rows of forgotten events: every row that no entry of the graph names any more leaves the
+        table, the remaining rows are packed in their old order into a new table and the graph's eids are renumbered to
+        match (NumericalFeature.compact_edge_rows, Graph.renumbered; tg_edge_rows.hip) -> EdgeRowsRelease(remap,
+        rows_before, rows, shift), also kept as `model.last_release`; None (and nothing changes) for a model without an
+        edge table.  Kept besides the rows the graph names: row 0 (padding), rows >= keep_from (default: none) - the rows
+        the caller appended for events it has NOT observed yet -, and the ids of `pin`.  Afterwards the model computes,
+        bit for bit, what it would have computed without the call: mailbox, memories, query tables and snapshots hold edge
+        ROWS or no edge data at all, never an eid.
+        Order: plan, one int64 read back (the only synchronisation), allocate, apply; only then graph (through the
+        setter: the restarter follows), table and `invalidate_struct()`.  If anything raises, nothing has changed.  Peak
+        memory is old table + new table.  The new table has head-room for the next `observe` (slack=: spare rows).
+        WHAT THE CALLER MUST DO AFTERWARDS - eids it holds are in the old numbering:
+          * pending events, a resident InteractionData: eid -> remap[eid], or eid - shift for ids >= keep_from;
+          * the `l1_eids` of a step returned earlier are old numbers;
+          * captured device graphs and resident evaluation runs built before the call read the old graph and the old
+            table: rebuild them.
+        Refused before anything runs: a partitioned model, a table in pinned host memory (register_buffer=False), a
+        keep_from outside [0, rows], an entry or pin that names no row (ValueError)."""
+        self._refuse_partitioned('release_edge_rows')
+        fg = self.raw_feat_getter
+        graph = self.graph if _graph is None else _graph
+        res = fg.compact_edge_rows(graph, keep_from, pin, slack=slack, swap=False)
+        if res is None:
+            if _graph is not None:
+                self.graph = _graph
+            self.last_release = None
+            return None
+        child = graph.renumbered(res.remap, res.eid_out)
+        self.graph = child
+        fg.adopt_edge_rows(res)
+        self.invalidate_struct()
+        self.last_release = res
+        return res
 
     # ---- remaining reference methods -----------------------------------------------------
     @torch.no_grad()

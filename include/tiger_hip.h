@@ -342,6 +342,14 @@ typedef struct tg_model {
   /* GRUCell (update_modules.py:33): weight_ih [3d, msg], weight_hh [3d, d] */
   const float *gru_w_ih, *gru_w_hh, *gru_b_ih, *gru_b_hh;
   /* MergeUpdater (update_modules.py:43): MergeLayer fc1 [d, msg+d], fc2 [d, d] */
+  /* With the GRU updater (upd_fn == TG_UPD_GRU) these two are unused and NULL, and upd_fc2 may instead carry - optional,
+   * NULL = off, only together with attn_fused - the updater's memory-side weights FOLDED through the merger's fc2
+   * (tg_gru_fc2_fold): upd_fc2.w = Whh2 = W_hh W2 [3d, d], upd_fc2.b = bhh2 = W_hh b2 + b_hh [3d].  The left memory row a
+   * step stores is h = W2 t + b2 with t the output of the merger's fc1, so W_hh h + b_hh = Whh2 t + bhh2: with the fold
+   * a streaming step whose updater reads the left memory (upd_src = left) runs the updater on t and moves fc2 off the
+   * chain of dependent launches, onto the step's last launch (TG_FORM_FC2_DEFERRED).  A product of parameters: valid for
+   * exactly as long as attn_fused is, rebuilt with it.  (An existing slot, not a new field: the struct's layout and
+   * TG_ABI_VERSION stay what callers compiled against.) */
   tg_linear upd_fc1, upd_fc2;
   /* TemporalAttention (temporal_agg_modules.py:196-235) */
   const float *attn_wq, *attn_wk, *attn_wv; /* [2d,2d], [2d,2d+d_e], [2d,2d+d_e] */
@@ -412,6 +420,10 @@ size_t tg_attn_fused_floats(const tg_model* m);
 size_t tg_attn_fuse_workspace_bytes(const tg_model* m);
 int tg_attn_fuse(const tg_model* m, float* fused, void* ws, size_t ws_bytes, void* stream);
 int tg_attn_tile_applies(const tg_model* m);
+/* The fold a GRU model may carry in tg_model.upd_fc2: `fold` receives tg_gru_fc2_fold_floats(m) = 3d*d + 3d floats (0: no GRU
+ * updater) - Whh2, then bhh2 - each a float64 sum rounded once.  Reads gru_w_hh / gru_b_hh / attn_fc2 only. */
+size_t tg_gru_fc2_fold_floats(const tg_model* m);
+int tg_gru_fc2_fold(const tg_model* m, float* fold, void* stream);
 /* G rows of the listed nodes into m->g_table (see tg_model.g_table): n (<= *n_dev when given) node ids, state rows read as
  * the attention centres read them; ws: n * d floats. */
 int tg_attn_gtab_rows(const tg_model* m, int64_t n, const int64_t* nids, const int32_t* n_dev, void* ws, size_t ws_bytes,
@@ -468,6 +480,15 @@ typedef struct tg_gemm_probe {
   int32_t nbatch; int64_t a0_bs, w_bs, bias_bs, c_bs;
 } tg_gemm_probe;
 int tg_debug_gemm(const tg_gemm_probe* p, const char** form_out, void* stream);
+/* diagnostic: product `p` with the plain short-K product `second` (a0 dense rows, bias, no other feature; second->c_rows
+ * non-NULL: its [m_cap] SECOND-destination row list - rows >= 0 are also stored to second_c2, ldc2 = second->ldc) as the
+ * second product of the same launch, as the streaming step's last launch hosts the merger's fc2 (TG_FORM_FC2_DEFERRED).
+ * *hosted: 1 - one launch ran both; 0 - the launcher does not host a second product for these shapes: only `p` ran.
+ * rider_blocks > 0 (a multiple of 8): a stand-in for the collate rider takes that many workgroups behind the two products,
+ * as the step's last launch is laid out; rider workgroup b adds 0x10000 + b to the words i of rider_out[0, rider_n) with
+ * (i / 256) % rider_blocks == b (the caller zeroes them).  With a rider nothing runs unless *hosted comes back 1. */
+int tg_debug_gemm2(const tg_gemm_probe* p, const tg_gemm_probe* second, float* second_c2, int32_t* hosted,
+                   uint32_t* rider_out, int64_t rider_n, int32_t rider_blocks, void* stream);
 
 /* Its backward (the operator path under autograd): dx [n, in_f] = dy W (NULL: not wanted), dw [out_f, in_f] = dy^T x and
  * db [out_f] = column sums of dy (NULL: not wanted; overwritten, not accumulated).  in_f and out_f multiples of 4. */
@@ -479,6 +500,13 @@ int tg_linear_bwd(int64_t n, const float* x, int32_t in_f, const float* w, int32
  * x [n, xw] messages, h [n, d] old memory, out [n, d]. */
 int tg_gru_fwd(int64_t n, const float* x, int32_t xw, const float* h, int32_t d, const float* w_ih,
                const float* w_hh, const float* b_ih, const float* b_hh, float* out, void* stream);
+/* The same cell in the updater's BLEND form (TG_FORM_FC2_DEFERRED): the old memory of row p is h_p = w2 t[index[p]] + b2
+ * and is never formed; the memory-side products run on t through the fold (tg_gru_fc2_fold: whh2 [3d, d], bhh2 [3d]) and
+ * a fifth plane rebuilds h_p for the blend term.  t [*, d], index [n] rows of t (repeats allowed), w2 [d, d], b2 [d].
+ * TG_EUNSUPPORTED where the 16 x 16 updater kernel, the only one with this form, does not apply. */
+int tg_gru_blend_fwd(int64_t n, const float* x, int32_t xw, const float* t, const int64_t* index, int32_t d,
+                     const float* w_ih, const float* whh2, const float* b_ih, const float* bhh2, const float* w2,
+                     const float* b2, float* out, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* STEP 1-2: consume pending messages (tiger.py:208-221,292-356)              */
@@ -719,7 +747,8 @@ typedef struct tg_step_io {
    *   stream_len:      number of events in the resident stream arrays (a batch past the end is not prefetched: the
    *                    rider does nothing and the batch must not be run);
    *   *prefetch_state: HOST int, in / out.  In: 1 - the previous call on this workspace prefetched this batch and
-   *                    neither state, graph, offset nor workspace were touched since (the caller's promise); 2 - it
+   *                    neither state, graph, offset nor workspace were touched since, nor did the step leave the form
+   *                    TG_FORM_FC2_DEFERRED if the prefetching call had it (the caller's promise); 2 - it
    *                    prefetched, but that work must be discarded (the step then clears the dedup slots the prefetch
    *                    marked and collates itself; a step that cannot use a prefetch - not lean, no eager query rows -
    *                    treats 1 the same way); 0 - nothing was prefetched.  Out: 1 - this call prefetched the next
@@ -813,7 +842,18 @@ int tg_stream_step(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, vo
 #define TG_FORM_FUSED_WB 2 /* STEP 4-6 as one pass (possibly riding on the attention block's launches) */
 #define TG_FORM_LEAN 4     /* no involved / outdated sets are formed */
 #define TG_FORM_TABLES 8   /* reads and maintains g_table / c_table */
+#define TG_FORM_FC2_DEFERRED 16 /* four launches: the merger's fc2 (h, STEP 6's rows) is a second product of the step's
+                                 * last launch, STEP 5 reads the left memory itself (no pre-batch snapshot) and, with
+                                 * upd_src = left, the updater reads fc1's output through the fold in tg_model.upd_fc2.  Taken by
+                                 * lean table steps of one attention layer with msg_src = left and the GRU updater, no
+                                 * dropout / h_new / h_prev / lazy restart / caller's rider, B <= 16384, where fc1's launch
+                                 * hosts the write-back rider and the query-row launch the second product (TG_FC2_DEFER=0:
+                                 * never) */
 int32_t tg_stream_step_form(const tg_model* m, const tg_step_io* io);
+/* ... and the form the same fields give a step that carries dropout (dropout != 0: the training step's forward pass, which
+ * shares the step's code; such a step reads no per-node tables and defers nothing) - the decision code asked with the
+ * one term tg_stream_step_form fixes at "no dropout". */
+int32_t tg_stream_step_form2(const tg_model* m, const tg_step_io* io, int32_t dropout);
 
 /* ------------------------------------------------------------------------- */
 /* Training tail: STEP 7, backward pass, Adam            */

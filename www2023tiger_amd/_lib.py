@@ -19,6 +19,7 @@ TG_TRAJ_LAST, TG_TRAJ_MAX, TG_TRAJ_SUM = 0, 1, 2  # tg_trajectory_accumulate mod
 TG_TRAJ_ERR_BAD_ID = 1
 TG_RANK_MAX_K = 8  # tg_rank_stats: cut-offs per call
 TG_TOPK_MAX_K = 64  # tg_topk_rows: positions per row
+TG_FORM_FC2_DEFERRED = 16  # tiger_hip.h: bit of tg_stream_step_form
 TG_INVOLVED_MAX_K = 64  # tg_involved_list: sampler slots per query
 TG_WALK_MAX_FANOUT, TG_WALK_MAX_FRONTIER, TG_WALK_MAX_ENDPOINTS = 64, 1024, 2048  # tg_walk_candidates: the caps
 TG_WALK_EXCLUDE_SEEN, TG_WALK_KEEP_SELF = 1, 2  # tg_walk_candidates: flags
@@ -221,6 +222,8 @@ SIGNATURES = {
     'tg_consume_update_right_rows': (C.c_int, [P(TgModel), vp, vp, i64, vp, vp, vp, vp]),
     'tg_linear_fwd': (C.c_int, [i64, vp, i32, P(TgLinear), i32, i32, vp, vp]),
     'tg_debug_gemm': (C.c_int, [P(TgGemmProbe), P(C.c_char_p), vp]),
+    'tg_debug_gemm2': (C.c_int, [P(TgGemmProbe), P(TgGemmProbe), vp, P(i32), vp, i64, i32, vp]),
+    'tg_gru_blend_fwd': (C.c_int, [i64, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'tg_linear_bwd_workspace_bytes': (sz, [i32, i32]),
     'tg_linear_bwd': (C.c_int, [i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     'tg_gru_fwd': (C.c_int, [i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
@@ -261,6 +264,7 @@ SIGNATURES = {
     'tg_stream_step_zero_bytes': (sz, [P(TgModel), i64]),
     'tg_stream_step_zero_bytes2': (sz, [P(TgModel), i64, i32]),
     'tg_stream_step_form': (i32, [P(TgModel), P(TgStepIo)]),
+    'tg_stream_step_form2': (i32, [P(TgModel), P(TgStepIo), i32]),
     'tg_part_step': (C.c_int, [P(TgModel), P(TgTcsr), P(TgStepIo), P(TgPart), vp, sz, vp, sz, vp]),
     'tg_xchg_selftest': (C.c_int, [P(TgPart), i32, i32, vp, vp]),
     'tg_xchg_alloc': (C.c_int, [sz, P(vp)]),
@@ -275,6 +279,8 @@ SIGNATURES = {
     'tg_train_step': (C.c_int, [P(TgModel), P(TgTcsr), P(TgTrainIo), vp, sz, vp]),
     'tg_adam_step': (C.c_int, [vp, i32, i32, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
     'tg_attn_fused_floats': (sz, [P(TgModel)]),
+    'tg_gru_fc2_fold_floats': (sz, [P(TgModel)]),
+    'tg_gru_fc2_fold': (C.c_int, [P(TgModel), vp, vp]),
     'tg_attn_fuse_workspace_bytes': (sz, [P(TgModel)]),
     'tg_attn_fuse': (C.c_int, [P(TgModel), vp, vp, sz, vp]),
     'tg_attn_tile_applies': (C.c_int, [P(TgModel)]),

@@ -542,7 +542,7 @@ static int attn_forward_fused(const tg_model* m, int64_t Q, const int64_t* nids,
                               const int64_t* l1_nids, const int64_t* l1_eids, const float* l1_ts, const float* reprs,
                               const uint64_t* bm, const uint32_t* rank, float* out, const AttnWs& w, hipStream_t st,
                               tg_profiler* pf, const PosArgs* pos, const DirectArgs* da, bool centres_done,
-                              const float* key_rows, bool use_gtab, const WbRider* wbr, bool* wb_rode) {
+                              const float* key_rows, bool use_gtab, const WbRider* wbr, bool* wb_rode, GemmArgs* fc2_defer) {
   // stage numbering of the profiler is kept: q -> "merged q+g", g -> skipped, v/out -> skipped, fc1 -> fused
   int stage = ST_ATTN_PREP + 1;
   const int d = m->d;
@@ -609,7 +609,14 @@ static int attn_forward_fused(const tg_model* m, int64_t Q, const int64_t* nids,
   } else {
     wbr = nullptr;
   }
-  if (wb_on_fc1) {  // ... or rode on fc1's already: this product only stores STEP 6's rows (c2)
+  if (fc2_defer) {
+    // four-launch form: this product is not launched here - the caller runs it as the second product of the step's last
+    // launch.  The step took no snapshot for STEP 5, so the rider must have run on fc1's launch, as the caller foresaw
+    // (attn_fc1_hosts_rider: the same decision code)
+    if (!wb_on_fc1 || !g.c2) return TG_EINVAL;
+    *fc2_defer = g;
+    rode = true;
+  } else if (wb_on_fc1) {  // ... or rode on fc1's already: this product only stores STEP 6's rows (c2)
     if ((rc = gemm_launch(g, st)) != TG_OK) return rc;
     rode = true;
   } else if ((rc = gemm_launch(g, st, wbr, &rode)) != TG_OK) {
@@ -624,7 +631,7 @@ int attn_forward(const tg_model* m, int64_t Q, const int64_t* nids, const float*
                  const uint32_t* rank, float* out, const AttnWs& w, hipStream_t st, tg_profiler* pf,
                  const DropCfg* drop, const PosArgs* pos, const DirectArgs* da,
                  const float* key_rows, bool centres_done, bool use_gtab,
-                 const WbRider* wbr, bool* wb_rode) {
+                 const WbRider* wbr, bool* wb_rode, GemmArgs* fc2_defer) {
   if (wb_rode) *wb_rode = false;
   const DropCfg dc = drop ? *drop : DropCfg{};
   int stage = ST_ATTN_PREP;
@@ -632,7 +639,8 @@ int attn_forward(const tg_model* m, int64_t Q, const int64_t* nids, const float*
   const int d = m->d, d_e = m->d_e, kvw = 2 * d + d_e, nh = m->n_head, dh = 2 * d / nh, E = 2 * d;
   if (m->attn_fused && dc.p == 0.f)  // (the pre-multiplied weights do not care where the node part of a key row comes from)
     return attn_forward_fused(m, Q, nids, ts, l1_nids, l1_eids, l1_ts, reprs, bm, rank, out, w, st, pf, pos, da, centres_done,
-                              key_rows, use_gtab && m->g_table && !key_rows, wbr, wb_rode);
+                              key_rows, use_gtab && m->g_table && !key_rows, wbr, wb_rode, fc2_defer);
+  if (fc2_defer) return TG_EINVAL;  // (only the pre-multiplied block defers its last product)
   const int qblocks = (int)cdiv(2 * d, 4);
   if (da) {  // the constant half of the query projection from the rank-form kernel (no centre rows), then the direct centres
     hipLaunchKernelGGL(k_attn_centres, dim3(1 + qblocks), dim3(256), 0, st, (int64_t)0, d / 4, nids, (const float4*)reprs, bm,
@@ -747,13 +755,47 @@ __global__ void __launch_bounds__(256) k_scatter_rows(int64_t cap, const int32_t
   }
 }
 
+// the shape of fc1 / of the query-row product as far as the launchers' form decisions read it (no data pointers needed
+// beyond non-null markers)
+static GemmArgs fc1_shape(const tg_model* m, int64_t Q) {
+  const int d = m->d;
+  const FusedView f = fused_view(m, m->attn_fused);
+  GemmArgs g{};
+  g.m_cap = Q; g.n = d; g.k = f.nk + d;
+  g.a0 = ASeg{nullptr, f.nk, f.nk, nullptr};
+  g.a1 = ASeg{m->attn_fused, d, d, nullptr};
+  g.w = f.w1f; g.ldw = f.nk + d; g.bias = f.b1; g.bias2 = f.c1;
+  g.ldc = d; g.relu = 1; g.alpha = 1.f; g.nbatch = 1;
+  return g;
+}
+bool attn_fc1_hosts_rider(const tg_model* m, int64_t Q) {
+  if (!m->attn_fused) return false;
+  const GemmArgs g = fc1_shape(m, Q);
+  WbRider probe{};
+  bool rode = false;
+  return gemm_ks16_launch(g, nullptr, &probe, &rode, true) && rode;
+}
+static GemmArgs gtab_shape(const tg_model* m, int64_t cap, int64_t rows_hint, const int32_t* n_dev, const int32_t* rows32) {
+  const FusedView f = fused_view(m, m->attn_fused);
+  GemmArgs g{};
+  g.m_cap = cap; g.m_dev = n_dev; g.m_hint = rows_hint; g.n = f.nk; g.k = m->d;
+  g.w = f.wqk; g.ldw = m->d; g.bias = f.gconst; g.c = m->g_table; g.ldc = f.nk; g.c_rows = rows32; g.alpha = 1.f; g.nbatch = 1;
+  return g;
+}
+bool gtab_hosts_second(const tg_model* m, int64_t cap, int64_t rows_hint, const GemmArgs& second) {
+  if (!m->g_table || !m->attn_fused) return false;
+  GemmArgs g = gtab_shape(m, cap, rows_hint, nullptr, nullptr);
+  g.a0 = ASeg{m->g_table, m->d, m->d, nullptr};
+  return gemm_hosts_second(g, second);
+}
+
 int gtab_rows(const tg_model* m, int64_t cap, const int64_t* nids, const int32_t* rows32, const int32_t* n_dev, float* crows,
-              hipStream_t st, bool crows_ready, const CollateRider* collate, bool* rode, int64_t rows_hint) {
+              hipStream_t st, bool crows_ready, const CollateRider* collate, bool* rode, int64_t rows_hint,
+              const GemmArgs* second, bool* second_done) {
   if (rode) *rode = false;
   if (!m->g_table || !m->attn_fused || !m->pending_vals) return TG_EINVAL;
   if (m->row_of) return TG_EUNSUPPORTED;  // (rows32 are node ids)
   const int d = m->d;
-  const FusedView f = fused_view(m, m->attn_fused);
   if (!crows_ready) {  // (the GRU updater writes these rows itself, GruArgs.out2 - into the per-node table when there is one)
     hipLaunchKernelGGL(k_attn_centres_direct, dim3(flat_grid(cap * (d / 4), 256)), dim3(256), 0, st, *m, cap, nids,
                        (const float4*)m->nfeats, (float4*)crows, DirectArgs{}, PosArgs{});
@@ -761,12 +803,10 @@ int gtab_rows(const tg_model* m, int64_t cap, const int64_t* nids, const int32_t
       hipLaunchKernelGGL(k_scatter_rows, dim3(flat_grid(cap * (d / 4), 256)), dim3(256), 0, st, cap, n_dev, d / 4, nids,
                          (const float4*)crows, (float4*)m->c_table);
   }
-  GemmArgs g{};
-  g.m_cap = cap; g.m_dev = n_dev; g.m_hint = rows_hint; g.n = f.nk; g.k = d;
+  GemmArgs g = gtab_shape(m, cap, rows_hint, n_dev, rows32);
   // the centre rows: this launch's compact copy, or - gathered by node id - the rows of the per-node table
   g.a0 = m->c_table ? ASeg{m->c_table, d, d, nids} : ASeg{crows, d, d, nullptr};
-  g.w = f.wqk; g.ldw = d; g.bias = f.gconst; g.c = m->g_table; g.ldc = f.nk; g.c_rows = rows32; g.alpha = 1.f; g.nbatch = 1;
-  return gemm_launch(g, st, nullptr, rode, collate);
+  return gemm_launch(g, st, nullptr, rode, collate, second, second_done);
 }
 }  // namespace tg
 using namespace tg;

@@ -374,6 +374,9 @@ struct PosArgs {
   // (the winner of its node) or -1 - the scatter list of the product that writes h(t-) straight into the left memory
   // (write-back rider, below)
   int32_t* win_row;
+  // nullable: [2B] per winner slot, the node at the OTHER end of the winning event (the snapshot-free write-back reads that
+  // node's memory row for the message: one dependent round trip less than finding it through the batch arrays there)
+  int64_t* other;
 };
 // dedup slot of a node: its rank in the involved set, or (lean steps: no involved set) the node id itself
 __device__ __forceinline__ int64_t pos_slot(const PosArgs& a, int64_t node) {
@@ -421,6 +424,7 @@ __device__ __forceinline__ void pos_winners_pass(const PosArgs& a, int64_t tid, 
       a.upos[slot] = node;
       a.index[slot] = i;
       if (a.upos32) a.upos32[slot] = (int32_t)node;
+      if (a.other) a.other[slot] = a.nids3[i < a.B ? i + a.B : i - a.B];
     }
     if (a.win_row) a.win_row[i] = win ? (int32_t)node : -1;
   }
@@ -445,6 +449,12 @@ struct DirectArgs {
   // lean step (no outdated list): the invariants are checked per centre here and per neighbour in the core launch -
   // the same node set, involved & has-message, some nodes more than once
   int per_row_checks;
+  // snapshot-free write-back (snap == nullptr, msg_src = left; tg_step.h: StepWs.fc2_defer): STEP 5 reads the left memory
+  // rows itself, so this pass walks no rows for it - but it still takes the TIMES of the snapshot, snap_ts[i] for
+  // positions i < times_only of cat[src, dst] (one thread per position).  The write-back checks every position's event
+  // time against them (tiger.py:437-438) and cannot read the table for that: it stores the batch's times into it.  Either
+  // form of this pass therefore leaves what a snapshot-free write-back needs.
+  int64_t times_only;
 };
 // (`id`: the node's ROW in the state tables, state_row)
 __device__ __forceinline__ void check_msg_times(const tg_model& m, int64_t id, uint32_t* err) {
@@ -525,6 +535,8 @@ __device__ __forceinline__ void centres_direct_body(const tg_model& m, int64_t Q
       }
     }
   }
+  if (da.times_only > 0 && !da.snap)
+    for (int64_t i = tid; i < da.times_only; i += nth) da.snap_ts[i] = left_ts[state_row(m, ids.id(i))];
   if (da.outdated) {
     const int64_t no = min((int64_t)*da.n_outdated, da.cap);
     for (int64_t i = tid; i < no; i += nth) check_msg_times(m, da.outdated[i], da.err);
@@ -585,6 +597,7 @@ struct WritebackArgs {
   // snap[i] = message-source memory row (+ node features) of position i of cat[src, dst], snap_ts[i] its time
   const float* snap;
   const float* snap_ts;
+  const int64_t* other;  // snapshot-free form (snap == nullptr): PosArgs.other
   // lean step (no involved set): the dedup slots are indexed by node id - the slots of the batch's positive nodes are
   // zeroed, not a prefix - and counts[0], counts[1] are reported as -1
   int clean_best_by_pos;
@@ -765,13 +778,28 @@ __device__ __forceinline__ void writeback_body(const tg_model& m, const Writebac
 // ROWS6 = false: the VALUES of STEP 6 (left[v] <- h(t-), tiger.py:253-255) are written by somebody else - the epilogue of
 // the product that computes h (GemmArgs.c2) - and only its bookkeeping (time, flags, invariant) happens here; nothing
 // else in this pass depends on h, which is what lets it share that product's launch (WbRider).
-template <bool ROWS6>
+// chunk c of (left memory row + node features) of a node, as the snapshot holds it (centres_direct_body)
+__device__ __forceinline__ float4 left_row_nf(const float4* left, const float4* nf, int64_t id, int d4, int c) {
+  float4 v = left[id * d4 + c];
+  if (nf) {
+    const float4 f = nf[id * d4 + c];
+    v.x += f.x; v.y += f.y; v.z += f.z; v.w += f.w;
+  }
+  return v;
+}
+template <bool ROWS6, bool SNAP_FREE = false>
 __device__ __forceinline__ void writeback_fused_body(const tg_model& m, const WritebackArgs& a, unsigned bid, unsigned nblk) {
   const int lane = lane_id();
   const int wpb = blockDim.x / TG_WAVE;
   const int64_t B = a.B;
   const int64_t n = min((int64_t)*a.n_upos, 2 * B);
   const int64_t wave0 = (int64_t)bid * wpb + (threadIdx.x / TG_WAVE), nwave = (int64_t)nblk * wpb;
+  // SNAP_FREE (a.snap == nullptr; ROWS6 = false, msg_src = left only; an instance of its own, so that the snapshot form
+  // compiles to what it was): no launch between the centres pass and this one writes the
+  // left memory's rows - STEP 6's values leave a LATER launch - so STEP 5 reads the table rows (+ node features: the same
+  // float sum the snapshot holds).  The times still come from the centres pass (DirectArgs.times_only): this pass
+  // stores the batch's times into the table
+  constexpr bool snap_free = !ROWS6 && SNAP_FREE;
   for (int64_t i = wave0 * TG_WAVE + lane; i < 2 * B; i += nwave * TG_WAVE) {  // tiger.py:437-438 over all 2B positions
     const int64_t e = i < B ? i : i - B;
     if (a.snap_ts[i] > a.ts[e]) atomicOr(a.err, TG_ERR_EVENT_BEFORE_MEM);
@@ -779,6 +807,7 @@ __device__ __forceinline__ void writeback_fused_body(const tg_model& m, const Wr
   const int d4 = m.d / 4, e4 = m.d_e / 4;
   const int row4 = 3 * d4 + e4;
   const float4* snap = reinterpret_cast<const float4*>(a.snap);
+  const float4* nf = reinterpret_cast<const float4*>(m.nfeats);
   const float4* ef = reinterpret_cast<const float4*>(m.efeats);
   const float4* fq = reinterpret_cast<const float4*>(m.te_freq);
   const float4* ph = reinterpret_cast<const float4*>(m.te_phase);
@@ -795,18 +824,19 @@ __device__ __forceinline__ void writeback_fused_body(const tg_model& m, const Wr
     const int64_t other_pos = idx < B ? B + e : e;
     const bool consume = bm_test(m.has_msg, id);  // STEP 4 applies (wave-uniform)
     const float t = a.ts[e];
-    const float own_ts = a.snap_ts[idx];
     const int64_t eid = a.eids[e];
     const float mts = m.msg_ts[id], rts = m.right_ts[id], lts = m.left_ts[id];
+    const float own_ts = a.snap_ts[idx];
+    const int64_t oid = snap_free ? a.other[p] : 0;
     for (int c0 = 0; c0 < row4; c0 += TG_WAVE) {
       const int c = c0 + lane;
       float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), hv = pv, v = pv;
       if (c < d4) {
         if (consume) pv = pend[id * d4 + c];
         if (ROWS6) hv = hrow[idx * d4 + c];
-        v = snap[idx * d4 + c];
+        v = snap_free ? left_row_nf(left, nf, id, d4, c) : snap[idx * d4 + c];
       } else if (c < 2 * d4) {
-        v = snap[other_pos * d4 + (c - d4)];
+        v = snap_free ? left_row_nf(left, nf, oid, d4, c - d4) : snap[other_pos * d4 + (c - d4)];
       } else if (c < 2 * d4 + e4) {
         if (ef) v = ef[eid * e4 + (c - 2 * d4)];
       } else if (c < row4) {
@@ -872,6 +902,13 @@ __device__ __forceinline__ void writeback_fused_body(const tg_model& m, const Wr
 // of the winning positions a second time, into the left memory (GemmArgs.c2 / c2_rows = PosArgs.win_row): the step has no
 // write-back launch at all.  Hazards: nothing in the product's launch reads what the rider writes (right memory, mailbox,
 // has-message bits, times) or what the epilogue scatters (left memory: STEP 5 reads the snapshot, not the table).
+// Who writes left_vals, by form.  Five launches: the rider sits on fc1's launch (C2 sizes) or on fc2's, the epilogue of
+// fc2 - the step's third launch - stores STEP 6's rows, and STEP 5 reads the snapshot the centres pass took before either.
+// Four launches (tg_step.h: StepWs.fc2_defer): the rider is always on fc1's launch and fc2 is a second product of the
+// step's LAST launch, so between the previous step's last launch and this step's last launch nothing writes left_vals:
+// the rider's STEP 5 reads the table rows themselves (a.snap == nullptr, writeback_fused_body<false, true>), and the
+// centres pass that shares the last launch with fc2's stores reads no left_vals row at all (only the times, which the
+// rider wrote two launches earlier).
 struct WbRider {
   tg_model m;
   WritebackArgs a;
@@ -882,7 +919,8 @@ struct WbRider {
   int planned0;
   __device__ __forceinline__ void run(unsigned bid) const {
     if (planned0) writeback_body<0>(m, a, bid, blocks);
-    else writeback_fused_body<false>(m, a, bid, blocks);
+    else if (a.snap) writeback_fused_body<false>(m, a, bid, blocks);
+    else writeback_fused_body<false, true>(m, a, bid, blocks);
   }
 };
 

@@ -81,13 +81,20 @@ bool gemm_sk_partials(const GemmArgs& g, float* ws, size_t ws_floats, hipStream_
 // Launches the LDS-free K-split kernel for `g` (bias / activation applied: final values) and returns true, or returns
 // false (nothing launched) when the shape does not call for it (tg_gemm.hip: k_gemm_ks16).
 // rider (nullable): the write-back rider shares the launch (*rode tells whether)
-bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider = nullptr, bool* rode = nullptr);
+// dry: nothing is launched - the answer (and *rode) is what a real call with the same arguments would give
+bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider = nullptr, bool* rode = nullptr,
+                      bool dry = false);
 
 // Riders (nullable, one at most): work that shares the launch as its FIRST workgroups - the one-pass write-back (WbRider,
 // tg_common.h) or the collate part of the next batch (CollateRider, tg_sample.h).  Not every kernel hosts them: *rode
 // tells the caller whether the rider was launched - otherwise the caller launches that work itself.
+// second (nullable, with `collate` semantics of *rode: *second_done tells whether it was hosted): another plain short-K
+// product whose 64 x 64 tiles are taken by extra workgroups of the same launch, between the first product's blocks and the
+// riders (k_gemm_direct_r2).  Hosted only by the register-operand form; same per-tile arithmetic as a launch of its own.
 int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider = nullptr, bool* rode = nullptr,
-                const CollateRider* collate = nullptr);
+                const CollateRider* collate = nullptr, const GemmArgs* second = nullptr, bool* second_done = nullptr);
+// would gemm_launch(g, ., collate) host a second product `s` (host-side decision only, nothing is launched)
+bool gemm_hosts_second(const GemmArgs& g, const GemmArgs& s);
 
 struct GruArgs {
   int64_t cap;
@@ -112,7 +119,14 @@ struct GruArgs {
   // k-tiles [x_skip_at, x_skip_at + x_skip_n) of the message operand are known to be all zero (the edge-feature segment
   // of a raw mailbox row when there is no edge table, feature_getter.py:95-99): they are not loaded and not multiplied
   int x_skip_at, x_skip_n;
+  // Blend form (nullable; k_gru_direct16 only - gru_blend_ok): the memory operand is NOT the old memory row but the row t
+  // it is an affine image of, h = w_blend t + b_blend ([d, d], [d]).  The caller hands w_hh = W_hh w_blend and
+  // b_hh = W_hh b_blend + b_hh (tg_gru_fc2_fold), and a fifth accumulator plane over the memory-side k-tiles rebuilds h
+  // itself for the blend term (1 - z) n + z h.  add2 / out2 rows are then addressed by out_rows (h.idx lists rows of t).
+  const float *w_blend, *b_blend;
 };
+// the blend form needs the 16 x 16 LDS-free updater: would gru_launch take it for this capacity / row bound / width
+bool gru_blend_ok(int64_t cap, int64_t rows_hint, int d);
 
 int gru_launch(const GruArgs& g, hipStream_t st);  // (tg_gru.hip)
 

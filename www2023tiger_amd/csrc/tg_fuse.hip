@@ -83,6 +83,25 @@ __global__ void k_fuse_compact(int d, int de, int nh, const float* __restrict__ 
 
 static size_t attn_fused_floats_of(size_t d, size_t nk) { return nk * d + nk + d * (nk + d) + 2 * d; }
 
+// the fold of a GRU model's tg_model.upd_fc2: Whh2[r, j] = sum_k W_hh[r, k] W2[k, j]  (r < 3d, j < d), then bhh2[r] = sum_k W_hh[r, k] b2[k] + b_hh[r];
+// float64 sums, rounded once
+__global__ void k_fc2_fold(int d, const float* __restrict__ whh, const float* __restrict__ bhh, const float* __restrict__ w2,
+                           const float* __restrict__ b2, float* __restrict__ out) {
+  const int64_t n_w = (int64_t)3 * d * d, total = n_w + 3 * d;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    double acc = 0.0;
+    if (t < n_w) {
+      const int r = (int)(t / d), j = (int)(t - (int64_t)r * d);
+      for (int k = 0; k < d; ++k) acc += (double)whh[(int64_t)r * d + k] * (double)w2[(int64_t)k * d + j];
+    } else {
+      const int r = (int)(t - n_w);
+      for (int k = 0; k < d; ++k) acc += (double)whh[(int64_t)r * d + k] * (double)b2[k];
+      acc += (double)bhh[r];
+    }
+    out[t] = (float)acc;
+  }
+}
+
 }  // namespace tg
 
 using namespace tg;
@@ -91,6 +110,19 @@ extern "C" size_t tg_attn_fused_floats(const tg_model* m) {
   if (!attn_dims_ok(m)) return 0;
   const size_t d = m->d, nk = (size_t)m->n_head * (2 * d + (m->efeats ? m->d_e : 0));  // compact without an edge table
   return attn_fused_floats_of(d, nk);
+}
+
+extern "C" size_t tg_gru_fc2_fold_floats(const tg_model* m) {
+  if (!attn_dims_ok(m) || m->upd_fn != TG_UPD_GRU || !m->gru_w_hh || !m->gru_b_hh || !m->attn_fc2.w || !m->attn_fc2.b) return 0;
+  return (size_t)3 * m->d * m->d + (size_t)3 * m->d;
+}
+
+extern "C" int tg_gru_fc2_fold(const tg_model* m, float* fold, void* stream) {
+  const size_t n = tg_gru_fc2_fold_floats(m);
+  if (!n || !fold) return TG_EINVAL;
+  hipLaunchKernelGGL(k_fc2_fold, dim3((unsigned)std::min<size_t>(cdiv(n, 256), 1024)), dim3(256), 0, as_stream(stream), (int)m->d,
+                     m->gru_w_hh, m->gru_b_hh, m->attn_fc2.w, m->attn_fc2.b, fold);
+  return check_launch("tg_gru_fc2_fold");
 }
 
 // the one-launch attention tile is retired (tools/experiments/): kept for callers that still ask, always 0

@@ -1025,6 +1025,21 @@ __global__ void __launch_bounds__(256) k_gemm_direct_r(GemmArgs g, R r) {
   gemm_direct_block<NS, RW, CW>(g, blockIdx.x, own);
 }
 
+// ... and a second product `g2` of the same family beside the first: its 64 x 64 tiles (2 x 2 wave tiles, the instance a launch
+// of its own takes at these sizes - same chunk slots, same k order per lane, hence the same bits) are dealt to `own2`
+// workgroups behind the first product's, in front of the riders.  own and own2 are multiples of 8: both XCD maps are those
+// of the separate launches.  The two products are independent (neither reads what the other writes).
+template <class R, int NS, int RW, int CW>
+__global__ void __launch_bounds__(256) k_gemm_direct_r2(GemmArgs g, GemmArgs g2, unsigned own2, R r) {
+  const unsigned own = gridDim.x - r.blocks - own2;
+  if (blockIdx.x >= own + own2) {
+    r.run(blockIdx.x - own - own2);
+    return;
+  }
+  if (blockIdx.x >= own) gemm_direct_block<NS, 2, 2>(g2, blockIdx.x - own, own2);
+  else gemm_direct_block<NS, RW, CW>(g, blockIdx.x, own);
+}
+
 // ---- LDS-free K-split blocks for long-K products with few tiles ------------------------------------------------------
 // The merged value / out / fc1 product of the fused attention (C2: M = 3 072, N = 172, K = 1 204) has 144 tiles of 64 x 64
 // for 256 CUs; as stream-K pieces (below) it fills the chip but leaves its result in two or three pieces per element for
@@ -1263,7 +1278,18 @@ struct NoRider {  // (k_gemm_ks16 without riders)
   unsigned blocks;
   __device__ __forceinline__ void run(unsigned) const {}
 };
-bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode) {
+// diagnostic stand-in for a rider (tg_debug_gemm2): rider workgroup b of `blocks` stamps its share of out[0, n) - every
+// word exactly once if and only if the launch hands each rider its own index in [0, blocks)
+struct FillRider {
+  unsigned blocks;
+  uint32_t* out;
+  int64_t n;
+  __device__ __forceinline__ void run(unsigned bid) const {
+    for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < n; i += (int64_t)blocks * blockDim.x)
+      atomicAdd(out + i, 0x10000u + bid);
+  }
+};
+bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode, bool dry) {
   static const int knob = env_int("TG_GEMM_KS16", 1);
   if (rode) *rode = false;
   if (!knob || g.m_cap <= 0 || !plain_epilogue(g) || g.c_rows || g.c2 || (g.k % 4) || (g.a0.w % 4) || (g.ldw % 4) ||
@@ -1287,6 +1313,7 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
   gd.dbg = (gdbg16 && phase_selected(g)) ? 16 : 0;
   const NoRider nr{0u};
   if (ct != 3) {
+    if (dry) return true;
     // (rows per block: 16 when that fits the chip at once, else 32)
     const bool r1 = cdiv(g.m_cap, 16) * ntc <= 256;
     if (ct == 4) {
@@ -1310,6 +1337,10 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
     // rider as well and fc1 only gets longer: C1 13.1 -> 14.5 us)
     static const int here = env_int("TG_WB_RIDER_FC1", 1);  // tuning knob: 0 = on fc2
     if (here && rt == 3 && cdiv(g.m_cap, 48) * nt48 <= 256) {
+      if (dry) {
+        *rode = true;
+        return true;
+      }
       WbRider wr = *rider;
       const int64_t live = std::min<int64_t>(256, cdiv(g.m_cap, 16 * rt) * nt48);
       wr.blocks = rider_blocks(live, 256, 2 * wr.a.B);
@@ -1321,6 +1352,7 @@ bool gemm_ks16_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, b
       return true;
     }
   }
+  if (dry) return true;
   TG_FORM(knob == 8 ? "ks16<3,3,8>" : rt == 1 ? "ks16<1,3,4>" : rt == 2 ? "ks16<2,3,4>" : "ks16<3,3,4>");
   if (knob == 8) TG_KLAUNCH((k_gemm_ks16<NoRider, 3, 3, 8>), dim3(256), dim3(512), 0, st, gd, nr);
   else if (rt == 1) TG_KLAUNCH((k_gemm_ks16<NoRider, 1, 3, 4>), dim3(256), dim3(256), 0, st, gd, nr);
@@ -1408,15 +1440,68 @@ static unsigned rider_blocks(int64_t live, int threads, int64_t rows) {
 // launch has one group of 16 lanes per query); the centres are a gather with four elements per thread in flight
 static void collate_blocks(CollateRider& c) {
   const int64_t Q = 3 * c.s.B;
-  const int64_t sg = cdiv(Q, (int64_t)16), cg = cdiv(Q * (c.cr.m.d / 4), (int64_t)256);
+  // (a centres pass that neither copies centre rows nor takes the snapshot walks no rows: one thread per centre for its checks)
+  const bool walks = c.cr.out || c.cr.da.snap;
+  const int64_t sg = cdiv(Q, (int64_t)16), cg = walks ? cdiv(Q * (c.cr.m.d / 4), (int64_t)256) : 4 * cdiv(Q, (int64_t)256);
   c.sblocks = (unsigned)std::min<int64_t>(sg, 1024);
   c.cr.blocks = (unsigned)std::min<int64_t>(cdiv(cg, (int64_t)4), 512);
   c.blocks = (c.sblocks + c.cr.blocks + 7u) & ~7u;
   c.last = 1u;
 }
 
-int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode, const CollateRider* collate) {
+// the register-operand form (k_gemm_direct) for `g`: chunk slots per lane quarter and the 64 x 64 tiles of the estimated
+// live rows, or false.  One place for gemm_launch and for callers that must know the form before they launch.
+static bool direct_form(const GemmArgs& g, int* nsl_out, int64_t* tiles64_out) {
+  static const int dir_knob = env_int("TG_GEMM_DIRECT", 1);  // tuning knob: 0 = off
+  static const int64_t dir_tiles = env_int("TG_GEMM_DIRECT_TILES", 512);  // tuning knob
+  const int nsl = (int)cdiv(cdiv(g.k, 4), 4);  // chunk slots per lane quarter
+  const int64_t rows_e = g.m_hint > 0 ? std::min(g.m_hint, g.m_cap) : g.m_cap;
+  const bool plain_d = plain_epilogue(g) && !g.a1.p && !g.bias2 && (!g.c2 || !g.c_rows) && g.a0.w == g.k;
+  const int64_t tiles64 = cdiv(rows_e, 64) * cdiv(g.n, 64);
+  *nsl_out = nsl;
+  *tiles64_out = tiles64;
+  return dir_knob && plain_d && nsl <= 12 && tiles64 <= dir_tiles;
+}
+// a second product rides only where both are register-operand products of the same instance (NS <= 11: the instance that
+// hosts riders) and no earlier branch of gemm_launch claims the first: not the K-split family (K >= 320 at the least),
+// not the many-row forms (>= 4 096 blocks of 128 rows)
+bool gemm_hosts_second(const GemmArgs& g, const GemmArgs& s) {
+  int nsl = 0, nsl2 = 0;
+  int64_t t1 = 0, t2 = 0;
+  if (g.m_cap <= 0 || s.m_cap <= 0 || g.k >= 320 || s.k >= 320 || (g.k % 4) || (s.k % 4) || (g.ldw % 4) || (s.ldw % 4)) return false;
+  if (cdiv(g.m_cap, 128) * cdiv(g.n, 64) >= 4096 || s.c_rows) return false;
+  // (the K-split family is asked itself: its least K is a knob, and without a rider gemm_launch offers it the first product)
+  if (gemm_ks16_launch(g, nullptr, nullptr, nullptr, true)) return false;
+  if (!direct_form(g, &nsl, &t1) || !direct_form(s, &nsl2, &t2)) return false;
+  // (at most 256 tiles in the second product: the size at which a launch of its own takes the 2 x 2 wave tiles it gets here)
+  return nsl <= 11 && nsl2 <= 11 && (nsl <= 7) == (nsl2 <= 7) && t2 <= 256;
+}
+// one grid for `gd` (256 persistent blocks), `second` (blocks for its 64 x 64 tiles, a multiple of 8) and the rider's r.blocks
+template <class R>
+static void direct2_launch(const GemmArgs& gd, const GemmArgs& second, const R& r, int nsl, bool wide, hipStream_t st) {
+  GemmArgs gd2 = second;
+  gd2.dbg = 0;
+  const int64_t rows2 = gd2.m_hint > 0 ? std::min(gd2.m_hint, gd2.m_cap) : gd2.m_cap;
+  const unsigned own2 = (unsigned)std::min<int64_t>(256, 8 * cdiv(cdiv(rows2, 64) * cdiv(gd2.n, 64), 8));
+  const dim3 gr(256 + own2 + r.blocks);
+  if (nsl <= 7) {
+    TG_FORM(r.blocks ? (wide ? "direct<7,2x3>+direct<2x2>+rider" : "direct<7,2x2>+direct<2x2>+rider")
+                     : (wide ? "direct<7,2x3>+direct<2x2>" : "direct<7,2x2>+direct<2x2>"));
+    if (wide) TG_KLAUNCH((k_gemm_direct_r2<R, 7, 2, 3>), gr, dim3(256), 0, st, gd, gd2, own2, r);
+    else TG_KLAUNCH((k_gemm_direct_r2<R, 7, 2, 2>), gr, dim3(256), 0, st, gd, gd2, own2, r);
+  } else {
+    TG_FORM(r.blocks ? (wide ? "direct<11,2x3>+direct<2x2>+rider" : "direct<11,2x2>+direct<2x2>+rider")
+                     : (wide ? "direct<11,2x3>+direct<2x2>" : "direct<11,2x2>+direct<2x2>"));
+    if (wide) TG_KLAUNCH((k_gemm_direct_r2<R, 11, 2, 3>), gr, dim3(256), 0, st, gd, gd2, own2, r);
+    else TG_KLAUNCH((k_gemm_direct_r2<R, 11, 2, 2>), gr, dim3(256), 0, st, gd, gd2, own2, r);
+  }
+}
+
+int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* rode, const CollateRider* collate,
+                const GemmArgs* second, bool* second_done) {
   if (rode) *rode = false;
+  if (second_done) *second_done = false;
+  if (second && (!second_done || rider)) return TG_EINVAL;
   if ((rider || collate) && (!rode || (rider && collate))) return TG_EINVAL;
   if (g.c2 && (g.bias_rs || g.bias2 || g.row_valid || g.relu_mask || g.c_rows || g.accumulate || !g.c2_rows || g.nbatch != 1))
     return TG_EINVAL;  // the second destination exists in the plain epilogue only
@@ -1511,14 +1596,10 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
   }
   // short K and few (live) rows: whole operands in registers (see gemm_direct_tile).  Wave tiles of 32 x 32, or 32 x 48
   // when that brings the blocks of the estimated live rows under the CU count
-  static const int dir_knob = env_int("TG_GEMM_DIRECT", 1);  // tuning knob: 0 = off
   {
-    const int nsl = (int)cdiv(cdiv(g.k, 4), 4);  // chunk slots per lane quarter
-    const int64_t rows_e = g.m_hint > 0 ? std::min(g.m_hint, g.m_cap) : g.m_cap;
-    const bool plain_d = plain_epilogue(g) && !g.a1.p && !g.bias2 && (!g.c2 || !g.c_rows) && g.a0.w == g.k;
-    static const int64_t dir_tiles = env_int("TG_GEMM_DIRECT_TILES", 512);  // tuning knob
-    if (dir_knob && plain_d && nsl <= 12 && cdiv(rows_e, 64) * cdiv(g.n, 64) <= dir_tiles) {
-      const int64_t tiles64 = cdiv(rows_e, 64) * cdiv(g.n, 64);
+    int nsl = 0;
+    int64_t tiles64 = 0;
+    if (direct_form(g, &nsl, &tiles64)) {
       const bool wide = tiles64 > 256 && nsl <= 11;  // (32 x 48 wave tiles: 5 x 44 operand registers)
       const unsigned own = 256;
       const bool ride = nsl <= 11;  // (the K <= 192 instance hosts no riders)
@@ -1530,6 +1611,14 @@ int gemm_launch(const GemmArgs& g, hipStream_t st, const WbRider* rider, bool* r
         wr.last = 1u;
       } else {
         no_ride();
+      }
+      // a second product (see k_gemm_direct_r2) beside it, riders behind both
+      if (second && gemm_hosts_second(g, *second)) {
+        *second_done = true;
+        if (co.blocks) direct2_launch(gd, *second, co, nsl, wide, st);
+        else direct2_launch(gd, *second, NoRider{0u}, nsl, wide, st);
+        if (collate && ride) *rode = true;
+        return check_launch("gemm(direct + direct)");
       }
       const dim3 gr(own + co.blocks + wr.blocks);
 #define TG_DIRECT(NS_)                                                                                                  \
@@ -1672,5 +1761,36 @@ extern "C" int tg_debug_gemm(const tg_gemm_probe* p, const char** form_out, void
   else
     rc = gemm_launch(g, as_stream(stream));
   if (form_out) *form_out = t_gemm_form;
+  return rc;
+}
+
+extern "C" int tg_debug_gemm2(const tg_gemm_probe* p, const tg_gemm_probe* q, float* second_c2, int32_t* hosted,
+                              uint32_t* rider_out, int64_t rider_n, int32_t rider_blocks, void* stream) {
+  using namespace tg;
+  if (hosted) *hosted = 0;
+  if (!p || !q || !hosted || !p->a0 || !p->w || !p->c || !q->a0 || !q->w || !q->c) return TG_EINVAL;
+  if (p->k <= 0 || p->n <= 0 || (p->k % 4) || (p->a0_w % 4) || (p->ldw % 4) || p->nbatch != 1 || p->a0_w != p->k) return TG_EINVAL;
+  if (q->k <= 0 || q->n <= 0 || (q->k % 4) || (q->a0_w % 4) || (q->ldw % 4) || q->nbatch != 1 || q->a0_w != q->k) return TG_EINVAL;
+  if (p->a1 || q->a1 || q->a0_idx || q->m_dev || (q->c_rows && !second_c2)) return TG_EINVAL;
+  if (rider_blocks < 0 || rider_blocks > 1024 || (rider_blocks % 8) || (rider_blocks && (!rider_out || rider_n <= 0))) return TG_EINVAL;
+  GemmArgs g{}, s{};
+  g.m_cap = p->m_cap; g.m_dev = p->m_dev; g.m_hint = p->m_hint; g.n = p->n; g.k = p->k;
+  g.a0 = ASeg{p->a0, p->a0_ld, p->a0_w, p->a0_idx};
+  g.w = p->w; g.ldw = p->ldw; g.bias = p->bias; g.c_rows = p->c_rows; g.alpha = p->alpha; g.relu = p->relu;
+  g.c = p->c; g.ldc = p->ldc; g.nbatch = 1;
+  s.m_cap = q->m_cap; s.n = q->n; s.k = q->k; s.a0 = ASeg{q->a0, q->a0_ld, q->a0_w, nullptr};
+  s.w = q->w; s.ldw = q->ldw; s.bias = q->bias; s.alpha = q->alpha; s.relu = q->relu; s.c = q->c; s.ldc = q->ldc; s.nbatch = 1;
+  if (q->c_rows) { s.c2 = second_c2; s.c2_rows = q->c_rows; s.c2_m = q->m_cap; s.ldc2 = q->ldc; }
+  if (rider_blocks) {  // the grid gemm_launch forms with a collate rider, with the stand-in in the rider's place
+    int nsl = 0;
+    int64_t tiles64 = 0;
+    if (g.m_cap <= 0 || !gemm_hosts_second(g, s) || !direct_form(g, &nsl, &tiles64)) return TG_OK;
+    direct2_launch(g, s, FillRider{(unsigned)rider_blocks, rider_out, rider_n}, nsl, tiles64 > 256 && nsl <= 11, as_stream(stream));
+    *hosted = 1;
+    return check_launch("tg_debug_gemm2");
+  }
+  bool done = false;
+  const int rc = gemm_launch(g, as_stream(stream), nullptr, nullptr, nullptr, &s, &done);
+  *hosted = done ? 1 : 0;
   return rc;
 }

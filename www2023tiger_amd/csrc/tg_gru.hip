@@ -794,11 +794,13 @@ __global__ void __launch_bounds__(256) k_gru_direct(GruArgs g) {
 // in a reduce-scatter through LDS (k-group order: bit-reproducible).  Blocks are dealt to the XCDs in contiguous chunks of
 // the (row tile, column tile) sequence - balanced to within one block, and a row tile's gathered rows are fetched by one
 // XCD's L2, two at a chunk border.
-template <int RT>
+// BL: the blend form (GruArgs.w_blend): a fifth plane w_blend[j, :] . t over the memory-side k-tiles gives the old memory
+// value of the blend term instead of a load; everything else - tiles, k order, fold order - is the present form's.
+template <int RT, bool BL = false>
 __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, int64_t mt, int nt, float* sc_raw) {
-  constexpr int KS = 4;
+  constexpr int KS = 4, NP = BL ? 5 : 4;
   TG_PT(const unsigned long long pt_entry = (g.dbg & 16) ? __builtin_amdgcn_s_memtime() : 0ull;)  // (diagnostic, as in gemm_ks16_tile)
-  float (*sc)[KS - 1][4][RT][64] = reinterpret_cast<float (*)[KS - 1][4][RT][64]>(sc_raw);  // [owner][slot][plane][row tile]
+  float (*sc)[KS - 1][NP][RT][64] = reinterpret_cast<float (*)[KS - 1][NP][RT][64]>(sc_raw);  // [owner][slot][plane][row tile]
   const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int d = g.d, xw = g.xw;
@@ -816,6 +818,7 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
   }
   const float* wi = g.w_ih + (int64_t)jc * xw;
   const float* wh = g.w_hh + (int64_t)jc * d;
+  const float* wb = BL ? g.w_blend + (int64_t)jc * d : nullptr;
   const int64_t wi_ps = (int64_t)d * xw, wh_ps = (int64_t)d * d;  // plane strides
   // epilogue operands of the rows this wavefront finishes: accumulator register ks of every row tile (row 4 lk + ks)
   float hold[RT], addv[RT];
@@ -823,11 +826,12 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int64_t mm = min(m0 + 16 * rt + 4 * lk + ks, M - 1);
-    const int64_t node = g.h.idx ? g.h.idx[mm] : mm;
-    hold[rt] = g.h.p[node * g.h.ld + jc];
-    addv[rt] = (g.out2 && g.add2) ? g.add2[node * d + jc] : 0.f;
     orow[rt] = g.out_rows ? (int64_t)g.out_rows[mm] : mm;
+    const int64_t node = BL ? orow[rt] : (g.h.idx ? g.h.idx[mm] : mm);
+    hold[rt] = BL ? 0.f : g.h.p[node * g.h.ld + jc];
+    addv[rt] = (g.out2 && g.add2) ? g.add2[node * d + jc] : 0.f;
   }
+  const float bb = BL ? g.b_blend[jc] : 0.f;
   const float br = g.b_ih[jc] + g.b_hh[jc];
   const float bz = g.b_ih[d + jc] + g.b_hh[d + jc];
   const float bin = g.b_ih[2 * d + jc], bhn = g.b_hh[2 * d + jc];
@@ -841,7 +845,7 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
   const int n_my = nx + nh;
   auto tile_of = [&](int i) { return i < nx ? ks + 4 * i : th0 + 4 * (i - nx); };
   struct Tile {
-    float4 a[RT][2], w0[2], w1[2], w2[2];
+    float4 a[RT][2], w0[2], w1[2], w2[2], w3[BL ? 2 : 1];
   };
   auto load_tile = [&](int i, Tile& T, unsigned& live) {  // raw loads from clamped addresses (see k_gru_direct)
     const int t = tile_of(max(0, min(i, n_my - 1)));
@@ -869,10 +873,14 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
     for (int q = 0; q < 2; ++q) T.w1[q] = ldg4(wr + ps + kc[q]);
 #pragma unroll
     for (int q = 0; q < 2; ++q) T.w2[q] = ldg4(wr + 2 * ps + kc[q]);
-  };
-  f32x4m acc_r[RT], acc_z[RT], acc_in[RT], acc_hn[RT];
+    if constexpr (BL) {  // (message tiles: a valid address, the values are not used)
 #pragma unroll
-  for (int rt = 0; rt < RT; ++rt) acc_r[rt] = acc_z[rt] = acc_in[rt] = acc_hn[rt] = f32x4m{0.f, 0.f, 0.f, 0.f};
+      for (int q = 0; q < 2; ++q) T.w3[q] = ldg4(wb + (hp ? kc[q] : 0));
+    }
+  };
+  f32x4m acc_r[RT], acc_z[RT], acc_in[RT], acc_hn[RT], acc_hb[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) acc_r[rt] = acc_z[rt] = acc_in[rt] = acc_hn[rt] = acc_hb[rt] = f32x4m{0.f, 0.f, 0.f, 0.f};
   auto mma_tile = [&](auto hp_tag, const Tile& T, unsigned live) {
     constexpr bool HP = decltype(hp_tag)::value;
 #pragma unroll
@@ -896,6 +904,11 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
         for (int rt = 0; rt < RT; ++rt) {
           if (HP) acc_hn[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][j], b2[j], acc_hn[rt], 0, 0, 0);
           else acc_in[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][j], b2[j], acc_in[rt], 0, 0, 0);
+        }
+        if constexpr (BL && HP) {
+          const float b3[4] = {T.w3[q].x, T.w3[q].y, T.w3[q].z, T.w3[q].w};
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) acc_hb[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][j], b3[j], acc_hb[rt], 0, 0, 0);
         }
       }
     }
@@ -949,16 +962,17 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
         sc[v][slot][1][rt][lane] = acc_z[rt][v];
         sc[v][slot][2][rt][lane] = acc_in[rt][v];
         sc[v][slot][3][rt][lane] = acc_hn[rt][v];
+        if constexpr (BL) sc[v][slot][NP - 1][rt][lane] = acc_hb[rt][v];
       }
     }
   }
   __syncthreads();
   // partial sums are added in wavefront order 0..3 whichever wavefront owns the row (k_gru: a row's result must not
   // depend on its place in the tile)
-  float o_r[RT], o_z[RT], o_in[RT], o_hn[RT];
+  float o_r[RT], o_z[RT], o_in[RT], o_hn[RT], o_hb[RT];
 #pragma unroll
   for (int gsrc = 0; gsrc < KS; ++gsrc) {
-    float t_r[RT], t_z[RT], t_in[RT], t_hn[RT];
+    float t_r[RT], t_z[RT], t_in[RT], t_hn[RT], t_hb[RT];
     if (gsrc == ks) {  // wave-uniform
 #pragma unroll
       for (int v = 0; v < KS; ++v)
@@ -966,6 +980,7 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt) {
             t_r[rt] = acc_r[rt][v]; t_z[rt] = acc_z[rt][v]; t_in[rt] = acc_in[rt][v]; t_hn[rt] = acc_hn[rt][v];
+            t_hb[rt] = acc_hb[rt][v];
           }
         }
     } else {
@@ -974,6 +989,7 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
       for (int rt = 0; rt < RT; ++rt) {
         t_r[rt] = sc[ks][sl][0][rt][lane]; t_z[rt] = sc[ks][sl][1][rt][lane];
         t_in[rt] = sc[ks][sl][2][rt][lane]; t_hn[rt] = sc[ks][sl][3][rt][lane];
+        t_hb[rt] = BL ? sc[ks][sl][NP - 1][rt][lane] : 0.f;
       }
     }
 #pragma unroll
@@ -982,10 +998,12 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
       o_z[rt] = gsrc == 0 ? t_z[rt] : o_z[rt] + t_z[rt];
       o_in[rt] = gsrc == 0 ? t_in[rt] : o_in[rt] + t_in[rt];
       o_hn[rt] = gsrc == 0 ? t_hn[rt] : o_hn[rt] + t_hn[rt];
+      o_hb[rt] = gsrc == 0 ? t_hb[rt] : o_hb[rt] + t_hb[rt];
     }
   }
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
+    if constexpr (BL) hold[rt] = o_hb[rt] + bb;
     const int64_t m = m0 + 16 * rt + 4 * lk + ks;
     const float rg = fast_sigmoid(o_r[rt] + br);
     const float zg = fast_sigmoid(o_z[rt] + bz);
@@ -1012,9 +1030,9 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
 constexpr int GRU16_RT_MAX = 6;
 // RTM: the most rows / 16 this instance offers (3: 16 / 32 / 48 rows, 176 + 72 registers; 6: also 64 / 96, 254 + 144 - the
 // bigger register file costs the 48-row blocks 5 %, so launches whose bound fits 48-row blocks take the small instance)
-template <int RTM>
+template <int RTM, bool BL = false>
 __global__ void __launch_bounds__(256) k_gru_direct16(GruArgs g) {
-  __shared__ float sc_raw[4 * 3 * 4 * RTM * 64];
+  __shared__ float sc_raw[4 * 3 * (BL ? 5 : 4) * RTM * 64];
   int64_t M = g.cap;
   if (g.n_dev) M = min(M, (int64_t)*g.n_dev);
   if (M <= 0) return;
@@ -1035,11 +1053,11 @@ __global__ void __launch_bounds__(256) k_gru_direct16(GruArgs g) {
     if (b >= total) break;
     const int64_t mt = b / NT;
     const int nt = (int)(b - mt * NT);
-    if (rt == 1) gru_direct16_body<1>(g, M, mt, nt, sc_raw);
-    else if (rt == 2) gru_direct16_body<2>(g, M, mt, nt, sc_raw);
-    else if (RTM == 3 || rt == 3) gru_direct16_body<3>(g, M, mt, nt, sc_raw);
-    else if (rt == 4) gru_direct16_body<(RTM > 3 ? 4 : 3)>(g, M, mt, nt, sc_raw);
-    else gru_direct16_body<RTM>(g, M, mt, nt, sc_raw);
+    if (rt == 1) gru_direct16_body<1, BL>(g, M, mt, nt, sc_raw);
+    else if (rt == 2) gru_direct16_body<2, BL>(g, M, mt, nt, sc_raw);
+    else if (RTM == 3 || rt == 3) gru_direct16_body<3, BL>(g, M, mt, nt, sc_raw);
+    else if (rt == 4) gru_direct16_body<(RTM > 3 ? 4 : 3), BL>(g, M, mt, nt, sc_raw);
+    else gru_direct16_body<RTM, BL>(g, M, mt, nt, sc_raw);
     __syncthreads();  // the fold's LDS is re-used by the next tile
   }
 }
@@ -1048,9 +1066,21 @@ extern "C" int tg_debug_gru_trace(unsigned long long* out_host, int n_blocks) {
   return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_gru_trace), sizeof(unsigned long long) * 4 * n_blocks) == hipSuccess ? 0 : -4;
 }
 
+// the condition under which gru_launch takes k_gru_direct16 (below), for callers that must know before they launch
+static bool gru_d16_fits(int64_t cap, int64_t rows_hint, int d) {
+  const int64_t rows_b = rows_hint > 0 ? std::min<int64_t>(rows_hint, cap) : cap;
+  return cdiv(rows_b, 16 * GRU16_RT_MAX) * ((d + 15) / 16) <= 256;
+}
+bool gru_blend_ok(int64_t cap, int64_t rows_hint, int d) {
+  static const int force_nw = env_int("TG_GRU_NW", 0), d16_knob = env_int("TG_GRU_D16", 1);
+  return cap > 0 && force_nw == 0 && d16_knob && (d16_knob == 3 || gru_d16_fits(cap, rows_hint, d));
+}
+
 int gru_launch(const GruArgs& g, hipStream_t st) {
   if (g.cap <= 0) return TG_OK;
   if (g.d <= 0 || (g.d % 4) || g.xw <= 0 || (g.xw % 4)) return TG_EINVAL;
+  // the blend form exists in the 16 x 16 kernel only, without gate outputs (gru_blend_ok; a missing kernel is an error)
+  if (g.w_blend && (!g.b_blend || g.gates || !gru_blend_ok(g.cap, g.rows_hint, g.d))) return TG_EUNSUPPORTED;
   static const int dbg = env_int("TG_GRU_DBG", 0);  // bit 16: trace stamps
   static const int force_nw = env_int("TG_GRU_NW", 0);  // tuning knob
   GruArgs a = g;
@@ -1089,12 +1119,15 @@ int gru_launch(const GruArgs& g, hipStream_t st) {
     static const int d16_knob = env_int("TG_GRU_D16", 1);  // tuning knob: 0 = off, 3 = always
     const int64_t rows_b = g.rows_hint > 0 ? std::min<int64_t>(g.rows_hint, g.cap) : g.cap;
     const int NT16 = (g.d + 15) / 16;
-    if (force_nw == 0 && d16_knob && (d16_knob == 3 || cdiv(rows_b, 16 * GRU16_RT_MAX) * NT16 <= 256)) {
+    if (force_nw == 0 && d16_knob && (d16_knob == 3 || gru_d16_fits(g.cap, g.rows_hint, g.d))) {
       a.tail_blocks = 0;
       // (the sampler riders of the collate prefetch were tried here too - the sampler reads the graph only - and cost the
       // updater more than they saved the query-row launch: C2 updater +4.6 us, launch behind it -0.7 us; C4 +22 us)
       const dim3 grid16((unsigned)std::min<int64_t>(256, 8 * cdiv(cdiv(g.cap, 16) * NT16, 8)));
-      if (cdiv(rows_b, 48) * NT16 <= 256) TG_KLAUNCH(k_gru_direct16<3>, grid16, dim3(256), 0, st, a);
+      const bool rt3 = cdiv(rows_b, 48) * NT16 <= 256;
+      if (g.w_blend && rt3) TG_KLAUNCH((k_gru_direct16<3, true>), grid16, dim3(256), 0, st, a);
+      else if (g.w_blend) TG_KLAUNCH((k_gru_direct16<GRU16_RT_MAX, true>), grid16, dim3(256), 0, st, a);
+      else if (rt3) TG_KLAUNCH(k_gru_direct16<3>, grid16, dim3(256), 0, st, a);
       else TG_KLAUNCH(k_gru_direct16<GRU16_RT_MAX>, grid16, dim3(256), 0, st, a);
       return check_launch("gru(16 x 16)");
     }

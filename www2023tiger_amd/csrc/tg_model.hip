@@ -35,10 +35,16 @@ static size_t apply_ws_bytes(const tg_model* m, int64_t cap) {
   return b + 16;
 }
 
+// the updater's blend form (GruArgs.w_blend): row p's memory operand is row index[p] of t, h = attn_fc2(t) is never read
+struct GruBlend {
+  const float* t;
+  const int64_t* index;
+  const float *whh2, *bhh2;  // the fold a GRU model carries in tg_model.upd_fc2
+};
 int apply_messages(const tg_model* m, const int64_t* outdated, const int32_t* out_pos, const int32_t* n_dev,
                    int64_t cap, float* reprs, uint32_t* err, void* ws, size_t ws_bytes, hipStream_t st,
                    bool checked_already = false, float* gates = nullptr, int64_t rows_bound = 0, float* out2 = nullptr,
-                   const float* add2 = nullptr, bool out2_by_row = false) {
+                   const float* add2 = nullptr, bool out2_by_row = false, const GruBlend* blend = nullptr) {
   const int d = m->d, mw = 3 * m->d + m->d_e;
   Carver cv(ws, ws_bytes);
   ApplyWs w{};
@@ -82,8 +88,14 @@ int apply_messages(const tg_model* m, const int64_t* outdated, const int32_t* ou
     }
     a.rows_hint = std::min<int64_t>(cap, m->n_nodes);
     if (rows_bound > 0) a.rows_hint = std::min<int64_t>(a.rows_hint, rows_bound);  // the caller's bound on the live rows
+    if (blend) {
+      a.h = ASeg{blend->t, d, d, blend->index};
+      a.w_hh = blend->whh2; a.b_hh = blend->bhh2;
+      a.w_blend = m->attn_fc2.w; a.b_blend = m->attn_fc2.b;
+    }
     return gru_launch(a, st);
   }
+  if (blend) return TG_EINVAL;
   GemmArgs g{};  // MergeUpdater: fc2(relu(fc1([msg | mem])))
   g.m_cap = cap; g.m_dev = n_dev; g.n = d; g.k = mw + d; g.a0 = x; g.a1 = h;
   g.w = m->upd_fc1.w; g.ldw = mw + d; g.bias = m->upd_fc1.b; g.c = w.t2; g.ldc = d; g.relu = 1; g.alpha = 1.f; g.nbatch = 1;
@@ -233,6 +245,18 @@ extern "C" int tg_gru_fwd(int64_t n, const float* x, int32_t xw, const float* h,
   return gru_launch(a, as_stream(stream));
 }
 
+extern "C" int tg_gru_blend_fwd(int64_t n, const float* x, int32_t xw, const float* t, const int64_t* index, int32_t d,
+                                const float* w_ih, const float* whh2, const float* b_ih, const float* bhh2, const float* w2,
+                                const float* b2, float* out, void* stream) {
+  if (n < 0 || d <= 0 || (d % 4) || xw <= 0 || (xw % 4)) return TG_EINVAL;
+  if (n == 0) return TG_OK;
+  if (!x || !t || !index || !w_ih || !whh2 || !b_ih || !bhh2 || !w2 || !b2 || !out) return TG_EINVAL;
+  GruArgs a{};
+  a.cap = n; a.d = d; a.xw = xw; a.x = ASeg{x, xw, xw, nullptr}; a.h = ASeg{t, d, d, index};
+  a.w_ih = w_ih; a.w_hh = whh2; a.b_ih = b_ih; a.b_hh = bhh2; a.w_blend = w2; a.b_blend = b2; a.out = out; a.ldo = d;
+  return gru_launch(a, as_stream(stream));
+}
+
 extern "C" size_t tg_apply_messages_workspace_bytes(const tg_model* m, int64_t cap) {
   if (!attn_dims_ok(m) || cap < 0) return 0;
   return apply_ws_bytes(m, cap);
@@ -293,6 +317,7 @@ bool carve_step(const tg_model* m, int64_t B, Carver& cv, StepWs& w, int n_layer
   w.apply_bytes = apply_ws_bytes(m, cap);
   w.apply_ws = cv.take<char>(w.apply_bytes);
   w.best_id = cv.take<unsigned long long>((size_t)m->n_nodes);  // lean steps: dedup slots indexed by node id (kept zero)
+  w.other = cv.take<int64_t>((size_t)2 * B);
   if (n_layers == 2) {
     const size_t Q2 = (size_t)Q * K;
     w.h2n = cv.take<int64_t>(Q2 * K);
@@ -343,8 +368,32 @@ static WritebackArgs writeback_args(const tg_model* m, const tg_step_io* io, Ste
 // Which form a step takes: one place, shared by step_forward and tg_stream_step_form (the host asks before / after a step
 // whether the per-node tables are read and kept by it).
 struct StepForm {
-  bool direct, fused_wb, lean, gtab, lz_static;
+  bool direct, fused_wb, lean, gtab, lz_static, fc2_defer;
 };
+// rows bound the eager updater launch of a step runs with (step_writeback_b, apply_messages)
+static int64_t eager_rows_bound(const tg_model* m, const tg_step_io* io) {
+  const int64_t P = 2 * io->B;
+  return std::min<int64_t>(std::min<int64_t>(P, m->n_nodes), io->rows_hint > 0 ? io->rows_hint : P);
+}
+// the merger's fc2 over the Q centres as the pre-multiplied attention block forms it (shape fields only)
+static GemmArgs fc2_shape(const tg_model* m, int64_t Q) {
+  GemmArgs g{};
+  g.m_cap = Q; g.n = m->d; g.k = m->d;
+  g.a0 = ASeg{m->attn_fc2.w, m->d, m->d, nullptr};
+  g.w = m->attn_fc2.w; g.ldw = m->d; g.bias = m->attn_fc2.b; g.ldc = m->d; g.alpha = 1.f; g.nbatch = 1;
+  return g;
+}
+// TG_FORM_FC2_DEFERRED (tiger_hip.h): every term is known before the step's first launch, and the launchers are asked
+// with the very code that decides at launch time (attn_fc1_hosts_rider, gtab_hosts_second, gru_blend_ok)
+static bool fc2_defer_form(const tg_model* m, const tg_step_io* io, const StepForm& f, bool drop, bool inner) {
+  static const int knob = env_int("TG_FC2_DEFER", 1), wbr_knob = env_int("TG_WB_RIDER", 1);
+  if (!knob || !wbr_knob) return false;
+  if (!(f.direct && f.fused_wb && f.lean && f.gtab && m->c_table) || drop || inner || io->lazy) return false;
+  if (m->upd_fn != TG_UPD_GRU || m->msg_src != TG_SRC_LEFT || m->row_of) return false;
+  if (io->h_new || io->h_prev_left || io->h_prev_right || io->B > SIDE_MIN_B) return false;
+  if (m->upd_src == TG_SRC_LEFT && (!m->upd_fc2.w || !m->upd_fc2.b || !gru_blend_ok(2 * io->B, eager_rows_bound(m, io), m->d))) return false;
+  return attn_fc1_hosts_rider(m, 3 * io->B) && gtab_hosts_second(m, 2 * io->B, io->rows_hint, fc2_shape(m, 3 * io->B));
+}
 static StepForm step_form(const tg_model* m, const tg_step_io* io, bool eager, bool drop, bool inner) {
   StepForm f{};
   const tg_lazy_restart* lz = (io->lazy && !io->embed_only) ? io->lazy : nullptr;
@@ -366,6 +415,7 @@ static StepForm step_form(const tg_model* m, const tg_step_io* io, bool eager, b
   // kernel rewrites itself - their query rows are refreshed right behind it)
   f.gtab = eager && m->g_table && m->attn_fused && (!lz || (f.lz_static && m->c_table && f.lean)) && !inner && !io->embed_only &&
            !io->collate_only && !drop;
+  f.fc2_defer = fc2_defer_form(m, io, f, drop, inner);
   return f;
 }
 
@@ -409,7 +459,11 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   static const int wbr_knob = env_int("TG_WB_RIDER", 1);
   // (not with io->h_new: those rows are read from the tables after the attention block, i.e. before STEP 4 must run)
   const bool want_rider = w.fused_wb && wbr_knob != 0 && !drop && !io->h_new;
+  // four launches (TG_FORM_FC2_DEFERRED; not with a caller's rider): no snapshot for STEP 5, fc2 leaves the chain
+  w.fc2_defer = form.fc2_defer && !w.ext_rider;
+  w.fc2 = GemmArgs{};
   if (want_rider) pos.win_row = w.win_row;
+  if (want_rider && w.fc2_defer) pos.other = w.other;
   const PosArgs* pp = (io->embed_only && !untouched) ? nullptr : &pos;
   w.gtab = form.gtab;
   // collate prefetch (tg_step_io.prefetch_state): this step runs the NEXT batch's sampler + centres on its last launch;
@@ -418,6 +472,8 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   w.prefetch = pf_knob != 0 && io->prefetch_state && io->stream_len > 0 && io->offset_dev && io->advance && io->ws_is_clean &&
                w.lean && w.gtab && w.fused_wb && !lz && io->strategy == 0 && K <= 16 && !io->l1_nids && !io->l1_eids && !io->l1_ts &&
                B <= SIDE_MIN_B;  // (large batches: the last product's launch takes no riders, see gemm_launch)
+  // (a batch prefetched by a step of the five-launch form serves this form too - its snapshot is simply not read; the
+  // reverse does not hold, see tg_step_io.prefetch_state)
   const int pf_in = io->prefetch_state ? *io->prefetch_state : 0;
   const bool prefetched = w.prefetch && pf_in == 1;
   if (io->prefetch_state) *io->prefetch_state = 0;  // set again by the end of the step, once the rider is enqueued
@@ -429,8 +485,9 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
       return TG_EHIP;
     }
   }
-  DirectArgs da{w.lean ? nullptr : w.outdated, w.counts + 1, cap, io->err, w.fused_wb ? (float4*)w.snap : nullptr,
-                w.snap_ts, 2 * B, w.lean ? 1 : 0};
+  DirectArgs da{w.lean ? nullptr : w.outdated, w.counts + 1, cap, io->err,
+                (w.fused_wb && !w.fc2_defer) ? (float4*)w.snap : nullptr, w.snap_ts, 2 * B, w.lean ? 1 : 0,
+                w.fc2_defer ? 2 * B : 0};
   // lean: the centres need nothing the sampler produces and share its launch
   // (with the per-node table of centre rows - tg_model.c_table, a step that uses the query-row table - no per-batch copy
   // of the centre rows is made: the centres pass keeps its checks, the first dedup pass and the snapshot)
@@ -527,12 +584,13 @@ int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, Step
   if (want_rider) {
     wbr.m = *m;
     wbr.a = writeback_args(m, io, w);
-    wbr.a.snap = w.snap;
+    wbr.a.snap = w.fc2_defer ? nullptr : w.snap;  // (nullptr: STEP 5 reads the left memory itself)
     wbr.a.snap_ts = w.snap_ts;
+    wbr.a.other = w.other;
   }
   if ((rc = attn_forward(m, Q, w.nids3, w.ts3f, w.l1n, w.l1e, w.l1t, w.reprs, w.bm, w.rank, io->h, w.attn, st, pf,
                          drop, pp, w.direct ? &da : nullptr, key_rows, w.lean && io->strategy == 0 && !lz, w.gtab,
-                         want_rider ? &wbr : w.ext_rider, &w.wb_rode)) != TG_OK)
+                         want_rider ? &wbr : w.ext_rider, &w.wb_rode, w.fc2_defer ? &w.fc2 : nullptr)) != TG_OK)
     return rc;
   prof_mark(pf, ST_DEDUP, st);
   // h(t'+) rows of cat[src, dst]: reprs[local(node)], or the table rows themselves
@@ -636,9 +694,13 @@ int step_writeback_b(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, 
     }
     const bool ctab = cr && m->c_table;  // ... or straight into the per-node table of centre rows
     KSlot ks_upd(KT_UPDATER);
+    // four-launch form, upd_src = left: the left rows of the positive nodes (STEP 6) are not stored yet - they are fc2 of
+    // the rows index[p] of fc1's output, and the updater reads those through the folded weights
+    const GruBlend blend{w.attn.t, w.index, m->upd_fc2.w, m->upd_fc2.b};
+    const bool use_blend = w.fc2_defer && m->upd_src == TG_SRC_LEFT;
     if ((rc = apply_messages(m, w.upos, w.upos32, n_upos, P, m->pending_vals, io->err, w.apply_ws, w.apply_bytes, st,
                             true, nullptr, bound, cr ? (ctab ? m->c_table : w.attn.t) : nullptr, cr ? m->nfeats : nullptr,
-                            ctab)) != TG_OK)
+                            ctab, use_blend ? &blend : nullptr)) != TG_OK)
       return rc;
   }
   prof_mark(pf, ST_GTAB, st);
@@ -646,9 +708,11 @@ int step_writeback_b(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, 
     // ... and the query rows of the same nodes: their effective rows have just changed (tg_model.g_table)
     bool rode = false;
     KSlot ks_q(KT_QROWS);
+    bool fc2_done = false;
     if ((rc = gtab_rows(m, 2 * io->B, w.upos, w.upos32, n_upos, w.attn.t, st, m->upd_fn == TG_UPD_GRU,
-                        w.prefetch ? &co : nullptr, &rode, io->rows_hint)) != TG_OK)
+                        w.prefetch ? &co : nullptr, &rode, io->rows_hint, w.fc2_defer ? &w.fc2 : nullptr, &fc2_done)) != TG_OK)
       return rc;
+    if (w.fc2_defer && !fc2_done) return TG_EINVAL;  // (fc2_defer_form asked the same launcher)
     if (w.prefetch && !rode) {  // this product's kernel does not host riders: the same work as a launch of its own
       collate_blocks_standalone(co);
       hipLaunchKernelGGL(k_collate, dim3(co.blocks), dim3(256), 0, st, co);
@@ -661,11 +725,12 @@ int step_writeback_b(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, 
 }
 }  // namespace tg
 
-extern "C" int32_t tg_stream_step_form(const tg_model* m, const tg_step_io* io) {
+extern "C" int32_t tg_stream_step_form(const tg_model* m, const tg_step_io* io) { return tg_stream_step_form2(m, io, 0); }
+extern "C" int32_t tg_stream_step_form2(const tg_model* m, const tg_step_io* io, int32_t dropout) {
   if (!m || !io) return 0;
-  const tg::StepForm f = tg::step_form(m, io, m->pending_vals != nullptr, false, io->inner != nullptr);
+  const tg::StepForm f = tg::step_form(m, io, m->pending_vals != nullptr, dropout != 0, io->inner != nullptr);
   return (f.direct ? TG_FORM_DIRECT : 0) | (f.fused_wb ? TG_FORM_FUSED_WB : 0) | (f.lean ? TG_FORM_LEAN : 0) |
-         (f.gtab ? TG_FORM_TABLES : 0);
+         (f.gtab ? TG_FORM_TABLES : 0) | (f.fc2_defer ? TG_FORM_FC2_DEFERRED : 0);
 }
 
 namespace tg {

@@ -51,6 +51,7 @@ struct StepWs {
   int64_t *l1_nids, *l1_eids;
   int32_t* out_pos;
   int32_t* upos32;
+  int64_t* other;    // [2B] per winner slot: the node at the other end of the winning event (PosArgs.other)
   int32_t* win_row;  // [2B] per position of cat[src, dst]: its node if the position wins the node's dedup, else -1 (write-back rider)
   bool wb_rode;      // STEP 4-6 rode on the launch of the attention block's last product: no write-back launch
   float *snap, *snap_ts;  // one-launch write-back: message-source rows (+ node features) / times of cat[src, dst], pre-batch
@@ -79,6 +80,11 @@ struct StepWs {
   float *h2t, *ts2, *emb2;
   AttnWs attn2;
   const WbRider* ext_rider;  // tg_part_step: the planned write-back's first launch rides on the embedding step's fc1 / fc2
+  // Four-launch form (tiger_hip.h: TG_FORM_FC2_DEFERRED).  fc2_defer: decided by step_forward before anything is launched
+  // (no snapshot is taken for this batch's STEP 5); fc2: the merger's fc2 product as the attention block left it, unlaunched
+  // - step_writeback_b hands it to the query-row launch as its second product
+  bool fc2_defer;
+  GemmArgs fc2;
 };
 // tg_stream_step with a rider handed in by the caller (tg_part_step; *rode: whether a launch of the step hosted it)
 int stream_step_ext(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, void* ws, size_t ws_bytes, hipStream_t st,
@@ -96,12 +102,16 @@ int attn_forward(const tg_model* m, int64_t Q, const int64_t* nids, const float*
                  const uint32_t* rank, float* out, const AttnWs& w, hipStream_t st, tg_profiler* pf = nullptr,
                  const DropCfg* drop = nullptr, const PosArgs* pos = nullptr, const DirectArgs* da = nullptr,
                  const float* key_rows = nullptr, bool centres_done = false, bool use_gtab = false,
-                 const WbRider* wbr = nullptr, bool* wb_rode = nullptr);
+                 const WbRider* wbr = nullptr, bool* wb_rode = nullptr, GemmArgs* fc2_defer = nullptr);
+// the merged fc1 product of the fused attention block over Q centres: does its launch host the write-back rider
+bool attn_fc1_hosts_rider(const tg_model* m, int64_t Q);
+// the query-row product of gtab_rows(m, cap, .., rows_hint) with a collate rider: would it host `second` beside it
+bool gtab_hosts_second(const tg_model* m, int64_t cap, int64_t rows_hint, const GemmArgs& second);
 void centre_rows_launch(const tg_model* m, int64_t n, const int64_t* nids, const float* reprs, const uint64_t* bm,
                         const uint32_t* rank, float* out, bool direct, hipStream_t st);
 int gtab_rows(const tg_model* m, int64_t cap, const int64_t* nids, const int32_t* rows32, const int32_t* n_dev, float* crows,
               hipStream_t st, bool crows_ready, const CollateRider* collate = nullptr, bool* rode = nullptr,
-              int64_t rows_hint = 0);
+              int64_t rows_hint = 0, const GemmArgs* second = nullptr, bool* second_done = nullptr);
 // collate + STEP 1-3 (+ io->h_new); `gates` (nullable) receives the GRU gate activations
 // eager: take the outdated nodes' rows from m->pending_vals instead of running the updater (tg_stream_step only)
 int step_forward(const tg_model* m, const tg_tcsr* g, const tg_step_io* io, StepWs& w, float* gates, hipStream_t st,

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import hip_ops
-from .._lib import TG_TOPK_MAX_K, TgLazyRestart, TgLinear, TgModel, TgStepIo, check, lib, ptr
+from .._lib import TG_FORM_FC2_DEFERRED, TG_TOPK_MAX_K, TgLazyRestart, TgLinear, TgModel, TgStepIo, check, lib, ptr
 from ..hip_ops import stream_ptr
 from .basic_modules import MergeLayer
 from .memory import Memory, MessageStoreNoGradLastOnly
@@ -309,6 +309,7 @@ class TIGE(nn.Module):
         self._struct_cache = None
         self._fused = None
         self._fused_l1 = None
+        self._fc2_fold = None
         self._pending = None
         self._pending_stamp = None
         self._step_ws = {}
@@ -373,6 +374,9 @@ class TIGE(nn.Module):
         if self.mem_update_type == 'gru':
             c = self.right_mem_updater.cell
             gru = [ptr(c.weight_ih), ptr(c.weight_hh), ptr(c.bias_ih), ptr(c.bias_hh)]
+            fold = getattr(self, '_fc2_fold', None)  # (tiger_hip.h: the GRU model's use of the upd_fc2 slot)
+            if fold is not None:
+                fc2 = TgLinear(ptr(fold), ptr(fold[3 * self.memory_dim * self.memory_dim:]))
         else:
             fc1, fc2 = lin(self.right_mem_updater.fn.fc1), lin(self.right_mem_updater.fn.fc2)
         L, R, S = self.left_memory, self.right_memory, self.msg_store
@@ -593,6 +597,7 @@ class TIGE(nn.Module):
         ignores the fused weights."""
         self._fused = None
         self._fused_l1 = None
+        self._fc2_fold = None
         self._struct_cache = None
         if not enable:
             return self
@@ -609,6 +614,13 @@ class TIGE(nn.Module):
             blobs.append(fused)
         self._fused = blobs[0]
         self._fused_l1 = blobs[1] if len(blobs) > 1 else None
+        # the updater's memory-side weights folded through the merger's fc2 (tg_model.upd_fc2 of a GRU model): same life as the blob
+        m = self.model_struct()
+        n = int(lib.tg_gru_fc2_fold_floats(C.byref(m))) if self.n_layers == 1 else 0
+        if n:
+            fold = torch.empty(n, dtype=torch.float32, device=self.device)
+            check(lib.tg_gru_fc2_fold(C.byref(m), ptr(fold), stream_ptr(self.device)), 'tg_gru_fc2_fold')
+            self._fc2_fold = fold
         self._fused_stamp = self._attn_stamp()
         self._struct_cache = None
         return self
@@ -1536,7 +1548,11 @@ class TIGE(nn.Module):
         m = self.model_struct()
         pf = bool(buf.io.prefetch_state)
         if pf:  # is the collate part this buffer's previous step prefetched still the one this step needs?
-            if buf._pf_state.value == 1 and buf._pf_stamp != self._prefetch_stamp(buf, g):
+            # (a batch prefetched by a step of the four-launch form carries no pre-batch snapshot: only such a step may use
+            # it.  The form is a function of the struct and the io fields as they stand now: asked once per step)
+            defer = bool(lib.tg_stream_step_form(C.byref(m), C.byref(buf.io)) & TG_FORM_FC2_DEFERRED)
+            lost_form = getattr(buf, '_pf_defer', False) and not defer
+            if buf._pf_state.value == 1 and (buf._pf_stamp != self._prefetch_stamp(buf, g) or lost_form):
                 if os.environ.get('TG_PF_DEBUG'):
                     print('prefetch discarded:', buf._pf_stamp, '->', self._prefetch_stamp(buf, g), flush=True)
                 buf._pf_state.value = 2  # made, but for another state / offset / graph: the step discards it
@@ -1548,6 +1564,7 @@ class TIGE(nn.Module):
             if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
                 buf._pf_state.value = before  # nothing ran: the device is where it was before the capturing call
             buf._pf_stamp = self._prefetch_stamp(buf, g)
+            buf._pf_defer = defer
         if (buf.io.lazy and getattr(self, '_gtab', None) is not None
                 and not (lib.tg_stream_step_form(C.byref(m), C.byref(buf.io)) & 8)):
             self._gtab_stamp = None  # the in-step restart loop re-initialised rows the tables did not follow

@@ -22,6 +22,9 @@ window") answer from less history, and the two lines may differ.
 names (`TIGE.forget(..., release_edge_rows=True, keep_from=first eid not observed yet)`), the eids of the events still
 to come are shifted by the returned `shift`, and the table's rows before and after are printed per batch.  The model
 computes what it would have computed, so the equality of the two lines holds under the same conditions.
+--grow lets the model itself start small: its tables and its graph cover the node ids of train + validation only, and the
+ids the test split brings are admitted batch by batch (`TIGE.observe(..., num_node='auto', nfeats=...)`); the ids admitted
+are printed per batch.  Each batch is ranked among the items known at that moment, so there is no offline line beside it.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -126,17 +129,23 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     return ids, scores, out
 
 
-def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest):
+def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None):
     """recommend, then `ingest`, batch by batch over the test split -> (ids [n_test, k], dict of the metrics of
-    eval_recommendation: position of the true destination in its list, folded the same way)"""
+    eval_recommendation: position of the true destination in its list, folded the same way).  known: a callable -> the
+    (catalogue, col_of) of the batch, for a model whose node ids grow on the way (run_online(grow=True))"""
     dev = model.device
     ids, pos = [], []
     place = torch.arange(k, device=dev)
     for lo in range(0, len(test.src), bs):
         src, dst, ts, eids = (np.ascontiguousarray(getattr(test, f)[lo:lo + bs]) for f in ('src', 'dst', 'ts', 'eids'))
         q, t, d = torch.from_numpy(src).to(dev), torch.from_numpy(ts.astype(np.float64)).to(dev), torch.from_numpy(dst).to(dev)
+        if known is not None:
+            catalogue, col_of = known()
+            q = q.clamp(max=model.n_nodes - 1)   # a source nobody has seen yet is asked for as the last id (and scores as a miss)
         i, _, _ = model.recommend(q, t, catalogue, k, exclude_seen=exclude_seen, col_of=col_of)
         hit = (i == d[:, None]) & (i != 0)
+        if known is not None:
+            hit &= torch.from_numpy(src).to(dev)[:, None] < model.n_nodes
         pos.append(torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1))
         ids.append(i)
         ingest(src, dst, ts.astype(np.float64), eids)
@@ -149,7 +158,7 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest):
 
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-               device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True):
+               device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -159,7 +168,14 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     release_edge_rows=True, keep_from=first eid not observed yet)`); the eids of the events still to come are shifted by
     the returned `shift`, and the online metrics carry 'rows': (table rows before, after) per batch.  What the model
     computes does not change, so the equality above holds under the same conditions.
-    offline=False: the online replay alone -> (its metrics, None)."""
+    offline=False: the online replay alone -> (its metrics, None).
+    grow: the model itself starts small - its tables and its graph cover the ids of train + validation only (num_node =
+    their largest id + 1; the checkpoint's per-node rows beyond it are cut off, they are zeros) - and admits the ids the
+    test split brings, batch by batch, through `observe(..., num_node='auto', nfeats=their feature rows)`.  Each batch is
+    ranked among the items the model knows at that moment, so the lists differ from the offline replay's (which ranks
+    items nobody has seen as well) and no offline replay is made; the metrics carry 'admitted': new ids per batch.  Data
+    without a node-feature file get a zero table (the same model: a missing table means zeros).  Needs the sequence
+    restarter."""
     from www2023tiger_amd.data.graph import Graph
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -167,14 +183,35 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         data, root, seed, num_workers=0, bs=bs, warmup_steps=0, subset=1.0, strategy=strategy, n_layers=1,
         n_neighbors=n_neighbors, restarter_type=restarter_type, hist_len=hist_len, device=device)
     nfeats, efeats, full_data, test = basic[0], basic[1], basic[2], basic[5]
-    model = init_model(nfeats, efeats, train_graph, full_graph, full_data, device, dim=dim, n_layers=1, n_heads=n_heads,
-                       n_neighbors=n_neighbors, hit_type=hit_type, dropout=0.0, restarter_type=restarter_type,
+    n_seen = len(full_data.src) - len(test.src)   # the test split is the tail of the stream
+    seen = lambda: Graph.from_arrays(full_data.src[:n_seen], full_data.dst[:n_seen], full_data.ts[:n_seen],
+                                     full_data.eids[:n_seen], strategy=full_graph.strategy, seed=seed,
+                                     max_node_id=n0 - 1, device=device)
+    n0 = full_graph.num_node
+    state = torch.load(ckpt_path, map_location=device)
+    if grow:
+        n0 = int(max(full_data.src[:n_seen].max(), full_data.dst[:n_seen].max())) + 1
+        width = dim if dim is not None else (efeats.shape[1] if efeats is not None else None)
+        if nfeats is None and width is None:
+            raise ValueError('grow: the data have neither a node nor an edge table to take the feature width from: give dim')
+        nfeats = np.zeros((full_graph.num_node, width), dtype=np.float32) if nfeats is None else nfeats
+        n_full, offline = full_graph.num_node, False
+        train_graph = full_graph = seen()   # (the model is built on the ids seen so far)
+        # per-node rows of the checkpoint (memories; a model trained on the full id space) beyond the ids seen so far
+        per_node = [key for key, v in state.items()
+                    if v.dim() and v.shape[0] == n_full and key.split('.')[0].endswith('_memory')]
+        for key in per_node:
+            if bool(state[key][n0:].any()):   # (e.g. a checkpoint saved after a pass over the test split)
+                raise ValueError(f'grow: {key} of the checkpoint holds state for node ids beyond {n0 - 1}, which train + '
+                                 'validation never name; cutting its rows off would drop it')
+            state[key] = state[key][:n0]
+    model = init_model(nfeats[:n0] if grow else nfeats, efeats, train_graph, full_graph, full_data, device, dim=dim, n_layers=1,
+                       n_heads=n_heads, n_neighbors=n_neighbors, hit_type=hit_type, dropout=0.0, restarter_type=restarter_type,
                        hist_len=hist_len, msg_src=msg_src, upd_src=upd_src, msg_tsfm_type='id', mem_update_type='gru')
-    model.load_state_dict(torch.load(ckpt_path, map_location=device))
+    model.load_state_dict(state)
     model.eval()
     catalogue = torch.from_numpy(np.unique(full_data.dst).astype(np.int64)).to(device)
-    col_of = hip_ops.catalogue_index(catalogue, model.n_nodes)
-    n_seen = len(full_data.src) - len(test.src)   # the test split is the tail of the stream
+    col_of = None if grow else hip_ops.catalogue_index(catalogue, model.n_nodes)
     start = model.save_memory_state()
     with torch.no_grad():
         ids_off = None
@@ -184,16 +221,32 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                                        lambda s, d, t, e: model.stream_step(s, d, d, t, e))
             model.load_memory_state(start)
         # the edge table already holds the rows of the test events; a live system hands them to observe(efeats=...)
-        model.graph = Graph.from_arrays(full_data.src[:n_seen], full_data.dst[:n_seen], full_data.ts[:n_seen],
-                                        full_data.eids[:n_seen], strategy=full_graph.strategy, seed=seed,
-                                        max_node_id=full_graph.num_node - 1, device=device)
+        model.graph = seen()
         forgot = []
         shifted = [0]   # rows released so far: the eids of the events still to come moved down by as much
         rows = []
 
+        admitted = []
+        cache = {}
+
+        def known():   # the items the model knows now (and their index), rebuilt when ids were admitted
+            if cache.get('n') != model.n_nodes:
+                items = catalogue[catalogue < model.n_nodes]
+                cache.update(n=model.n_nodes, items=items, col_of=hip_ops.catalogue_index(items, model.n_nodes))
+            return cache['items'], cache['col_of']
+
+        def observe(s, d, t, e):
+            if not grow:
+                return model.observe(s, d, t, e)
+            n_old, n_new = model.n_nodes, max(model.n_nodes, int(max(s.max(), d.max())) + 1)
+            model.observe(s, d, t, e, num_node='auto', nfeats=torch.from_numpy(nfeats[n_old:n_new]))
+            admitted.append(model.n_nodes - n_old)
+            if verbose:
+                print(f'batch {len(admitted) - 1}: {admitted[-1]} node ids admitted, {model.n_nodes} known')
+
         def observe_and_forget(s, d, t, e):
             e = e - shifted[0]
-            model.observe(s, d, t, e)
+            observe(s, d, t, e)
             before = model.graph.tcsr.num_entry
             g = model.forget(before=None if window is None else float(t[-1]) - window, keep_last=keep_last,
                              release_edge_rows=release_rows, keep_from=int(e[-1]) + 1 if release_rows else None)
@@ -208,10 +261,12 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                     print(f'batch {len(forgot) - 1}: edge table {rel.rows_before} rows -> {rel.rows}')
         forgetting = window is not None or keep_last is not None
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
-                                 observe_and_forget if forgetting else model.observe)
+                                 observe_and_forget if forgetting else observe, known=known if grow else None)
     need = max(n_neighbors, hist_len if restarter_type == 'seq' else 0)
     if ids_off is not None and (not forgetting or (window is None and keep_last >= need and not exclude_seen)):
         assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
+    if grow:
+        online = dict(online, admitted=admitted)
     if forgetting:
         online = dict(online, forgot=forgot)
         if release_rows:
@@ -286,6 +341,9 @@ if __name__ == '__main__':
     ap.add_argument('--release_rows', action='store_true', help='--online with --keep_last / --window: every forget also '
                     'releases the edge-table rows of the forgotten events (TIGE.forget(..., release_edge_rows=True)) and the '
                     'eids still to come are shifted; prints the table\'s rows before and after per batch')
+    ap.add_argument('--grow', action='store_true', help='--online: the model starts with the node ids of train + validation '
+                    '(num_node = their largest id + 1) and admits the ids the test split brings (TIGE.observe(..., '
+                    "num_node='auto')); prints the ids admitted per batch; no offline replay")
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -304,7 +362,9 @@ if __name__ == '__main__':
         for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
                                                               seed=a.seed, bs=a.bs, restarter_type=a.restarter_type,
                                                               window=a.window, keep_last=a.keep_last,
-                                                              release_rows=a.release_rows)):
+                                                              release_rows=a.release_rows, grow=a.grow)):
+            if m is None:
+                continue
             print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "
                   f"({m['n_events']} events)")
         sys.exit(0)

@@ -117,6 +117,21 @@ int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_t* src_host
                         const double* ts_host, const int64_t* eid_host, int64_t* indptr_out_host, double* ts_out_host,
                         int32_t* nbr_out_host, int32_t* eid_out_host);
 
+/* The same with a LARGER node count (online admission of new node ids; graph.py:11-42: no counterpart): indptr_out has
+ * num_node_out + 1 entries, ids lie in [0, num_node_out), and the out arrays equal, byte for byte, what tg_tcsr_build_host
+ * gives for the old events followed by the new ones with num_node_out nodes - ids in [g->num_node, num_node_out) own no old
+ * entry.  Same launches as tg_tcsr_append (which forwards here with num_node_out = g->num_node): no pass or memset over
+ * num_node_out beside the indptr write, no atomics.  n_new == 0 with num_node_out > g->num_node is a pure widening (the
+ * entries are copied, indptr is padded with the total).  TG_EINVAL: num_node_out < g->num_node, num_node_out > 2^31 - 1;
+ * the host twin also for an id >= num_node_out. */
+size_t tg_tcsr_append_grow_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node, int64_t num_node_out);
+int tg_tcsr_append_grow(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src, const int64_t* dst,
+                        const double* ts, const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
+                        int32_t* eid_out, void* ws, size_t ws_bytes, void* stream);
+int tg_tcsr_append_grow_host(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src_host,
+                             const int64_t* dst_host, const double* ts_host, const int64_t* eid_host,
+                             int64_t* indptr_out_host, double* ts_out_host, int32_t* nbr_out_host, int32_t* eid_out_host);
+
 /* Sliding-window expiry: the T-CSR of `g` without its expired entries, written to caller-owned arrays; `g` itself is only
  * read and num_node does not change.  None of the four entries has a counterpart in the reference, which builds its
  * adjacency lists once over the whole stream and never drops an entry (graph.py:11-42).  Per node v with old row

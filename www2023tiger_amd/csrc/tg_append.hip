@@ -14,6 +14,11 @@
 // steps 1-2 are one launch while m <= AP_SMALL (one workgroup sorts the unique keys owner << 12 | j in LDS - unique keys:
 // any sort is stable), else key formation + radix_sort_pairs (tg_build.hip) + one launch for INS.
 // Cost: every old entry is read and written once (16 + 16 bytes) - the price of keeping the compact layout every sampler reads.
+//
+// Growth (tg_tcsr_append_grow: num_node_out >= num_node): ids in [num_node, num_node_out) own no old entry, so their old row
+// is the empty row at the end of the old array - every read of indptr_old is clamped to index num_node (steps 2 and 3),
+// step 3 runs over num_node_out + 1 entries and the large path sorts on the key bits of num_node_out.  Same launches, no
+// pass over num_node_out beside step 3 itself; with num_node_out == num_node the clamps never bind and the grid is the old one.
 #include <algorithm>
 #include <vector>
 
@@ -53,7 +58,7 @@ __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t 
 // steps 1-2, m <= AP_SMALL: one workgroup, bitonic sort of M2 = pow2 >= m keys in LDS (padding keys sort last)
 __global__ void __launch_bounds__(AP_SORT_THREADS) k_append_sort_small(uint32_t m, uint32_t M2, const int64_t* __restrict__ src,
                                                                       const int64_t* __restrict__ dst,
-                                                                      const int64_t* __restrict__ indptr_old,
+                                                                      const int64_t* __restrict__ indptr_old, int64_t n_old,
                                                                       uint32_t* __restrict__ S, uint32_t* __restrict__ J,
                                                                       uint32_t* __restrict__ INS) {
   __shared__ uint64_t key[AP_SMALL];
@@ -80,7 +85,7 @@ __global__ void __launch_bounds__(AP_SORT_THREADS) k_append_sort_small(uint32_t 
     const uint32_t own = (uint32_t)(v >> 12);
     S[s] = own;
     J[s] = (uint32_t)(v & 4095u);
-    INS[s] = (uint32_t)indptr_old[(int64_t)own + 1];
+    INS[s] = (uint32_t)indptr_old[min((int64_t)own + 1, n_old)];  // (an owner the old graph lacks: the end of the old array)
   }
 }
 
@@ -93,15 +98,16 @@ __global__ void k_append_keys(uint32_t m, const int64_t* __restrict__ src, const
     v[j] = (uint32_t)j;
   }
 }
-__global__ void k_append_ins(uint32_t m, const uint32_t* __restrict__ S, const int64_t* __restrict__ indptr_old,
+__global__ void k_append_ins(uint32_t m, const uint32_t* __restrict__ S, const int64_t* __restrict__ indptr_old, int64_t n_old,
                              uint32_t* __restrict__ INS) {
   const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < m) INS[s] = (uint32_t)indptr_old[(int64_t)S[s] + 1];
+  if (s < m) INS[s] = (uint32_t)indptr_old[min((int64_t)S[s] + 1, n_old)];
 }
 
 // steps 3-5.  Blocks [0, nb_new): the new entries; [nb_new, nb_new + nb_ptr): indptr; the rest: one tile of old entries each.
 struct AppendArgs {
   tg_tcsr g;
+  int64_t num_node_out;  // >= g.num_node: rows of indptr_out - 1
   uint32_t m;
   const uint32_t *S, *J, *INS;
   const int64_t *src, *dst, *eid;
@@ -127,9 +133,10 @@ __global__ void __launch_bounds__(AP_THREADS) k_append_apply(AppendArgs a) {
     return;
   }
   b -= a.nb_new;
-  if (b < a.nb_ptr) {  // step 3 (v = num_node included: lower_bound = m)
+  if (b < a.nb_ptr) {  // step 3 (v = num_node_out included: lower_bound = m; v > num_node: the old prefix is the old total)
     const int64_t v = (int64_t)b * AP_THREADS + t;
-    if (v <= a.g.num_node) a.indptr_out[v] = a.g.indptr[v] + (int64_t)lower_bound_u32(a.S, 0u, a.m, (uint32_t)v);
+    if (v <= a.num_node_out)
+      a.indptr_out[v] = a.g.indptr[min(v, a.g.num_node)] + (int64_t)lower_bound_u32(a.S, 0u, a.m, (uint32_t)v);
     return;
   }
   b -= a.nb_ptr;  // step 4: old entries [p0, p1)
@@ -170,19 +177,25 @@ static int append_key_bits(int64_t num_node) {
 
 using namespace tg;
 
-extern "C" size_t tg_tcsr_append_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node) {
-  if (num_entry_old < 0 || n_new < 0 || num_node <= 0) return 0;
+extern "C" size_t tg_tcsr_append_grow_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node,
+                                                      int64_t num_node_out) {
+  if (num_entry_old < 0 || n_new < 0 || num_node <= 0 || num_node_out < num_node || num_node_out > 0x7fffffffLL) return 0;
   const size_t m = 2 * (size_t)n_new;
   if (m == 0) return 0;
   if (m <= (size_t)AP_SMALL) return 3 * align16(m * 4) + 256;
   return 5 * align16(m * 4) + radix_sort_scratch_bytes((uint32_t)m) + 256;
 }
 
-extern "C" int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* src, const int64_t* dst, const double* ts,
-                              const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out, int32_t* eid_out,
-                              void* ws, size_t ws_bytes, void* stream) {
+extern "C" size_t tg_tcsr_append_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node) {
+  return tg_tcsr_append_grow_workspace_bytes(num_entry_old, n_new, num_node, num_node);
+}
+
+extern "C" int tg_tcsr_append_grow(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src, const int64_t* dst,
+                                   const double* ts, const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
+                                   int32_t* eid_out, void* ws, size_t ws_bytes, void* stream) {
   if (!g || n_new < 0 || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || !g->indptr || !indptr_out)
     return TG_EINVAL;
+  if (num_node_out < g->num_node || num_node_out > 0x7fffffffLL) return TG_EINVAL;
   if ((uint64_t)g->num_entry + 2 * (uint64_t)n_new > 0xffffffffull) return TG_EINVAL;
   if (g->num_entry > 0 && (!g->ts || !g->nbr || !g->eid)) return TG_EINVAL;
   if (g->num_entry + 2 * n_new > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
@@ -200,7 +213,7 @@ extern "C" int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* sr
       uint32_t M2 = 128;
       while (M2 < m) M2 <<= 1;
       const unsigned threads = std::min<unsigned>(AP_SORT_THREADS, M2 / 2);
-      hipLaunchKernelGGL(k_append_sort_small, dim3(1), dim3(threads), 0, st, m, M2, src, dst, g->indptr, S, J, INS);
+      hipLaunchKernelGGL(k_append_sort_small, dim3(1), dim3(threads), 0, st, m, M2, src, dst, g->indptr, g->num_node, S, J, INS);
     } else {
       uint32_t* k0 = cv.take<uint32_t>(m);
       uint32_t* v0 = cv.take<uint32_t>(m);
@@ -211,15 +224,16 @@ extern "C" int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* sr
       char* scratch = cv.take<char>(sb);
       if (!cv.ok) return TG_EWORKSPACE;
       hipLaunchKernelGGL(k_append_keys, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, m, src, dst, k0, v0);
-      const int rc = radix_sort_pairs(m, append_key_bits(g->num_node), k0, v0, k1, v1, scratch, sb, st);
+      const int rc = radix_sort_pairs(m, append_key_bits(num_node_out), k0, v0, k1, v1, scratch, sb, st);
       if (rc != TG_OK) return rc;
       S = k0;
       J = v0;
-      hipLaunchKernelGGL(k_append_ins, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, m, S, g->indptr, INS);
+      hipLaunchKernelGGL(k_append_ins, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, m, S, g->indptr, g->num_node, INS);
     }
   }
   AppendArgs a{};
   a.g = *g;
+  a.num_node_out = num_node_out;
   a.m = m;
   a.S = S;
   a.J = J;
@@ -233,20 +247,29 @@ extern "C" int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* sr
   a.nbr_out = nbr_out;
   a.eid_out = eid_out;
   a.nb_new = (uint32_t)cdiv(m, AP_THREADS);
-  a.nb_ptr = (uint32_t)cdiv(g->num_node + 1, AP_THREADS);
+  a.nb_ptr = (uint32_t)cdiv(num_node_out + 1, AP_THREADS);
   const uint32_t nb_copy = (uint32_t)cdiv(g->num_entry, AP_TILE);
   hipLaunchKernelGGL(k_append_apply, dim3(a.nb_new + a.nb_ptr + nb_copy), dim3(AP_THREADS), 0, st, a);
-  return check_launch("tg_tcsr_append");
+  return check_launch("tg_tcsr_append_grow");
 }
 
-// The host twin: plain C++ over host pointers, the same arrays as tg_tcsr_build_host over [old events | new events].
-extern "C" int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_t* src, const int64_t* dst, const double* ts,
-                                   const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
-                                   int32_t* eid_out) {
+extern "C" int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* src, const int64_t* dst, const double* ts,
+                              const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out, int32_t* eid_out,
+                              void* ws, size_t ws_bytes, void* stream) {
+  if (!g) return TG_EINVAL;
+  return tg_tcsr_append_grow(g, g->num_node, n_new, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out, ws, ws_bytes, stream);
+}
+
+// The host twin: plain C++ over host pointers, the same arrays as tg_tcsr_build_host over [old events | new events] with
+// num_node_out nodes.
+extern "C" int tg_tcsr_append_grow_host(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src,
+                                        const int64_t* dst, const double* ts, const int64_t* eid, int64_t* indptr_out,
+                                        double* ts_out, int32_t* nbr_out, int32_t* eid_out) {
   if (!g || n_new < 0 || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || !g->indptr || !indptr_out)
     return TG_EINVAL;
+  if (num_node_out < g->num_node || num_node_out > 0x7fffffffLL) return TG_EINVAL;
   if ((uint64_t)g->num_entry + 2 * (uint64_t)n_new > 0xffffffffull) return TG_EINVAL;
-  const int64_t N = g->num_node;
+  const int64_t N0 = g->num_node, N = num_node_out;
   for (int64_t i = 0; i < n_new; ++i) {
     if (src[i] < 0 || src[i] >= N || dst[i] < 0 || dst[i] >= N) return TG_EINVAL;
     if (eid[i] < 0 || eid[i] > 0x7fffffffLL) return TG_EINVAL;
@@ -257,10 +280,10 @@ extern "C" int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_
     add[dst[i] + 1]++;
   }
   for (int64_t v = 0; v < N; ++v) add[v + 1] += add[v];  // add[v]: new entries of nodes below v
-  for (int64_t v = 0; v <= N; ++v) indptr_out[v] = g->indptr[v] + add[v];
+  for (int64_t v = 0; v <= N; ++v) indptr_out[v] = g->indptr[std::min(v, N0)] + add[v];  // (a new id: the old total)
   std::vector<int64_t> cur(N);
   for (int64_t v = 0; v < N; ++v) {
-    const int64_t lo = g->indptr[v], len = g->indptr[v + 1] - lo, q = indptr_out[v];
+    const int64_t lo = g->indptr[std::min(v, N0)], len = g->indptr[std::min(v + 1, N0)] - lo, q = indptr_out[v];
     std::copy(g->ts + lo, g->ts + lo + len, ts_out + q);
     std::copy(g->nbr + lo, g->nbr + lo + len, nbr_out + q);
     std::copy(g->eid + lo, g->eid + lo + len, eid_out + q);
@@ -277,4 +300,11 @@ extern "C" int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_
     eid_out[p] = (int32_t)((uint32_t)eid[i] | 0x80000000u);
   }
   return TG_OK;
+}
+
+extern "C" int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_t* src, const int64_t* dst, const double* ts,
+                                   const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
+                                   int32_t* eid_out) {
+  if (!g) return TG_EINVAL;
+  return tg_tcsr_append_grow_host(g, g->num_node, n_new, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out);
 }

@@ -28,9 +28,10 @@ from ..hip_ops import stream_ptr
 class _HostRoot:
     """Host-side origin of a graph: the events of from_arrays and / or the host T-CSR arrays.  Shared by reference along a
     chain of `extended` graphs until one of them materialises its own host view."""
-    __slots__ = ('events', 'host', 'dev')
+    __slots__ = ('events', 'host', 'dev', 'num_node')
 
-    def __init__(self):
+    def __init__(self, num_node):
+        self.num_node = num_node  # ids the host arrays cover (a chain that admitted new ids covers more than its root)
         self.events = None  # (src, dst, ts, eids) of from_arrays, the input of either builder
         self.host = None    # host T-CSR arrays (indptr, ts, nbr, eid), built on demand
         self.dev = None     # a graph trimmed on the device: its device arrays, which `host` is downloaded from on demand
@@ -74,7 +75,7 @@ class Graph:
         self._device = torch.device(device) if device is not None else None
         self._dev = None  # device tensors, built / uploaded lazily
         self._mt = None
-        self._root = _HostRoot()  # the host view: `_events`, `_host` below
+        self._root = _HostRoot(self.num_node)  # the host view: `_events`, `_host` below
         self._log = None     # extended graphs: (parent's log, batch) - the batches appended to the root, newest first
         self._time_ordered = False
         self._t_last = -np.inf  # latest event time, kept on the host (a 0-d device tensor after an unvalidated device batch)
@@ -113,7 +114,7 @@ class Graph:
         to_np = lambda x, dt: np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=dt)
         src, dst, ts, eids = (np.concatenate([to_np(b[i], dt) for b in batches])
                               for i, dt in enumerate((np.int64, np.int64, np.float64, np.int64)))
-        old, new = self._root, _HostRoot()
+        old, new = self._root, _HostRoot(self.num_node)
         if old.events is not None:
             new.events = tuple(np.concatenate([a, b]) for a, b in zip(old.events, (src, dst, ts, eids)))
         if old.host is not None or old.events is None or not self._time_ordered:
@@ -121,9 +122,10 @@ class Graph:
             n = len(src)
             h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(len(old.host[1]) + 2 * n, dtype=np.float64),
                  np.empty(len(old.host[1]) + 2 * n, dtype=np.int32), np.empty(len(old.host[1]) + 2 * n, dtype=np.int32))
-            g = TgTcsr(self.num_node, len(old.host[1]), *(ptr(a) for a in old.host))
-            check(lib.tg_tcsr_append_host(C.byref(g), n, ptr(src), ptr(dst), ptr(ts), ptr(eids), *(ptr(a) for a in h)),
-                  'tg_tcsr_append_host')
+            # (the root may cover fewer ids than this graph: a chain that admitted new ones - `extended(num_node=)`)
+            g = TgTcsr(old.num_node, len(old.host[1]), *(ptr(a) for a in old.host))
+            check(lib.tg_tcsr_append_grow_host(C.byref(g), self.num_node, n, ptr(src), ptr(dst), ptr(ts), ptr(eids),
+                                               *(ptr(a) for a in h)), 'tg_tcsr_append_grow_host')
             new.host = h
         self._root, self._log = new, None
 
@@ -149,12 +151,12 @@ class Graph:
         self._time_ordered = bool(E < 2 or np.all(ts[1:] >= ts[:-1])) and 2 * E < 2 ** 32
         return self
 
-    def _build_host(self, events):
+    def _build_host(self, events, num_node):
         src, dst, ts, eids = events
         E = len(src)
-        h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(2 * E, dtype=np.float64),
+        h = (np.empty(num_node + 1, dtype=np.int64), np.empty(2 * E, dtype=np.float64),
              np.empty(2 * E, dtype=np.int32), np.empty(2 * E, dtype=np.int32))
-        check(lib.tg_tcsr_build_host(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), self.num_node, *(ptr(a) for a in h)),
+        check(lib.tg_tcsr_build_host(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), num_node, *(ptr(a) for a in h)),
               'tg_tcsr_build_host')
         return h
 
@@ -165,7 +167,7 @@ class Graph:
             if root.dev is not None:
                 root.host = tuple(np.ascontiguousarray(t.cpu().numpy()) for t in root.dev)
             else:
-                root.host = self._build_host(root.events)
+                root.host = self._build_host(root.events, root.num_node)
         root.dev = None
         return root.host
 
@@ -237,19 +239,36 @@ class Graph:
         return self._mt
 
     # ---- online ingestion -----------------------------------------------------------
-    def extended(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None) -> 'Graph':
+    def extended(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None, num_node=None) -> 'Graph':
         """A NEW Graph over this graph's events followed by the batch (src, dst, ts, eids) - what `from_arrays` over the
         concatenated stream builds, bit for bit (tg_tcsr_append; graph.py:11-42,226-241 has no counterpart: the reference
         builds over the whole stream in advance).  This graph stays valid and unchanged: whatever holds it (captured
         graphs, resident evaluation runs, a collator thread) keeps working.  The batch must be non-decreasing in time and
-        start no earlier than this graph's latest event (equal is allowed); ids in [0, num_node) - num_node never grows,
-        the model's tables are sized by it -; eids within 31 bits: ValueError otherwise, before anything is launched.
+        start no earlier than this graph's latest event (equal is allowed); ids in [0, num_node) - without the num_node
+        argument below num_node does not grow, the model's tables are sized by it -; eids within 31 bits: ValueError
+        otherwise, before anything is launched.
         Host inputs (numpy, CPU tensors) are checked on the host; device tensors with torch reductions and one read-back,
         or not at all with validate=False.  A device-resident parent costs no host work proportional to its size and no
         synchronisation (one launch pair over the old entries, on the current stream); the host view of the new graph is
         produced on first use.  strategy / seed / alpha / device carry over, and the child shares the parent's `rng` and
         device MT19937 state: 'uniform' draws continue one stream.  eid_rows: the rows of the caller's edge-feature table -
-        an eid at or beyond it is refused with the rest (TIGE.observe; it shares the one read-back)."""
+        an eid at or beyond it is refused with the rest (TIGE.observe; it shares the one read-back).
+        num_node: admit new node ids (tg_tcsr_append_grow).  An int >= self.num_node: the child covers that
+        many ids and the batch may name any id below it; 'auto': max(self.num_node, largest id of the batch + 1), from the
+        maximum the validation reads back anyway (so refused with validate=False on a device batch; an explicit int is
+        trusted there).  The child is what `from_arrays(..., max_node_id=num_node - 1)` over the concatenated stream
+        builds, bit for bit; `trimmed`, `renumbered` and later `extended` calls keep its num_node.  The default None keeps
+        num_node and refuses an id at or beyond it.  ValueError: an int below self.num_node or above 2^31 - 1."""
+        auto = isinstance(num_node, str)
+        if auto and num_node != 'auto':
+            raise ValueError(f"extended: num_node must be None, an int or 'auto', not {num_node!r}")
+        n_out = self.num_node
+        if num_node is not None and not auto:
+            n_out = operator.index(num_node)
+            if n_out < self.num_node:
+                raise ValueError(f'extended: num_node = {n_out} is below the graph\'s {self.num_node} (node ids are never released)')
+            if n_out > 0x7FFFFFFF:
+                raise ValueError('extended: node ids must fit in 31 bits')
         on_dev = torch.is_tensor(src) and src.device.type != 'cpu'
         if on_dev:
             batch = tuple(torch.as_tensor(x).to(src.device, dt).contiguous().reshape(-1)
@@ -260,6 +279,9 @@ class Graph:
         n = int(batch[0].shape[0])
         if any(int(b.shape[0]) != n for b in batch):
             raise ValueError('extended: src, dst, ts and eids must have one entry per event')
+        if auto and n and on_dev and not validate:
+            raise ValueError("extended: num_node='auto' takes the largest id from the validation's read-back; with "
+                             'validate=False pass an int')
         t_last = self._t_last
         if n and (validate or not on_dev):
             if torch.is_tensor(t_last):
@@ -276,7 +298,13 @@ class Graph:
                 raise ValueError('extended: the batch must be non-decreasing in time')
             if st[1] < t_last:
                 raise ValueError(f'extended: the batch starts at t = {st[1]}, before the latest event of the graph ({t_last})')
-            if st[3] < 0 or st[4] >= self.num_node:
+            if auto:
+                if st[4] > 0x7FFFFFFE:
+                    raise ValueError('extended: node ids must fit in 31 bits')
+                n_out = max(self.num_node, int(st[4]) + 1)
+            if st[3] < 0 or st[4] >= n_out:
+                if num_node is not None:
+                    raise ValueError(f'node ids must lie in [0, num_node) (num_node = {n_out})')
                 raise ValueError('node ids must lie in [0, num_node) (num_node does not grow: the model\'s tables are sized by it)')
             if st[5] < 0 or st[6] > 0x7FFFFFFF:
                 raise ValueError('edge ids must fit in 31 bits')
@@ -294,7 +322,7 @@ class Graph:
         if old_entries + 2 * n >= 2 ** 32:
             raise ValueError('extended: the device T-CSR holds fewer than 2^32 entries')
         child = Graph.__new__(Graph)
-        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
+        child._init_common(n_out, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
         child._time_ordered = self._time_ordered
         child._t_last = t_last
         if self._dev is not None:  # device-resident parent: extend on the device
@@ -303,19 +331,25 @@ class Graph:
             d_batch = batch if on_dev and batch[0].device == dev else tuple(torch.as_tensor(b).to(dev) for b in batch)
             batch = d_batch  # kept as uploaded (`last_batch`); the host view downloads it if it is ever asked for
             P = old_entries + 2 * n
-            out = (torch.empty(self.num_node + 1, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.float64, device=dev),
+            out = (torch.empty(n_out + 1, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.float64, device=dev),
                    torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev))
-            nbytes = int(lib.tg_tcsr_append_workspace_bytes(old_entries, n, self.num_node))
+            nbytes = int(lib.tg_tcsr_append_grow_workspace_bytes(old_entries, n, self.num_node, n_out))
             ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
             # (inputs and workspace come from the caching allocator: their memory is reused in stream order, no wait needed)
-            check(lib.tg_tcsr_append(C.byref(g), n, *(ptr(b) for b in d_batch), *(ptr(t) for t in out), ptr(ws), nbytes,
-                                     stream_ptr(dev)), 'tg_tcsr_append')
+            check(lib.tg_tcsr_append_grow(C.byref(g), n_out, n, *(ptr(b) for b in d_batch), *(ptr(t) for t in out), ptr(ws),
+                                          nbytes, stream_ptr(dev)), 'tg_tcsr_append')
             child._dev = out
             child._set_struct()
             child._mt = self._mt_state()
         child._root, child._log = self._root, (self._log, batch)
         child.last_batch = batch
         return child
+
+    def widened(self, num_node: int) -> 'Graph':
+        """`extended` with no events: a NEW Graph over the same entries that covers num_node >= self.num_node ids (the new
+        ones own empty rows).  This graph stays valid and unchanged."""
+        e = np.empty(0, dtype=np.int64)
+        return self.extended(e, e, np.empty(0, dtype=np.float64), e, num_node=operator.index(num_node))
 
     # ---- sliding-window expiry --------------------------------------------------------
     def trimmed(self, before: Optional[float] = None, keep_last: Optional[int] = None) -> 'Graph':

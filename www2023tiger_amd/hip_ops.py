@@ -37,6 +37,21 @@ def new_bitmap(n_nodes: int, device) -> Tensor:
     return torch.zeros(bitmap_words(n_nodes), dtype=torch.int64, device=device)
 
 
+def bitmap_grown(bits: Tensor, n_new: int) -> Tensor:
+    """A bitmap of `new_bitmap` over n_new node ids with the bits of `bits` (a bitmap over fewer ids: TIGE.grow_nodes admitted
+    new ones since) - `bits` itself while the word count stands, else a zero-padded copy.  ValueError: bits is no int64
+    bitmap, or it holds more words than n_new ids take (ids are never released)."""
+    W = bitmap_words(n_new)
+    if not torch.is_tensor(bits) or bits.dtype != torch.int64 or bits.dim() != 1 or bits.numel() > W:
+        what = f'{bits.dtype} {tuple(bits.shape)}' if torch.is_tensor(bits) else type(bits).__name__
+        raise ValueError(f'bitmap_grown: {what} is no int64 bitmap of at most {W} words ({n_new} node ids)')
+    if bits.numel() == W:
+        return bits
+    out = torch.zeros(W, dtype=torch.int64, device=bits.device)
+    out[:bits.numel()] = bits
+    return out
+
+
 def bitmap_mark(ids: Tensor, bitmap: Tensor, n_nodes: int):
     ids = _i64(ids)
     check(lib.tg_bitmap_mark(ids.numel(), ptr(ids), ptr(bitmap), n_nodes, stream_ptr(ids.device)), 'tg_bitmap_mark')

@@ -71,6 +71,35 @@ class NumericalFeature(nn.Module):
             self._nz_cache = hit
         return hit[1]
 
+    def append_node_rows(self, rows, reserve: Optional[int] = None) -> bool:
+        """Append rows to the node table (online admission of new node ids, TIGE.grow_nodes): `rows` [k, d_n], or an int k
+        for k zero rows -> whether the table's data pointer moved.  As `append_edge_rows`: the table is the leading view
+        of a backing store that grows by half (reserve=: rows of a new store, as Memory.grow), `n_nodes` follows.  Refused, with nothing changed: a getter without a node
+        table (n_nodes comes from it: NotImplementedError), a table in pinned host memory (register_buffer=False:
+        NotImplementedError), rows of another width, a negative count or a reserve below the new row count (ValueError)."""
+        from .memory import grow_capacity, grow_table
+        if self.nfeats is None:
+            raise NotImplementedError('append_node_rows: the feature getter has no node table (n_nodes is its row count)')
+        if not self.pin_mem:
+            raise NotImplementedError('append_node_rows: the node table lives in pinned host memory (register_buffer=False)')
+        cur = self.nfeats
+        if isinstance(rows, int):
+            if rows < 0:
+                raise ValueError(f'append_node_rows: {rows} rows')
+            k, rows = rows, None
+        else:
+            rows = torch.as_tensor(rows)
+            if rows.dim() != 2 or rows.shape[1] != cur.shape[1]:
+                raise ValueError(f'append_node_rows: rows {tuple(rows.shape)} for a node table of width {cur.shape[1]}')
+            k = rows.shape[0]
+        n0 = cur.shape[0]
+        moved = grow_table(self, 'nfeats', n0 + k, grow_capacity(n0, n0 + k, reserve))
+        if rows is not None and k:
+            self.nfeats[n0:] = rows.to(cur.device, cur.dtype)
+        self.n_nodes = n0 + k
+        self._version_ = getattr(self, '_version_', 0) + 1
+        return moved
+
     def append_edge_rows(self, rows) -> bool:
         """Append rows [n, d_e] to the edge table (online ingestion, TIGE.observe) -> whether the table's data pointer moved
         (the caller then drops whatever caches it: TIGE.invalidate_struct).  The table is a leading view of a backing

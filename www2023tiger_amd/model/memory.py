@@ -16,6 +16,34 @@ from .. import hip_ops
 from .utils import select_latest_nids
 
 
+def grow_capacity(n0: int, n: int, reserve: Optional[int]) -> int:
+    """rows of a new backing store for a table that grows from n0 to n rows: `reserve` (>= n) or half as many again"""
+    if reserve is not None:
+        reserve = int(reserve)
+        if reserve < n:
+            raise ValueError(f'grow: reserve = {reserve} rows is below the {n} rows asked for')
+        return reserve
+    return max(n, n0 + max(16, n0 // 2))
+
+
+def grow_table(mod: nn.Module, name: str, rows: int, cap_rows: int) -> bool:
+    """Buffer `name` of `mod` becomes the leading `rows`-row view of a ZEROED backing store of at least cap_rows rows
+    (kept in mod._stores) -> whether its data pointer moved.  While the store has room nothing is copied and no pointer
+    moves: the rows at and beyond the old view are zero because the store was born zeroed and every kernel bounds the
+    ids it writes by the n_nodes of the struct it is handed.  A buffer that was moved or replaced since
+    (.to(), load_memory_state) no longer heads its store and gets a new one."""
+    cur = getattr(mod, name)
+    stores = mod.__dict__.setdefault('_stores', {})
+    store = stores.get(name)
+    if (store is None or store.device != cur.device or store.data_ptr() != cur.data_ptr() or store.shape[0] < cur.shape[0]
+            or store.shape[0] < rows):
+        store = torch.zeros((max(cap_rows, rows),) + tuple(cur.shape[1:]), dtype=cur.dtype, device=cur.device)
+        store[:cur.shape[0]] = cur
+        stores[name] = store
+    setattr(mod, name, store[:rows])
+    return getattr(mod, name).data_ptr() != cur.data_ptr()
+
+
 class Memory(nn.Module):
     def __init__(self, n, dim):
         super().__init__()
@@ -42,6 +70,22 @@ class Memory(nn.Module):
         self.vals.zero_()
         self.update_ts.zero_()
         self.active_mask.zero_()
+
+    def grow(self, n: int, reserve: Optional[int] = None) -> bool:
+        """Rows for node ids [self.n, n): zero state, as in a freshly built Memory(n, dim) (online admission of new ids,
+        TIGE.grow_nodes; memory.py has no counterpart: the reference sizes its tables once) -> whether a data pointer
+        moved.  vals, update_ts and active_mask stay buffers of exactly n rows under their names (state_dict and
+        checkpoints interchange with a module born with n rows); each is the leading view of a backing store that grows
+        by half (reserve=: rows of a new store), so most calls copy nothing.  ValueError: n < self.n (rows are never
+        released), reserve < n."""
+        n = int(n)
+        if n < self.n:
+            raise ValueError(f'Memory.grow: {n} rows is fewer than the {self.n} the table has (rows are never released)')
+        cap = grow_capacity(self.n, n, reserve)
+        moved = [grow_table(self, name, n, cap) for name in ('vals', 'update_ts', 'active_mask')]
+        self.n = n
+        self._version_ += 1
+        return any(moved)
 
     def get(self, ids: Tensor) -> Tuple[Tensor, Tensor]:
         return hip_ops.gather_rows(self.vals, ids, self.update_ts)
@@ -83,6 +127,23 @@ class MessageStoreNoGradLastOnly(nn.Module):
 
     def clone(self):
         return copy.deepcopy(self)
+
+    def grow(self, n: int, reserve: Optional[int] = None) -> bool:
+        """Rows for node ids [self.n, n): no message, as in a freshly built store (Memory.grow: the same contract) -> whether
+        a data pointer moved.  has_msg_bits gets bitmap_words(n) words; the spare bits of the old last word are zero
+        already (tg_bitmap_mark and the step bound ids by n_nodes)."""
+        n = int(n)
+        if n < self.n:
+            raise ValueError(f'MessageStoreNoGradLastOnly.grow: {n} rows is fewer than the {self.n} the mailbox has '
+                             '(rows are never released)')
+        cap = grow_capacity(self.n, n, reserve)
+        moved = [grow_table(self, name, n, cap) for name in ('node_msg_vals', 'node_msg_ts')]
+        if moved[0]:  # the rows got a new store: the bitmap gets one of the same capacity (its old one may still have room)
+            self.__dict__.get('_stores', {}).pop('has_msg_bits', None)
+        moved.append(grow_table(self, 'has_msg_bits', hip_ops.bitmap_words(n), hip_ops.bitmap_words(cap)))
+        self.n = n
+        self._version_ += 1
+        return any(moved)
 
     # -- set view of the bitmap (host sync; diagnostic / compatibility only) --------
     def _has_msg_numpy(self) -> np.ndarray:

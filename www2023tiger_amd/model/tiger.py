@@ -16,6 +16,7 @@ Ways to run a batch:
   * `fuse_attention()` - inference with fixed parameters: pre-multiplied attention weights.
 """
 import ctypes as C
+import operator
 from typing import Optional, Tuple, Union
 
 import numpy as np
@@ -79,6 +80,10 @@ class CatalogueSnapshot:
     def col_of(self) -> Tensor:
         if self._col_of is None:
             self._col_of = hip_ops.catalogue_index(self.ids, self.n_nodes)
+        m = self.model
+        grown = int(getattr(m, 'n_nodes', 0) or 0) - int(self._col_of.numel())
+        if grown > 0:  # the model admitted node ids since (TIGE.grow_nodes): none of them is in the snapshot
+            self._col_of = torch.cat([self._col_of, self._col_of.new_full((grown,), -1)])
         return self._col_of
 
     def __len__(self):
@@ -885,7 +890,15 @@ class TIGE(nn.Module):
         if chunk_queries < 1:
             raise ValueError('chunk_queries must be positive')
         self.check_graph(graph)
+        if uptodate is not None:
+            self._check_uptodate(what, uptodate)
         return graph, strategy
+
+    def _check_uptodate(self, what: str, uptodate):
+        if torch.is_tensor(uptodate) and uptodate.numel() != hip_ops.bitmap_words(self.n_nodes):
+            raise ValueError(f'{what}: the uptodate bitmap holds {uptodate.numel()} words, {self.n_nodes} node ids take '
+                             f'{hip_ops.bitmap_words(self.n_nodes)} - after grow_nodes / observe(num_node=) pass '
+                             'hip_ops.bitmap_grown(uptodate, model.n_nodes)')
 
     def _restart_pairs(self, src_ids: Tensor, ids_all: Tensor, ts: Tensor, uptodate: Tensor, graph) -> int:
         """the lazy restart of rank_scores / recommend: ONE `restart_involved` over the flat query list `_pair_scores`
@@ -1036,9 +1049,12 @@ class TIGE(nn.Module):
             raise ValueError('recommend: the catalogue snapshot was embedded by another model')
         if snap.device != self.device:
             raise ValueError(f'recommend: the catalogue snapshot lives on {snap.device}, the model on {self.device}')
-        if snap.n_nodes != self.n_nodes or snap.h.shape[1] != self.memory_dim:
+        # (a snapshot from before the model admitted node ids - grow_nodes - is stale like one from before any observe)
+        # (growth bumps the state stamp; a snapshot over fewer ids whose stamp is current did not come from this model's past)
+        stale = snap.stamp != self._snapshot_stamp() or snap.graph_serial != getattr(graph, 'serial', None)
+        if snap.n_nodes > self.n_nodes or (snap.n_nodes < self.n_nodes and not stale) or snap.h.shape[1] != self.memory_dim:
             raise ValueError(f'recommend: the catalogue snapshot covers {snap.n_nodes} node ids, the model {self.n_nodes}')
-        if not stale_ok and (snap.stamp != self._snapshot_stamp() or snap.graph_serial != getattr(graph, 'serial', None)):
+        if not stale_ok and stale:
             raise RuntimeError('recommend: the catalogue snapshot is stale - the state, the parameters or the graph have '
                                'changed since embed_catalogue (stream_step / observe / forget / a restart).  Embed it '
                                'again, or pass stale_ok=True to score the items as of the snapshot')
@@ -1600,7 +1616,7 @@ class TIGE(nn.Module):
                 raise_invariants(word & 0xFFFFFFFF)
         return buf
 
-    def observe(self, src, dst, ts, eids, *, efeats=None, neg=None, want_prev: bool = False):
+    def observe(self, src, dst, ts, eids, *, efeats=None, neg=None, want_prev: bool = False, num_node=None, nfeats=None):
         """Online ingestion of one time-ordered batch of NEW events: their edge-feature rows (efeats [n, d_e], for a model
         with an edge table) are appended to the table, the graph is replaced by `graph.extended(...)` and the batch is
         streamed (`stream_step`; neg defaults to dst) -> the step's StepBuffers.  Extending first is what the reference's
@@ -1609,10 +1625,18 @@ class TIGE(nn.Module):
         and returns the embeddings, of a model that had the full graph from the start - bit for bit.  Afterwards
         `recommend(..., exclude_seen=True)` and `rank_scores` see the new edges.  eval() mode only; refused before anything
         runs: a partitioned model, training mode, an eid that is no row of the edge table (tg_model carries no row count:
-        the step would read past the table), and what `Graph.extended` refuses."""
+        the step would read past the table), and what `Graph.extended` refuses.
+        num_node: admit NEW NODE IDS with the batch.  An int N >= n_nodes, or 'auto' (= the batch's largest
+        id + 1 when that is more than n_nodes): ids below N are accepted, the model's per-node tables grow to N rows
+        (`grow_nodes`) and nfeats [N - n_nodes, d_n] become the feature rows of the ids [n_nodes, N) (zeros if omitted).
+        A model built on N0 nodes that admits ids up to N1 on the way ends in the state, and returns the embeddings, of
+        one built on N1 nodes - bit for bit.  The child graph is computed first (it validates), then what `grow_nodes`
+        refuses is refused: nothing has changed if the call raises.  The caller's part is that of `grow_nodes`."""
         self._refuse_partitioned('observe')
         if self.training:
             raise RuntimeError('observe streams the model in eval() mode')
+        if num_node is None and nfeats is not None:
+            raise ValueError('observe: nfeats are the feature rows of newly admitted node ids (pass num_node)')
         fg = self.raw_feat_getter
         n = len(src)
         if efeats is not None and fg.efeats is not None:
@@ -1622,13 +1646,103 @@ class TIGE(nn.Module):
         rows = None if fg.efeats is None else fg.efeats.shape[0] + (n if efeats is not None else 0)
         # (validates, the eids against the table's rows included - on the host, before any launch; nothing has changed if
         # it raises)
-        new_graph = self.graph.extended(src, dst, ts, eids, eid_rows=rows)
+        if num_node is None:
+            new_graph = self.graph.extended(src, dst, ts, eids, eid_rows=rows)
+        else:
+            new_graph = self.graph.extended(src, dst, ts, eids, eid_rows=rows, num_node=num_node)
+            nfeats = self._grow_refusals('observe', max(new_graph.num_node, self.n_nodes), nfeats, None)
         if efeats is not None and fg.efeats is not None and fg.append_edge_rows(efeats):
             self.invalidate_struct()
-        self.graph = new_graph
+        if new_graph.num_node > self.n_nodes:
+            self._grow(new_graph.num_node, nfeats, None, new_graph)  # (swaps the graph in with the tables)
+        else:
+            self.graph = new_graph
         if torch.is_tensor(new_graph.last_batch[0]):  # extended on the device: the batch is already there
             src, dst, ts, eids = new_graph.last_batch
         return self.stream_step(src, dst, dst if neg is None else neg, ts, eids, want_prev=want_prev)
+
+    def _grow_refusals(self, what: str, num_node, nfeats, reserve):
+        """everything grow_nodes refuses, before anything has changed -> the feature rows of the new ids (a tensor, or the
+        count of zero rows)"""
+        self._refuse_partitioned(what)
+        if self.training:
+            raise RuntimeError(f'{what}: node ids are admitted in eval() mode (the streaming state of a served model)')
+        num_node = operator.index(num_node)
+        k = num_node - self.n_nodes
+        if k < 0:
+            raise ValueError(f'{what}: num_node = {num_node} is below the model\'s {self.n_nodes} (node ids are never released)')
+        if num_node > 0x7FFFFFFF:
+            raise ValueError(f'{what}: node ids must fit in 31 bits')
+        from .restarters import StaticRestarter
+        if k and isinstance(getattr(self, 'restarter_fn', None), StaticRestarter):
+            raise NotImplementedError(f'{what}: the static restarter holds one TRAINED embedding row per node; a new node has '
+                                      'none, and resizing a parameter under an optimizer is not supported')
+        if k and self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: tables cannot grow while a stream is being captured into a graph')
+        fg = self.raw_feat_getter
+        if k and fg.nfeats is None:
+            raise NotImplementedError(f'{what}: the feature getter has no node table (n_nodes is its row count)')
+        if k and not fg.pin_mem:
+            raise NotImplementedError(f'{what}: the node table lives in pinned host memory (register_buffer=False)')
+        if k and not (fg.nfeats.shape[0] == self.left_memory.n == self.right_memory.n == self.msg_store.n == self.n_nodes):
+            raise RuntimeError(f'{what}: the per-node tables do not all hold n_nodes = {self.n_nodes} rows')
+        if self.graph.num_node > num_node:
+            raise ValueError(f'{what}: the graph covers {self.graph.num_node} node ids, more than num_node = {num_node}')
+        if reserve is not None and int(reserve) < num_node:
+            raise ValueError(f'{what}: reserve = {reserve} rows is below num_node = {num_node}')
+        if nfeats is not None:
+            nfeats = torch.as_tensor(nfeats)
+            if nfeats.dim() != 2 or nfeats.shape[0] != k or (k and nfeats.shape[1] != fg.nfeats.shape[1]):
+                raise ValueError(f'{what}: nfeats {tuple(nfeats.shape)} for {k} new node ids of width {self.nfeat_dim}')
+        if k:  # the step buffers are about to be dropped: a deferred invariant word of an earlier batch is read first
+            self._poll_train_errors()
+        return k if nfeats is None else nfeats
+
+    def _grow(self, num_node: int, nfeats, reserve, graph) -> bool:
+        """grow_nodes after its refusals: tables, counts, graph, caches"""
+        eager = self._pending is not None
+        moved = [self.left_memory.grow(num_node, reserve), self.right_memory.grow(num_node, reserve),
+                 self.msg_store.grow(num_node, reserve), self.raw_feat_getter.append_node_rows(nfeats, reserve)]
+        self.n_nodes = num_node
+        if getattr(self, 'restarter_fn', None) is not None:
+            self.restarter_fn.n_nodes = num_node
+        self.graph = graph  # (the setter: the restarter follows)
+        self._touch()
+        self.invalidate_struct()
+        # whatever was sized by the old count: step buffers (bitmaps, caps, the prefetched collate part), per-node tables
+        self._step_ws = {k: v for k, v in self._step_ws.items() if k == 'rng'}
+        self._gtab = self._ctab = self._gtab_stamp = None
+        self._pending = self._pending_stamp = None
+        if eager:
+            self.eager_updates()  # a zeroed table of the new size: rebuilt from the state before the next eager step
+        return any(moved)
+
+    def grow_nodes(self, num_node: int, nfeats=None, reserve: Optional[int] = None) -> bool:
+        """Admit the node ids [n_nodes, num_node) online -> whether a table's data pointer moved.  The two memories, the
+        mailbox and the node-feature table get rows for them - zero state and no message, exactly the rows of a freshly
+        built model; nfeats [num_node - n_nodes, d_n] are their feature rows (zeros if omitted) -, n_nodes changes on the
+        model, the restarter and the feature getter, and the graph is replaced by `graph.widened(num_node)` if it is
+        narrower.  From then on the model is, bit for bit, the model that was built on num_node nodes: `observe` /
+        `stream_step` / `recommend` accept the new ids, and a checkpoint taken now loads into such a model.  Every table
+        is the leading view of a backing store that grows by half (reserve=: rows of the new stores - memories, mailbox
+        and node table alike -, for a caller that knows how far the ids will go), so most calls copy nothing and move no pointer; the stores are born zeroed and
+        no kernel writes a row at or beyond n_nodes (each bounds its ids by the n_nodes of the struct it is handed).
+        Dropped, because they were sized by the old count: the step buffers of `step_buffers` (their bitmaps, caps and
+        prefetched batch), the eager-update and query tables (rebuilt before the next eager step).
+        WHAT THE CALLER MUST DO AFTERWARDS (as after `release_edge_rows`): captured device graphs and resident evaluation
+        runs built before a growth read the old tables and the old count - rebuild them; `uptodate` bitmaps go through
+        `hip_ops.bitmap_grown`; StepBuffers and CatalogueSnapshots held from before are stale; a `save_memory_state` from
+        before holds fewer rows and is refused by `load_memory_state` until its three modules were grown (`grow(n)`).
+        Refused before anything runs - nothing has changed if it raises: a partitioned model, training mode, a model
+        with a StaticRestarter (its per-node embeddings are trained parameters), growth while a stream is being captured,
+        a model without a node-feature table or with one in pinned host memory, num_node below n_nodes or the graph's
+        count or above 2^31 - 1, nfeats of another shape, reserve below num_node."""
+        nfeats = self._grow_refusals('grow_nodes', num_node, nfeats, reserve)
+        num_node = operator.index(num_node)
+        if num_node == self.n_nodes:
+            return False
+        graph = self.graph if self.graph.num_node == num_node else self.graph.widened(num_node)
+        return self._grow(num_node, nfeats, reserve, graph)
 
     def forget(self, before=None, keep_last=None, release_edge_rows: bool = False, keep_from=None):
         """Sliding-window expiry for a model that keeps observing: the graph is replaced by `graph.trimmed(before,
@@ -1736,6 +1850,10 @@ class TIGE(nn.Module):
         return (self.left_memory.clone(), self.right_memory.clone(), self.msg_store.clone())
 
     def load_memory_state(self, data):
+        for new, cur in zip(data, (self.left_memory, self.right_memory, self.msg_store)):
+            if new.n != cur.n:  # (a state saved before grow_nodes: the structs would address rows it does not have)
+                raise ValueError(f'load_memory_state: the saved state holds {new.n} rows per table, the model {cur.n} '
+                                 '(saved before grow_nodes admitted node ids? grow it with its own grow(n) first)')
         self._touch()
         self.left_memory, self.right_memory, self.msg_store = data
         self.msg_memory = self.left_memory if self.msg_src == 'left' else self.right_memory
@@ -1833,6 +1951,7 @@ class TIGER(TIGE):
             raise NotImplementedError(f"restart_involved lists 'recent_edges' or 'recent_nodes' neighbourhoods; strategy="
                                       f"{strategy!r} would make the set depend on the graph's random stream")
         self.check_graph(graph)
+        self._check_uptodate('restart_involved', uptodate)
         dev = self.device
         nodes = torch.as_tensor(nodes).to(dev).long().contiguous().reshape(-1)
         ts64 = torch.as_tensor(ts).to(dev).double().contiguous().reshape(-1)

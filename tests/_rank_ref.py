@@ -69,15 +69,15 @@ def score_bound(A, d, W):
     return (2 * W + d + 8) * 2.0 ** -24 * A
 
 
-# (d, K, B, C, hit): each the smallest shape that reaches its path of k_rank_tile (csrc/tg_rank.hip)
+# (d, K, B, C, hit): each the smallest shape that reaches its path of k_rank_tile / k_head_half (csrc/tg_rank.hip, tg_rank_head.h)
 SCORE_CASES = [
     (8, 5, 3, 1, 'bin'),       # the smallest: one tile, one k tile, `min(n, d - 1)` clamps 120 of the 128 weight rows
     (8, 6, 1, 0, 'vec'),       # P = 1: `min(m0 + tid, P - 1)` repeats the one pair in the 31 spare rows
-    (30, 2, 4, 7, 'vec'),      # KX = 34: dst hits end k tile 0, src hits open k tile 1 (`k < d + K`, `k < KX`); P = 32 exactly
-    (32, 16, 3, 10, 'vec'),    # KX = 64, W = 48: the `k < W` weight-index switch falls inside k tile 1; P = 33
+    (30, 2, 4, 7, 'vec'),      # KX = 34: dst hits end k tile 0, src hits open k tile 1 (hit_operand: `k < K`, `k < 2 * K`); P = 32 exactly
+    (32, 16, 3, 10, 'vec'),    # KX = 64, W = 48: the `k < W` weight-index switch (pair_weight) falls inside k tile 1; P = 33
     (33, 5, 31, 0, 'count'),   # wave 1 holds one column (`n < d` under `live`); C = 0; P = 31
     (96, 4, 5, 6, 'bin'),      # wave 3 is dead: `live` false for a whole wavefront
-    (128, 4, 33, 1, 'none'),   # one full column pass; the source half spans two tiles (B > 32); all id arrays NULL
+    (128, 4, 33, 1, 'none'),   # one full column pass; the source half (k_head_half) spans two tiles (B > 32); all id arrays NULL
     (129, 3, 3, 40, 'count'),  # the second `nc` pass holds one column; an event's 41 pairs straddle tiles (`p / C1`)
     (172, 10, 7, 5, 'vec'),    # KX = 192, W = 182: two column passes with hit operand columns
     (172, 10, 7, 5, 'count'),  # two column passes with class tables; n_hit_rows = K + 3 > K + 1 (EXTRA_HIT_ROWS)

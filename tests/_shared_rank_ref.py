@@ -23,7 +23,7 @@ SHARED_CASES = [
     (172, 10, 7, 6, 'count'),   # the project's headline width; n_hit_rows = K + 3 > K + 1 (EXTRA_HIT_ROWS)
     (16, 3, 70, 67, 'bin'),     # B and C beyond 64, neither a multiple of 32
     (16, 4, 65, 1, 'vec'),      # many sources, one item
-    # the edges of k_shared_pairs's tile (csrc/tg_rank_shared.hip: 16 sources x chunks of 8 items, strips of 64 items) and of
+    # the edges of k_shared_pairs's tile (csrc/tg_rank_snapshot.hip: 16 sources x chunks of 8 items, strips of 64 items) and of
     # the 32-row tile of the half products, on both axes
     (8, 2, 16, 8, 'count'),     # one block, one chunk, every row and column live
     (8, 2, 17, 9, 'bin'),       # one source and one item past: a second block row with one live source, a chunk of one item

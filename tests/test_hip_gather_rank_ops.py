@@ -1,4 +1,4 @@
-"""tg_rank_scores_gathered called directly (csrc/tg_rank_gather.hip) on the constructed cases of tests/_shared_rank_ref.py:
+"""tg_rank_scores_gathered called directly (csrc/tg_rank_snapshot.hip) on the constructed cases of tests/_shared_rank_ref.py:
 no model, no sampler.  Two yardsticks per call, and no pair is left out of either:
 
   exact   for col[i, q] = j >= 0 the bits of tg_rank_scores_shared at [i, j] on the same inputs (the order contract is
@@ -7,7 +7,7 @@ no model, no sampler.  Two yardsticks per call, and no pair is left out of eithe
   float64 within _rank_ref.score_bound of the float64 score s[i, j] - so the two kernels cannot drift together.
 
 The col patterns stand at the edges of the NEW kernel's tile (k_gather_pairs: one source per block, chunks of GA_CH = 16
-columns - the fk halves of a wavefront take alternate items - and strips of GA_JS = 32; k_gather_vec: 32 pair rows).  Every
+columns - the fk halves of a wavefront take alternate items - and strips of GA_JS = 32; k_snap_vec<true>: 32 pair rows).  Every
 call runs on a NaN-filled workspace and a NaN-filled score array."""
 import ctypes as C
 
@@ -20,7 +20,7 @@ from test_hip_rank_ops import bits, dev, to_dev
 from test_hip_shared_rank_ops import params, run_half, run_shared
 
 pytestmark = pytest.mark.gpu
-GA_CH, GA_JS = 16, 32   # csrc/tg_rank_gather.hip: columns of a chunk, columns of a block's strip
+GA_CH, GA_JS = 16, 32   # csrc/tg_rank_snapshot.hip: columns of a chunk, columns of a block's strip
 
 KEYS = [(8, 5, 3, 2, 'bin'), (8, 6, 1, 1, 'vec'), (30, 2, 4, 8, 'vec'), (33, 5, 31, 1, 'count'), (96, 4, 5, 7, 'bin'),
         (128, 4, 33, 2, 'none'), (129, 3, 3, 41, 'count'), (172, 10, 7, 6, 'vec'), (172, 10, 7, 6, 'count'),

@@ -1,4 +1,4 @@
-"""tg_rank_cand_half and tg_rank_scores_shared called directly (csrc/tg_rank_shared.hip) on the constructed cases of
+"""tg_rank_cand_half and tg_rank_scores_shared called directly (csrc/tg_rank_snapshot.hip) on the constructed cases of
 tests/_shared_rank_ref.py: no model, no sampler.
 
 The main claim is exact: a pair's bits equal those of tg_rank_scores on the BROADCAST inputs (every source meets the

@@ -138,9 +138,13 @@ def measure(model, st, cols, Cn, steps, reps):
 
 
 def clocks():
+    """what the runtime reports about the device and its clocks; a field this torch build does not have is left out"""
     p = torch.cuda.get_device_properties(0)
-    out = dict(device=p.name, compute_units=p.multi_processor_count, max_engine_clock_mhz=p.clock_rate / 1e3,
-               max_memory_clock_mhz=p.memory_clock_rate / 1e3)
+    out = dict(device=p.name, compute_units=p.multi_processor_count)
+    for name, attr in (('max_engine_clock_mhz', 'clock_rate'), ('max_memory_clock_mhz', 'memory_clock_rate')):
+        v = getattr(p, attr, None)
+        if v is not None:
+            out[name] = v / 1e3
     try:
         out['engine_clock_now_mhz'] = torch.cuda.clock_rate()
     except Exception as e:  # the management library is optional

@@ -2,9 +2,10 @@
 // Reference: the score head of tiger/model/tiger.py:257-288 (hit features: data_loader.py:61-75), applied to every
 // candidate column in place of the one negative; MRR / Hits@k as the DGB / TGB protocol states them.
 //
-// tg_rank_scores.  score(i, j) = fc2(relu(fc1([xp | yp]))), fc1 = [d, 2W].  fc1's product is split by operand:
-//   source half   S[i, :] = W1[:, :d] x_i + b1                one 32-row MFMA tile pass over the B events (k_rank_tile<true>)
-//   hit classes   T_s[c, :] = W1[:, :W] e(c), T_d[c, :] = W1[:, W:] e(c)   ('bin' / 'count': n_hit_rows rows each, k_rank_tables)
+// tg_rank_scores.  score(i, j) = fc2(relu(fc1([xp | yp]))), fc1 = [d, 2W].  fc1's product is split by operand
+// (tg_rank_head.h; this unit also holds the head's two shared kernels, k_head_tables and k_head_half):
+//   source half   S[i, :] = W1[:, :d] x_i + b1                one 32-row MFMA tile pass over the B events (k_head_half)
+//   hit classes   T_s[c, :] = W1[:, :W] e(c), T_d[c, :] = W1[:, W:] e(c)   ('bin' / 'count': n_hit_rows rows each, k_head_tables)
 //   pair half     W1[:, W:W+d] y_p (+ 'vec': the K hit columns of either side as 2K more operand columns)
 // The pair half is the B (1 + C)-row product: a 256-thread block owns 32 pair rows, its four wavefronts own 32 hidden
 // columns each (a hidden width above 128 takes further column passes) and multiply with v_mfma_f32_32x32x2_f32 (lane l
@@ -19,88 +20,132 @@
 // in (tiger_hip.h); a second one-wave launch folds the events' ranks into the caller's accumulator in a fixed order.
 #include <cmath>
 
-#include "tg_mfma.h"
+#include "tg_rank_head.h"
 
 namespace tg {
 
-constexpr int RK_BM = 32;   // pair rows of a block
-constexpr int RK_BN = 128;  // hidden columns of a column pass (4 wavefronts x 32)
-
-struct RankArgs {
-  int64_t B, P;  // events; rows of this pass (B: source half, B * C1: pairs)
-  int C1, d, K, W, KX;  // 1 + C; hidden width; neighbours; operand width of one side; operand columns of this pass
-  int hit_type, n_hit_rows;
-  const float *h_src, *h_cand;
-  const int64_t *nbr_src, *nbr_cand, *src, *cand;
-  const float *w1, *b1, *w2, *b2;
-  float *srow, *tab_s, *tab_d;
-  float* scores;
+struct RankArgs : HeadArgs {  // item = candidate: one row of h_cand, nbr_item and item per pair
+  int64_t NP;  // pair rows, B * C1
+  int C1, KX;  // 1 + C; operand columns of a pair row
+  const float* h_cand;
 };
 
 // T_s / T_d: the hit embedding's rows through either half of fc1 (one thread per output)
-__global__ void k_rank_tables(RankArgs a, const float* __restrict__ emb) {
-  const int total = a.n_hit_rows * a.d;
+__global__ void k_head_tables(int n_hit_rows, int d, int W, const float* __restrict__ w1, const float* __restrict__ emb,
+                              float* __restrict__ tab_s, float* __restrict__ tab_d) {
+  const int total = n_hit_rows * d;
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    const int c = t / a.d, n = t - c * a.d;
-    const float* w = a.w1 + (int64_t)n * 2 * a.W;
-    const float* e = emb + (int64_t)c * a.d;
+    const int c = t / d, n = t - c * d;
+    const float* w = w1 + (int64_t)n * 2 * W;
+    const float* e = emb + (int64_t)c * d;
     float s = 0.f, q = 0.f;
-    for (int k = 0; k < a.d; ++k) {
+    for (int k = 0; k < d; ++k) {
       s += w[k] * e[k];
-      q += w[a.W + k] * e[k];
+      q += w[W + k] * e[k];
     }
-    a.tab_s[t] = s;
-    a.tab_d[t] = q;
+    tab_s[t] = s;
+    tab_d[t] = q;
   }
 }
 
-// PRE: rows are the events, operand x_i, weights W1[:, :d], output S = product + b1.
-// else: rows are the pairs, operand [y_p | dst hits | src hits], weights W1[:, W:] (| W1[:, d:W]), output the scores.
-template <bool PRE>
-__global__ void __launch_bounds__(256) k_rank_tile(RankArgs a) {
-  __shared__ float As[RK_BM][LDK];
-  __shared__ float Bs[RK_BN][LDK];
-  __shared__ float red[4][RK_BM];
-  __shared__ int ev[RK_BM];
-  __shared__ int cls[RK_BM][2];
+int head_tables(const HeadArgs& a, const float* emb, hipStream_t st, const char* what) {
+  hipLaunchKernelGGL(k_head_tables, dim3(flat_grid((int64_t)a.n_hit_rows * a.d, 256)), dim3(256), 0, st, a.n_hit_rows, a.d, a.W,
+                     a.w1, emb, a.tab_s, a.tab_d);
+  return check_launch(what);
+}
+
+// out[r, n] = sum_k w1[n, wofs + k] h[r, k] (+ bias[n]): a 32-row MFMA tile pass on either weight block of fc1.  The chain
+// per output is the one k_rank_tile runs over an operand's first d columns: accumulator from 0, k ascending, two per MFMA,
+// zero padding past d - so P stored as f32 and loaded again continues that chain exactly.
+__global__ void __launch_bounds__(256) k_head_half(int64_t R, int d, int ldw, int wofs, const float* __restrict__ h,
+                                                   const float* __restrict__ w1, const float* __restrict__ bias,
+                                                   float* __restrict__ out) {
+  __shared__ float As[RH_BM][LDK];
+  __shared__ float Bs[RH_BN][LDK];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 31, fk = lane >> 5;
-  const int64_t m0 = (int64_t)blockIdx.x * RK_BM;
-  const int d = a.d, K = a.K, W = a.W, KX = a.KX;
-  const bool vec = !PRE && a.hit_type == TG_HIT_VEC;
-  const bool emb = !PRE && (a.hit_type == TG_HIT_BIN || a.hit_type == TG_HIT_COUNT);
-  if (tid < RK_BM) {
-    const int64_t p = min(m0 + tid, a.P - 1);  // rows past the end repeat the last one; they are never stored
-    const int64_t i = PRE ? p : p / a.C1;
-    ev[tid] = (int)i;
-    int cs = 0, cd = 0;
-    if (emb) {
-      const int64_t s = a.src[i], c = a.cand[p];
-      for (int k = 0; k < K; ++k) {
-        cs += a.nbr_cand[p * K + k] == s ? 1 : 0;  // the source among the candidate's neighbours (src hits)
-        cd += a.nbr_src[i * K + k] == c ? 1 : 0;   // the candidate among the source's neighbours (dst hits)
+  const int64_t m0 = (int64_t)blockIdx.x * RH_BM;
+  const int sr = tid >> 3, sk = (tid & 7) * 4;  // staging: 8 threads per 32-float row, 4 consecutive k each
+  const float* arow = h + min(m0 + sr, R - 1) * d;  // rows past the end repeat the last one; they are never stored
+  const int nkt = (d + BK - 1) / BK;
+  for (int nc = 0; nc < d; nc += RH_BN) {
+    const bool live = nc + wave * 32 < d;  // wave-uniform
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int kt = 0; kt < nkt; ++kt) {
+      __syncthreads();  // the previous tile has been read
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int k = kt * BK + sk + e;
+        As[sr][sk + e] = k < d ? arow[k] : 0.f;
       }
-      if (a.hit_type == TG_HIT_BIN) {
-        cs = cs > 0;
-        cd = cd > 0;
+#pragma unroll
+      for (int rr = 0; rr < RH_BN / 32; ++rr) {
+        const int n = nc + sr + 32 * rr;
+        const float* wrow = w1 + (int64_t)min(n, d - 1) * ldw + wofs;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int k = kt * BK + sk + e;
+          Bs[sr + 32 * rr][sk + e] = (n < d && k < d) ? wrow[k] : 0.f;
+        }
       }
-      cs = min(cs, a.n_hit_rows - 1);
-      cd = min(cd, a.n_hit_rows - 1);
+      __syncthreads();
+      if (live) {
+        const float* pa = &As[fr][fk];
+        const float* pb = &Bs[wave * 32 + fr][fk];
+#pragma unroll
+        for (int s = 0; s < BK / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb[2 * s], acc, 0, 0, 0);
+      }
     }
-    cls[tid][0] = cs;
-    cls[tid][1] = cd;
+    const int n = nc + wave * 32 + fr;
+    if (live && n < d) {
+      const float b = bias ? bias[n] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * fk;
+        if (m0 + row < R) out[(m0 + row) * d + n] = bias ? acc[r] + b : acc[r];
+      }
+    }
+  }
+}
+
+int head_half(int64_t R, int d, int ldw, int wofs, const float* h, const float* w1, const float* bias, float* out,
+              hipStream_t st, const char* what) {
+  hipLaunchKernelGGL(k_head_half, dim3((unsigned)cdiv(R, RH_BM)), dim3(256), 0, st, R, d, ldw, wofs, h, w1, bias, out);
+  return check_launch(what);
+}
+
+// rows are the pairs, operand [y_p | dst hits | src hits], weights W1[:, W:] (| W1[:, d:W]), output the scores
+__global__ void __launch_bounds__(256) k_rank_tile(RankArgs a) {
+  __shared__ float As[RH_BM][LDK];
+  __shared__ float Bs[RH_BN][LDK];
+  __shared__ float red[4][RH_BM];
+  __shared__ int ev[RH_BM];
+  __shared__ int2 off[RH_BM];  // (class of the src hits, class of the dst hits) * d per pair row
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 31, fk = lane >> 5;
+  const int64_t m0 = (int64_t)blockIdx.x * RH_BM;
+  const int d = a.d, K = a.K, W = a.W, KX = a.KX;
+  const bool vec = a.hit_type == TG_HIT_VEC;
+  const bool emb = a.hit_type == TG_HIT_BIN || a.hit_type == TG_HIT_COUNT;
+  if (tid < RH_BM) {
+    const int64_t p = min(m0 + tid, a.NP - 1);  // rows past the end repeat the last one; they are never stored
+    const int64_t i = p / a.C1;
+    ev[tid] = (int)i;
+    if (emb) off[tid] = hit_class_off(a, i, p);
   }
   // staging coordinates: 8 threads per 32-float row, 4 consecutive k each
   const int sr = tid >> 3, sk = (tid & 7) * 4;
-  const int64_t ap = min(m0 + sr, a.P - 1);
-  const int64_t ai = PRE ? ap : ap / a.C1;
-  const float* arow = PRE ? a.h_src + ap * d : a.h_cand + ap * d;
-  const int64_t a_src = vec ? a.src[ai] : 0, a_cand = vec ? a.cand[ap] : 0;
+  const int64_t ap = min(m0 + sr, a.NP - 1);
+  const int64_t ai = ap / a.C1;
+  const float* arow = a.h_cand + ap * d;
+  const int64_t a_src = vec ? a.src[ai] : 0, a_cand = vec ? a.item[ap] : 0;
   float part[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) part[r] = 0.f;
   const int nkt = (KX + BK - 1) / BK;
-  for (int nc = 0; nc < d; nc += RK_BN) {
+  for (int nc = 0; nc < d; nc += RH_BN) {
     const bool live = nc + wave * 32 < d;  // wave-uniform: this wavefront has hidden columns in this pass
     f32x16 acc;
 #pragma unroll
@@ -113,22 +158,20 @@ __global__ void __launch_bounds__(256) k_rank_tile(RankArgs a) {
         float v = 0.f;
         if (k < d) {
           v = arow[k];
-        } else if (vec && k < d + K) {
-          v = a.nbr_src[ai * K + (k - d)] == a_cand ? 1.f : 0.f;
-        } else if (vec && k < KX) {
-          v = a.nbr_cand[ap * K + (k - d - K)] == a_src ? 1.f : 0.f;
+        } else if (vec) {
+          v = hit_operand(k - d, K, a.nbr_src + ai * K, a.nbr_item + ap * K, a_src, a_cand);
         }
         As[sr][sk + e] = v;
       }
 #pragma unroll
-      for (int rr = 0; rr < RK_BN / 32; ++rr) {
+      for (int rr = 0; rr < RH_BN / 32; ++rr) {
         const int n = nc + sr + 32 * rr;
         const float* wrow = a.w1 + (int64_t)min(n, d - 1) * 2 * W;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int k = kt * BK + sk + e;
           float v = 0.f;
-          if (n < d && k < KX) v = PRE ? wrow[k] : (k < W ? wrow[W + k] : wrow[d + (k - W)]);
+          if (n < d && k < KX) v = pair_weight(wrow, k, W, d);
           Bs[sr + 32 * rr][sk + e] = v;
         }
       }
@@ -142,32 +185,20 @@ __global__ void __launch_bounds__(256) k_rank_tile(RankArgs a) {
     }
     const int n = nc + wave * 32 + fr;
     if (live && n < d) {
-      const float b1 = PRE ? a.b1[n] : 0.f;
-      const float w2 = PRE ? 0.f : a.w2[n];
+      const float w2 = a.w2[n];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * fk;
-        if (PRE) {
-          if (m0 + row < a.P) a.srow[(m0 + row) * d + n] = acc[r] + b1;
-        } else {
-          float v = acc[r] + a.srow[(int64_t)ev[row] * d + n];
-          if (emb) v += a.tab_s[cls[row][0] * d + n] + a.tab_d[cls[row][1] * d + n];
-          part[r] += fmaxf(v, 0.f) * w2;
-        }
+        float v = acc[r] + a.srow[(int64_t)ev[row] * d + n];
+        if (emb) v += a.tab_s[off[row].x + n] + a.tab_d[off[row].y + n];
+        part[r] += fmaxf(v, 0.f) * w2;
       }
     }
   }
-  if (PRE) return;
-  // the 32 lanes of one fk half hold the columns of the same 16 rows
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float v = part[r];
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if (fr == 0) red[wave][(r & 3) + 8 * (r >> 2) + 4 * fk] = v;
-  }
+  for (int r = 0; r < 16; ++r) fold_slot(part[r], fr, &red[wave][(r & 3) + 8 * (r >> 2) + 4 * fk]);
   __syncthreads();
-  if (tid < RK_BM && m0 + tid < a.P) a.scores[m0 + tid] = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + a.b2[0];
+  if (tid < RH_BM && m0 + tid < a.NP) a.scores[m0 + tid] = head_score(red, tid, a.b2);
 }
 
 // ---- rank statistics --------------------------------------------------------------------------------------------------
@@ -255,63 +286,35 @@ static bool rank_shape_ok(int64_t B, int32_t C) {
   return B >= 0 && C >= 0 && C < 0x7fffffff && (B == 0 || (int64_t)(C + 1) <= 0x7fffffffLL / B);
 }
 
-static bool rank_score_params_ok(const tg_score_params* sp, int32_t d, int32_t K) {
-  if (!sp || !sp->fc1.w || !sp->fc1.b || !sp->fc2.w || !sp->fc2.b) return false;
-  if (sp->hit_type < TG_HIT_NONE || sp->hit_type > TG_HIT_COUNT) return false;
-  const bool emb = sp->hit_type == TG_HIT_BIN || sp->hit_type == TG_HIT_COUNT;
-  if (emb && (!sp->hit_emb || sp->n_hit_rows < (sp->hit_type == TG_HIT_BIN ? 2 : K + 1))) return false;
-  return true;
-}
-
 }  // namespace tg
 
 using namespace tg;
 
 extern "C" size_t tg_rank_scores_workspace_bytes(int64_t B, int32_t d, const tg_score_params* sp) {
-  if (B < 0 || d <= 0 || !sp) return 0;
-  const bool emb = sp->hit_type == TG_HIT_BIN || sp->hit_type == TG_HIT_COUNT;
-  const int64_t rows = B + (emb ? 2 * (int64_t)sp->n_hit_rows : 0);
-  return (size_t)(rows * d) * sizeof(float) + 16;
+  return head_workspace_bytes(B, d, sp);
 }
 
 extern "C" int tg_rank_scores(int64_t B, int32_t C, int32_t d, int32_t K, const tg_score_params* sp, const float* h_src,
                               const float* h_cand, const int64_t* nbr_src, const int64_t* nbr_cand, const int64_t* src,
                               const int64_t* cand_ids, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  if (!rank_shape_ok(B, C) || d <= 0 || K < 0 || !rank_score_params_ok(sp, d, K)) return TG_EINVAL;
+  if (!rank_shape_ok(B, C) || d <= 0 || K < 0 || !head_params_ok(sp, K)) return TG_EINVAL;
   if (sp->hit_type == TG_HIT_VEC && (2 * (d + K)) % 4) return TG_EUNSUPPORTED;  // as the one-call evaluation step
   if (B == 0) return TG_OK;
   if (!h_src || !h_cand || !scores || !ws) return TG_EINVAL;
   const bool hits = sp->hit_type != TG_HIT_NONE;
   if (hits && (K <= 0 || !nbr_src || !nbr_cand || !src || !cand_ids)) return TG_EINVAL;
   if (ws_bytes < tg_rank_scores_workspace_bytes(B, d, sp)) return TG_EWORKSPACE;
-  const bool emb = sp->hit_type == TG_HIT_BIN || sp->hit_type == TG_HIT_COUNT;
   hipStream_t st = as_stream(stream);
   RankArgs a{};
-  a.B = B;
+  head_fill(a, B, d, K, sp, nbr_src, nbr_cand, src, cand_ids, scores, ws);
   a.C1 = C + 1;
-  a.d = d;
-  a.K = K;
-  a.W = d + (sp->hit_type == TG_HIT_VEC ? K : 0);
-  a.hit_type = sp->hit_type;
-  a.n_hit_rows = emb ? sp->n_hit_rows : 0;
-  a.h_src = h_src; a.h_cand = h_cand;
-  a.nbr_src = nbr_src; a.nbr_cand = nbr_cand; a.src = src; a.cand = cand_ids;
-  a.w1 = sp->fc1.w; a.b1 = sp->fc1.b; a.w2 = sp->fc2.w; a.b2 = sp->fc2.b;
-  a.srow = static_cast<float*>(ws);
-  a.tab_s = a.srow + B * d;
-  a.tab_d = a.tab_s + (int64_t)a.n_hit_rows * d;
-  a.scores = scores;
-  if (emb) {
-    hipLaunchKernelGGL(k_rank_tables, dim3(flat_grid((int64_t)a.n_hit_rows * d, 256)), dim3(256), 0, st, a, sp->hit_emb);
-    if (int rc = check_launch("tg_rank_scores(tables)")) return rc;
-  }
-  a.P = B;
-  a.KX = d;
-  hipLaunchKernelGGL(k_rank_tile<true>, dim3((unsigned)cdiv(a.P, RK_BM)), dim3(256), 0, st, a);
-  if (int rc = check_launch("tg_rank_scores(source half)")) return rc;
-  a.P = B * a.C1;
+  a.NP = B * a.C1;
   a.KX = d + (sp->hit_type == TG_HIT_VEC ? 2 * K : 0);
-  hipLaunchKernelGGL(k_rank_tile<false>, dim3((unsigned)cdiv(a.P, RK_BM)), dim3(256), 0, st, a);
+  a.h_cand = h_cand;
+  if (head_emb(sp))
+    if (int rc = head_tables(a, sp->hit_emb, st, "tg_rank_scores(tables)")) return rc;
+  if (int rc = head_half(B, d, 2 * a.W, 0, h_src, a.w1, a.b1, a.srow, st, "tg_rank_scores(source half)")) return rc;
+  hipLaunchKernelGGL(k_rank_tile, dim3((unsigned)cdiv(a.NP, RH_BM)), dim3(256), 0, st, a);
   return check_launch("tg_rank_scores");
 }
 

@@ -952,6 +952,12 @@ class TIGE(nn.Module):
                 nb[off:off + n] = nbq[:n]
         return h, nb
 
+    def _check_ids(self, ids: Tensor, message: str):
+        """ValueError(message) if a node id of the non-empty int64 tensor `ids` lies outside [0, n_nodes)"""
+        lo_id, hi_id = torch.aminmax(ids)
+        if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
+            raise ValueError(message)
+
     def _pair_scores(self, what: str, src_ids: Tensor, ids_all: Tensor, ts: Tensor, graph, strategy: str,
                      chunk_queries: int) -> Tensor:
         """scores [B, C1] of the pairs (src_ids[i], ids_all[i, j]) at ts[i] on the current state, nothing written (the body
@@ -961,9 +967,7 @@ class TIGE(nn.Module):
         d, K, dev = self.memory_dim, self.n_neighbors, self.device
         B = src_ids.numel()
         if B:
-            lo_id, hi_id = torch.aminmax(torch.cat([src_ids, ids_all.reshape(-1)]))
-            if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
-                raise ValueError(f'{what}: a node id outside [0, n_nodes)')
+            self._check_ids(torch.cat([src_ids, ids_all.reshape(-1)]), f'{what}: a node id outside [0, n_nodes)')
         ts64 = ts.to(dev).double().contiguous()
         C1 = ids_all.shape[1]
         scores = torch.empty(B, C1, dtype=torch.float32, device=dev)
@@ -1032,9 +1036,7 @@ class TIGE(nn.Module):
         if t != t:
             raise ValueError('embed_catalogue: t is NaN')
         if cand.numel():
-            lo_id, hi_id = torch.aminmax(cand)
-            if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
-                raise ValueError('embed_catalogue: a node id outside [0, n_nodes)')
+            self._check_ids(cand, 'embed_catalogue: a node id outside [0, n_nodes)')
         if uptodate is not None and cand.numel():
             self.restart_involved(cand, torch.full((cand.numel(),), t, dtype=torch.float64, device=self.device), uptodate,
                                   graph=graph)
@@ -1129,6 +1131,28 @@ class TIGE(nn.Module):
         return self._recommend(src_ids, ts, cand, k, mask, False, graph, chunk_queries, None, uptodate, catalogue_at, stale_ok,
                                subset)
 
+    def _snapshot_scores(self, snap: CatalogueSnapshot, P: Tensor, sp, src_c: Tensor, h_src: Tensor,
+                         nb_src: Optional[Tensor], col: Optional[Tensor] = None) -> Tensor:
+        """one score block of a chunk's b sources (ids src_c, rows h_src / nb_src of `_embed_queries`) on the snapshot's
+        rows, whose item half is P: float32 [b, C] over all C rows (tg_rank_scores_shared), or, with col int32 [b, Cq]
+        naming a snapshot row per pair (-1: not in the catalogue), [b, Cq] (tg_rank_scores_gathered)"""
+        d, K, dev = self.memory_dim, self.n_neighbors, self.device
+        b, Cc = src_c.numel(), snap.ids.numel()
+        with torch.no_grad():
+            scores = torch.empty(b, Cc if col is None else col.shape[1], dtype=torch.float32, device=dev)
+            if col is None:
+                ws = self._ws('rank', int(lib.tg_rank_scores_shared_workspace_bytes(b, d, C.byref(sp))))
+                check(lib.tg_rank_scores_shared(b, Cc, d, K, C.byref(sp), ptr(h_src), ptr(P), ptr(nb_src), ptr(snap.nb),
+                                                ptr(src_c), ptr(snap.ids), ptr(scores), Cc, ptr(ws), ws.numel(),
+                                                stream_ptr(dev)), 'tg_rank_scores_shared')
+            else:
+                ws = self._ws('rank', int(lib.tg_rank_scores_gathered_workspace_bytes(b, d, C.byref(sp))))
+                check(lib.tg_rank_scores_gathered(b, Cc, col.shape[1], d, K, C.byref(sp), ptr(h_src), ptr(P), ptr(nb_src),
+                                                  ptr(snap.nb), ptr(src_c), ptr(snap.ids), ptr(col), ptr(scores),
+                                                  col.shape[1], ptr(ws), ws.numel(), stream_ptr(dev)),
+                      'tg_rank_scores_gathered')
+        return scores
+
     def _recommend(self, src_ids, ts, cand, k, mask, exclude_seen, graph, chunk_queries, col_of, uptodate, catalogue_at,
                    stale_ok, subset):
         """the body of recommend (subset None) and recommend_subset"""
@@ -1168,9 +1192,7 @@ class TIGE(nn.Module):
             if subset.dim() != 2 or subset.shape[0] != B:
                 raise ValueError(f'recommend: subset {tuple(subset.shape)} for {B} queries; per-query candidates are int64 [B, Cq]')
             if subset.numel():
-                lo_id, hi_id = torch.aminmax(subset)
-                if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
-                    raise ValueError('recommend: a node id outside [0, n_nodes) in subset')
+                self._check_ids(subset, 'recommend: a node id outside [0, n_nodes) in subset')
         Cq = Cc if subset is None else subset.shape[1]  # score columns per query
         if mask is not None:
             mask = torch.as_tensor(mask).to(dev).bool()
@@ -1180,9 +1202,7 @@ class TIGE(nn.Module):
             elif mask.shape != ((Cc,) if mask.dim() == 1 and shared else (B, Cc)):
                 raise ValueError(f'recommend: mask {tuple(mask.shape)} for cand {tuple(cand.shape)} of {B} queries')
         if B and Cc:
-            lo_id, hi_id = torch.aminmax(torch.cat([src_ids, cand.reshape(-1)]))
-            if int(lo_id) < 0 or int(hi_id) >= self.n_nodes:
-                raise ValueError('recommend: a node id outside [0, n_nodes)')
+            self._check_ids(torch.cat([src_ids, cand.reshape(-1)]), 'recommend: a node id outside [0, n_nodes)')
         sub_col = None
         if subset is not None:  # the snapshot row of every candidate, -1: not in the catalogue
             try:
@@ -1217,7 +1237,6 @@ class TIGE(nn.Module):
         step = max(1, int(chunk_queries) // (Cq + 1))
         if snap is not None:
             from .training import score_struct
-            d, K = self.memory_dim, self.n_neighbors
             with torch.no_grad():
                 self._embed_prepare()
                 sp = score_struct(self)
@@ -1229,16 +1248,10 @@ class TIGE(nn.Module):
                 hip_ops.raise_if_err(err)
         for lo in range(0, B, step):
             hi = min(B, lo + step)
+            nb_c = None if snap is None or nb_all is None else nb_all[lo:hi]
             if subset is not None:  # a per-query subset of the snapshot's rows
-                with torch.no_grad():
-                    src_c, col_c = src_ids[lo:hi], sub_col[lo:hi]
-                    h_src, nb_src = h_all[lo:hi], None if nb_all is None else nb_all[lo:hi]
-                    scores = torch.empty(hi - lo, Cq, dtype=torch.float32, device=dev)
-                    nbytes = int(lib.tg_rank_scores_gathered_workspace_bytes(hi - lo, d, C.byref(sp)))
-                    ws = self._ws('rank', nbytes)
-                    check(lib.tg_rank_scores_gathered(hi - lo, Cc, Cq, d, K, C.byref(sp), ptr(h_src), ptr(P), ptr(nb_src),
-                                                      ptr(snap.nb), ptr(src_c), ptr(snap.ids), ptr(col_c), ptr(scores), Cq,
-                                                      ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_rank_scores_gathered')
+                col_c = sub_col[lo:hi]
+                scores = self._snapshot_scores(snap, P, sp, src_ids[lo:hi], h_all[lo:hi], nb_c, col_c)
                 mk = col_c >= 0
                 if mask is not None:
                     mk = mk & mask[lo:hi]
@@ -1249,15 +1262,7 @@ class TIGE(nn.Module):
             if snap is None:
                 scores = self._pair_scores('recommend', src_ids[lo:hi], ids, ts64[lo:hi], graph, strategy, chunk_queries)
             else:  # the items' rows are the snapshot's
-                with torch.no_grad():
-                    src_c = src_ids[lo:hi]
-                    h_src, nb_src = h_all[lo:hi], None if nb_all is None else nb_all[lo:hi]
-                    scores = torch.empty(hi - lo, Cc, dtype=torch.float32, device=dev)
-                    nbytes = int(lib.tg_rank_scores_shared_workspace_bytes(hi - lo, d, C.byref(sp)))
-                    ws = self._ws('rank', nbytes)
-                    check(lib.tg_rank_scores_shared(hi - lo, Cc, d, K, C.byref(sp), ptr(h_src), ptr(P), ptr(nb_src),
-                                                    ptr(snap.nb), ptr(src_c), ptr(snap.ids), ptr(scores), Cc, ptr(ws),
-                                                    ws.numel(), stream_ptr(dev)), 'tg_rank_scores_shared')
+                scores = self._snapshot_scores(snap, P, sp, src_ids[lo:hi], h_all[lo:hi], nb_c)
             mk = None
             if mask is not None:
                 mk = mask.unsqueeze(0).expand(hi - lo, -1) if mask.dim() == 1 else mask[lo:hi]

@@ -25,6 +25,11 @@ computes what it would have computed, so the equality of the two lines holds und
 --grow lets the model itself start small: its tables and its graph cover the node ids of train + validation only, and the
 ids the test split brings are admitted batch by batch (`TIGE.observe(..., num_node='auto', nfeats=...)`); the ids admitted
 are printed per batch.  Each batch is ranked among the items known at that moment, so there is no offline line beside it.
+--erase_nodes FILE and --retract_eids FILE (each a .npy of ids) take nodes and events out of the online replay before it
+starts (`TIGE.erase`: a closed account, a de-listed item, a cancelled transaction): their entries leave the device graph,
+the erased nodes' memory and mailbox rows are reset, and the entries dropped are printed.  The offline replay beside it
+still has them, so the two lines are not held equal; an erased id that the test split brings back starts as a node never
+seen.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -158,7 +163,8 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=N
 
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-               device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False):
+               device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
+               erase_nodes=None, retract_eids=None):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -175,7 +181,10 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     ranked among the items the model knows at that moment, so the lists differ from the offline replay's (which ranks
     items nobody has seen as well) and no offline replay is made; the metrics carry 'admitted': new ids per batch.  Data
     without a node-feature file get a zero table (the same model: a missing table means zeros).  Needs the sequence
-    restarter."""
+    restarter.
+    erase_nodes / retract_eids (int arrays): `erase(nodes=..., eids=...)` once, on the graph over train + validation,
+    before the online replay; its metrics then carry 'erased': (entries kept, entries dropped), and the two replays are not
+    held equal (the offline one still has the nodes and events)."""
     from www2023tiger_amd.data.graph import Graph
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -222,6 +231,15 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
             model.load_memory_state(start)
         # the edge table already holds the rows of the test events; a live system hands them to observe(efeats=...)
         model.graph = seen()
+        erasing = erase_nodes is not None or retract_eids is not None
+        erased = None
+        if erasing:
+            before = int(model.graph.tcsr.num_entry)
+            g = model.erase(nodes=erase_nodes, eids=retract_eids)
+            erased = (int(g.tcsr.num_entry), before - int(g.tcsr.num_entry))
+            if verbose:
+                print(f'erase: {0 if erase_nodes is None else len(erase_nodes)} nodes, '
+                      f'{0 if retract_eids is None else len(retract_eids)} eids: {erased[0]} entries kept, {erased[1]} dropped')
         forgot = []
         shifted = [0]   # rows released so far: the eids of the events still to come moved down by as much
         rows = []
@@ -263,10 +281,12 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
                                  observe_and_forget if forgetting else observe, known=known if grow else None)
     need = max(n_neighbors, hist_len if restarter_type == 'seq' else 0)
-    if ids_off is not None and (not forgetting or (window is None and keep_last >= need and not exclude_seen)):
+    if ids_off is not None and not erasing and (not forgetting or (window is None and keep_last >= need and not exclude_seen)):
         assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
     if grow:
         online = dict(online, admitted=admitted)
+    if erasing:
+        online = dict(online, erased=erased)
     if forgetting:
         online = dict(online, forgot=forgot)
         if release_rows:
@@ -344,6 +364,10 @@ if __name__ == '__main__':
     ap.add_argument('--grow', action='store_true', help='--online: the model starts with the node ids of train + validation '
                     '(num_node = their largest id + 1) and admits the ids the test split brings (TIGE.observe(..., '
                     "num_node='auto')); prints the ids admitted per batch; no offline replay")
+    ap.add_argument('--erase_nodes', default=None, metavar='FILE', help='--online: a .npy of node ids that are erased once '
+                    'before the replay (TIGE.erase); prints the entries dropped')
+    ap.add_argument('--retract_eids', default=None, metavar='FILE', help='--online: a .npy of edge ids that are retracted '
+                    'once before the replay (TIGE.erase); prints the entries dropped')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -362,7 +386,10 @@ if __name__ == '__main__':
         for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
                                                               seed=a.seed, bs=a.bs, restarter_type=a.restarter_type,
                                                               window=a.window, keep_last=a.keep_last,
-                                                              release_rows=a.release_rows, grow=a.grow)):
+                                                              release_rows=a.release_rows, grow=a.grow,
+                                                              erase_nodes=None if a.erase_nodes is None else np.load(a.erase_nodes),
+                                                              retract_eids=None if a.retract_eids is None
+                                                              else np.load(a.retract_eids))):
             if m is None:
                 continue
             print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "

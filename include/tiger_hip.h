@@ -163,6 +163,45 @@ int tg_tcsr_trim_apply(const tg_tcsr* g, const int64_t* indptr_out, int64_t num_
 int tg_tcsr_trim_host(const tg_tcsr* g, double t_cut, int64_t keep_last, int64_t* indptr_out_host, double* ts_out_host,
                       int32_t* nbr_out_host, int32_t* eid_out_host, int64_t* num_entry_out);
 
+/* Erasing nodes and retracting events (tg_erase.hip): the T-CSR of `g` without the entries of erased nodes and retracted
+ * events, written to caller-owned arrays; `g` itself is only read and num_node does not change.  None of the four entries
+ * has a counterpart in the reference, which builds its adjacency lists once over the whole stream and never takes a node
+ * or an event out (graph.py:11-42).  An entry p of row v is DROPPED iff
+ *   node_bits has bit v   (the owner is erased: it keeps an empty row),
+ *   node_bits has bit nbr[p]   (the partner is erased), or
+ *   eid_bits has bit eid[p] & 0x7FFFFFFF   (the event is retracted: both of its entries name that eid and go together).
+ * - node_bits covers num_node ids, eid_bits n_rows ids, both in the format of tg_bitmap_words / tg_bitmap_mark (int64
+ *   words); either may be NULL (nothing is matched by it).  An eid >= n_rows is never matched by eid_bits; n_rows = 0
+ *   matches nothing.  Both NULL: a copy.
+ * - kept entries keep neighbour id, edge id, the direction flag in bit 31 and the time, bit for bit, and their order -
+ *   a trim keeps a suffix of every row (tg_tcsr_trim_*), this drops an arbitrary subset: a stable stream compaction.
+ *
+ * tg_tcsr_erase_workspace_bytes (graph.py:11-42: no counterpart): bytes of `ws`: with n_tile = ceil(num_entry / 2048),
+ * 256 n_tile (one keep bit per entry) + 4 n_tile + 4 (n_tile + 1), each part rounded up to 16 bytes; 0 for a bad
+ * num_node or num_entry.  The same `ws`, untouched in between, goes to plan and to apply.
+ * tg_tcsr_erase_plan (graph.py:11-42: no counterpart): one launch over tiles of 2048 OLD entries (a hub row is spread
+ * over as many workgroups as it has tiles), one over the tiles, one over the row bounds.  Writes indptr_out[0 .. num_node]
+ * (final; indptr_out[num_node] = number of kept entries) and the keep bits into ws.  The caller reads back that ONE
+ * int64 - the only synchronisation of an erase - to allocate ts_out / nbr_out / eid_out exactly, then calls
+ * tg_tcsr_erase_apply (graph.py:11-42: no counterpart): one launch over the tiles of old entries, num_entry_out =
+ * indptr_out[num_node]; ts_out / nbr_out / eid_out hold exactly num_entry_out entries (they may be NULL when it is 0:
+ * nothing is launched then).
+ * All pointers are DEVICE pointers, ws 16-byte aligned; asynchronous on `stream`; a short workspace returns
+ * TG_EWORKSPACE before anything is launched.  No atomics: the result does not depend on the launch geometry.
+ * TG_EINVAL for num_node outside [1, 2^31), num_entry outside [0, 2^32), a negative n_rows, num_entry_out outside
+ * [0, g->num_entry]. */
+size_t tg_tcsr_erase_workspace_bytes(int64_t num_node, int64_t num_entry);
+int tg_tcsr_erase_plan(const tg_tcsr* g, const int64_t* node_bits, const int64_t* eid_bits, int64_t n_rows,
+                       int64_t* indptr_out, void* ws, size_t ws_bytes, void* stream);
+int tg_tcsr_erase_apply(const tg_tcsr* g, const int64_t* indptr_out, int64_t num_entry_out, double* ts_out,
+                        int32_t* nbr_out, int32_t* eid_out, const void* ws, size_t ws_bytes, void* stream);
+/* tg_tcsr_erase_host (graph.py:11-42: no counterpart): the host twin, HOST pointers (those of `g` and the bitmaps
+ * included), plain C++.  The out arrays have capacity g->num_entry; *num_entry_out = kept entries =
+ * indptr_out_host[num_node]. */
+int tg_tcsr_erase_host(const tg_tcsr* g, const int64_t* node_bits_host, const int64_t* eid_bits_host, int64_t n_rows,
+                       int64_t* indptr_out_host, double* ts_out_host, int32_t* nbr_out_host, int32_t* eid_out_host,
+                       int64_t* num_entry_out);
+
 /* Releasing edge-feature rows (tg_edge_rows.hip; online serving after a trim).  The reference never drops a row of its
  * tables (feature_getter.py:41-47, graph.py:11-42: built once over the whole stream).  A row r of the table
  * T [n_rows, d_e] (float32, d_e % 4 == 0) is LIVE iff r == 0 (the padding row), some entry of g has

@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "tg_sample.h"
+#include "tg_search.h"
 #include "tg_step.h"
 
 namespace tg {
@@ -83,25 +84,6 @@ __global__ void __launch_bounds__(TR_THREADS) k_trim_plan_ptr(int64_t num_node, 
     shift[v] -= o;
   }
   if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1) indptr_out[num_node] = (int64_t)base + (int64_t)blk[blockIdx.x];
-}
-
-// first index i in [lo, hi) with a[i] > x, else hi; a ascending
-__device__ __forceinline__ int64_t upper_bound_i64(const int64_t* __restrict__ a, int64_t lo, int64_t hi, int64_t x) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ uint32_t upper_bound_lds(const uint32_t* a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 struct TrimApplyArgs {

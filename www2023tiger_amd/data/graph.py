@@ -9,8 +9,8 @@ The object is immutable after construction, so the collator thread and the main
 thread may sample concurrently (each call allocates its own outputs and runs on
 the calling thread's current stream).  New events are ingested by `extended`, which
 returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was; old entries
-are dropped by `trimmed` (csrc/tg_trim.hip), which does the same, and `renumbered` gives the entries the row numbers of
-a packed edge table (csrc/tg_edge_rows.hip).
+are dropped by `trimmed` (csrc/tg_trim.hip), which does the same, `without` takes particular nodes and events out
+(csrc/tg_erase.hip), and `renumbered` gives the entries the row numbers of a packed edge table (csrc/tg_edge_rows.hip).
 """
 import ctypes as C
 import itertools
@@ -412,6 +412,100 @@ class Graph:
             ev = self._root.events
             if keep_last is None and ev is not None:  # a horizon alone: still the T-CSR of an event list
                 m = ev[2] >= t_cut
+                child._events = tuple(np.ascontiguousarray(a[m]) for a in ev)
+            if self._mt is not None:
+                child._mt = self._mt
+        return child
+
+    # ---- erasing nodes, retracting events ----------------------------------------------
+    @staticmethod
+    def _erase_ids(what, ids):
+        """an int sequence / tensor of ids -> (int64 array or tensor as given, flattened; min; max), None for None"""
+        if ids is None:
+            return None
+        if torch.is_tensor(ids):
+            if ids.numel() and (ids.dtype.is_floating_point or ids.dtype == torch.bool):
+                raise ValueError(f'without: {what} are integer ids, not {ids.dtype}')
+            ids = ids.detach().to(torch.int64).contiguous().reshape(-1)
+            lo, hi = (int(x) for x in torch.aminmax(ids)) if ids.numel() else (0, -1)
+        else:
+            ids = np.asarray(ids)
+            if ids.size and ids.dtype.kind not in 'iu':
+                raise ValueError(f'without: {what} are integer ids, not {ids.dtype}')
+            ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            lo, hi = (int(ids.min()), int(ids.max())) if ids.size else (0, -1)
+        return ids, lo, hi
+
+    def without(self, nodes=None, eids=None, *, eid_rows: Optional[int] = None) -> 'Graph':
+        """A NEW Graph without the entries of the erased `nodes` and the retracted events `eids` (tg_tcsr_erase_*;
+        graph.py:11-42 has no counterpart: the reference never takes a node or an event out).  An entry is dropped if its
+        owner or its neighbour is one of `nodes`, or if its edge id is one of `eids` (both entries of an event name it and
+        go together); every other entry stays, bit for bit and in order - what `from_arrays` over the events with src, dst
+        not in `nodes` and eid not in `eids` builds (max_node_id = num_node - 1).  num_node does not change: an erased node
+        owns an empty row, and a later `extended` may bring its id back as a node never seen.  nodes / eids: int sequences
+        or tensors, duplicates are fine, an eid that names no entry is a no-op; the bitmaps are built with `new_bitmap` and
+        `bitmap_mark`; eid_rows: the ids the eid bitmap covers (default 1 + max(eids); an eid at or beyond it is not
+        retracted).
+        This graph stays valid and unchanged, and the child holds no reference to it.  A device-resident parent is
+        compacted on the device, on the current stream with allocator-owned buffers: a plan over tiles of the old entries,
+        ONE int64 read back (the number of kept entries - the only synchronisation - so that the child's arrays are
+        allocated exactly), a copy.  A host-only parent takes the host twin at once.  strategy / seed / alpha / device
+        carry over, the child shares the parent's `rng` and device MT19937 state, keeps the parent's latest event time EVEN
+        WHEN EVERY ENTRY WENT and the time-ordered flag, and has a `serial` of its own.  On the host path with a known
+        event list `_events` is the filtered list; on the device path it is None.
+        ValueError before anything is launched: a node id outside [0, num_node), node id 0 (the padding id can never be
+        erased), a negative eid or one beyond 31 bits, both arguments None, an eid_rows that is negative."""
+        from .. import hip_ops
+        if nodes is None and eids is None:
+            raise ValueError('without: pass nodes, eids or both (both None erases nothing)')
+        nd, ed = self._erase_ids('nodes', nodes), self._erase_ids('eids', eids)
+        if nd is not None and len(nd[0]):
+            if nd[1] < 0 or nd[2] >= self.num_node:
+                raise ValueError(f'without: node ids must lie in [0, num_node) (num_node = {self.num_node})')
+            if nd[1] == 0:
+                raise ValueError('without: node id 0 is the padding id and can never be erased')
+        if ed is not None and len(ed[0]) and (ed[1] < 0 or ed[2] > 0x7FFFFFFF):
+            raise ValueError('without: edge ids are non-negative and fit in 31 bits')
+        if eid_rows is None:
+            n_rows = ed[2] + 1 if ed is not None and len(ed[0]) else 0
+        else:
+            n_rows = operator.index(eid_rows)
+            if n_rows < 0 or n_rows > 0x80000000:
+                raise ValueError(f'without: eid_rows = {n_rows} is outside [0, 2^31]')
+        child = Graph.__new__(Graph)
+        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
+        child._time_ordered = self._time_ordered
+        child._t_last = self._t_last
+        if self._dev is not None:  # device-resident parent: plan, one read-back, allocate exactly, apply
+            dev = self._dev[0].device
+            node_bits = eid_bits = None
+            with torch.cuda.device(dev):
+                if nd is not None:
+                    node_bits = hip_ops.new_bitmap(self.num_node, dev)
+                    hip_ops.bitmap_mark(torch.as_tensor(nd[0]).to(dev), node_bits, self.num_node)
+                if ed is not None and n_rows > 0:
+                    eid_bits = hip_ops.new_bitmap(n_rows, dev)
+                    hip_ops.bitmap_mark(torch.as_tensor(ed[0]).to(dev), eid_bits, n_rows)  # (ids >= n_rows are not marked)
+            indptr, P, ws = hip_ops.tcsr_erase_plan(self, node_bits, eid_bits, n_rows if eid_bits is not None else 0)
+            out = (indptr,) + hip_ops.tcsr_erase_apply(self, indptr, P, ws)
+            child._dev = out
+            child._set_struct()
+            child._mt = self._mt_state()
+            child._root.dev = out
+        else:
+            to_np = lambda x: x.cpu().numpy() if torch.is_tensor(x) else x
+            n_ids = to_np(nd[0]) if nd is not None else None
+            e_ids = to_np(ed[0]) if ed is not None else None
+            node_bits = hip_ops.host_bitmap(n_ids, self.num_node) if nd is not None else None
+            eid_bits = hip_ops.host_bitmap(e_ids, n_rows) if ed is not None and n_rows > 0 else None
+            child._host = hip_ops.tcsr_erase_host(self, node_bits, eid_bits, n_rows if eid_bits is not None else 0)
+            ev = self._root.events
+            if ev is not None:  # still the T-CSR of an event list: the filtered one
+                m = np.ones(len(ev[0]), dtype=bool)
+                if nd is not None:
+                    m &= ~np.isin(ev[0], n_ids) & ~np.isin(ev[1], n_ids)
+                if eid_bits is not None:
+                    m &= ~np.isin(ev[3], e_ids[e_ids < n_rows])
                 child._events = tuple(np.ascontiguousarray(a[m]) for a in ev)
             if self._mt is not None:
                 child._mt = self._mt

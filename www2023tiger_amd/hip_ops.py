@@ -679,3 +679,92 @@ def edge_rows_host(graph, table, n_rows: int, keep_from: Optional[int] = None, p
         raise ValueError(f'edge_rows_host: an entry of the graph or a pinned id names no row of the table ({n_rows} rows)')
     check(rc, 'tg_edge_rows_host')
     return remap, (None if t_out is None else t_out[:n_live.value].copy()), eid_out
+
+
+# ---- erasing nodes and retracting events (tg_tcsr_erase_plan / _apply and their host twin) ----------------------------------
+def host_bitmap(ids, n_ids: int):
+    """The bitmap of `new_bitmap` + `bitmap_mark` over n_ids ids as a numpy int64 array (the host twins' format); ids at or
+    beyond n_ids are not marked, duplicates are fine."""
+    import numpy as np
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    ids = ids[(ids >= 0) & (ids < n_ids)]
+    bits = np.zeros(bitmap_words(n_ids), dtype=np.uint64)
+    np.bitwise_or.at(bits, ids >> 6, np.uint64(1) << (ids & 63).astype(np.uint64))
+    return bits.view(np.int64)
+
+
+def _erase_bits(what: str, bits: Optional[Tensor], n_ids: int, dev) -> Optional[Tensor]:
+    if bits is None:
+        return None
+    if (not torch.is_tensor(bits) or bits.dtype != torch.int64 or bits.dim() != 1 or not bits.is_contiguous()
+            or bits.numel() < bitmap_words(n_ids) or bits.device != dev):
+        raise ValueError(f'{what}: a bitmap over {n_ids} ids is a contiguous int64 tensor of {bitmap_words(n_ids)} words on {dev}')
+    return bits
+
+
+def tcsr_erase_plan(graph, node_bits: Optional[Tensor] = None, eid_bits: Optional[Tensor] = None, n_rows: int = 0, device=None):
+    """Which entries of `graph` survive the erasure of the nodes of `node_bits` and the retraction of the events of
+    `eid_bits` (tiger_hip.h: tg_tcsr_erase_plan)?  node_bits: a `new_bitmap` over graph.num_node ids, eid_bits: one over
+    n_rows ids (an eid at or beyond n_rows is never matched); None: nothing is matched by it.  -> (indptr_out int64
+    [num_node + 1], the number of kept entries, ws - the workspace `tcsr_erase_apply` wants back).  Reads ONE int64 back
+    (the kept entries: what the child's arrays are allocated by).  ValueError for a negative n_rows or a bitmap of another
+    dtype, size or device."""
+    import ctypes as C_
+    dev = torch.device(graph.device if device is None else device)
+    if dev.type == 'cpu':
+        raise ValueError('tcsr_erase_plan runs on the device (host arrays: tcsr_erase_host)')
+    n_rows = int(n_rows)
+    if n_rows < 0:
+        raise ValueError(f'tcsr_erase_plan: n_rows = {n_rows} is negative')
+    g, _ = _graph_struct('tcsr_erase_plan', graph, dev)
+    dev = graph._dev[0].device  # (with its index: what the bitmaps are compared with)
+    node_bits = _erase_bits('tcsr_erase_plan: node_bits', node_bits, graph.num_node, dev)
+    eid_bits = _erase_bits('tcsr_erase_plan: eid_bits', eid_bits, n_rows, dev)
+    indptr = torch.empty(graph.num_node + 1, dtype=torch.int64, device=dev)
+    nbytes = int(lib.tg_tcsr_erase_workspace_bytes(g.num_node, g.num_entry))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tg_tcsr_erase_plan(C_.byref(g), ptr(node_bits), ptr(eid_bits), n_rows, ptr(indptr), ptr(ws), nbytes,
+                                     stream_ptr(dev)), 'tg_tcsr_erase_plan')
+        n = int(indptr[-1])  # the one read-back
+    return indptr, n, ws
+
+
+def tcsr_erase_apply(graph, indptr_out: Tensor, num_entry_out: int, ws: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """Copy the kept entries of `graph` (tiger_hip.h: tg_tcsr_erase_apply) with the indptr and the workspace of
+    `tcsr_erase_plan` -> (ts float64, nbr int32, eid int32), each of exactly num_entry_out entries."""
+    import ctypes as C_
+    dev = indptr_out.device
+    g, _ = _graph_struct('tcsr_erase_apply', graph, dev)
+    P = int(num_entry_out)
+    out = (torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+           torch.empty(P, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        # (parent arrays and workspace belong to the caching allocator: reused in stream order, no wait needed)
+        check(lib.tg_tcsr_erase_apply(C_.byref(g), ptr(indptr_out), P, *(ptr(t) for t in out), ptr(ws), ws.numel(),
+                                      stream_ptr(dev)), 'tg_tcsr_erase_apply')
+    return out
+
+
+def tcsr_erase_host(graph, node_bits=None, eid_bits=None, n_rows: int = 0):
+    """The host twin of plan + apply (tiger_hip.h: tg_tcsr_erase_host) over the graph's host arrays and numpy int64 bitmaps
+    (`host_bitmap`) -> (indptr int64 [num_node + 1], ts float64, nbr int32, eid int32: numpy arrays of the kept entries).
+    ValueError as `tcsr_erase_plan`."""
+    import ctypes as C_
+    import numpy as np
+    n_rows = int(n_rows)
+    if n_rows < 0:
+        raise ValueError(f'tcsr_erase_host: n_rows = {n_rows} is negative')
+    h = graph._host_tcsr()
+    for what, bits, n in (('node_bits', node_bits, graph.num_node), ('eid_bits', eid_bits, n_rows)):
+        if bits is not None and (not isinstance(bits, np.ndarray) or bits.dtype != np.int64 or bits.ndim != 1
+                                 or not bits.flags.c_contiguous or len(bits) < bitmap_words(n)):
+            raise ValueError(f'tcsr_erase_host: {what} over {n} ids is a contiguous numpy int64 array of {bitmap_words(n)} words')
+    P0 = len(h[1])
+    g = _lib.TgTcsr(graph.num_node, P0, *(ptr(a) for a in h))
+    out = (np.empty(graph.num_node + 1, dtype=np.int64), np.empty(P0, dtype=np.float64), np.empty(P0, dtype=np.int32),
+           np.empty(P0, dtype=np.int32))
+    kept = C_.c_int64(0)
+    check(lib.tg_tcsr_erase_host(C_.byref(g), ptr(node_bits), ptr(eid_bits), n_rows, *(ptr(a) for a in out), C_.byref(kept)),
+          'tg_tcsr_erase_host')
+    return (out[0],) + tuple(a[:kept.value].copy() for a in out[1:])  # (copies: the full-size arrays die)

@@ -65,11 +65,23 @@ class Memory(nn.Module):
     def device(self):
         return self.vals.device
 
-    def clear(self):
+    def clear(self, nids: Optional[Tensor] = None):
+        """Zero state, as in a freshly built Memory: every row (memory.py:31-34), or - nids: int64 ids, duplicates are
+        fine - the rows of those ids alone (TIGE.erase; memory.py has no counterpart)."""
         self._version_ += 1
-        self.vals.zero_()
-        self.update_ts.zero_()
-        self.active_mask.zero_()
+        if nids is None:
+            self.vals.zero_()
+            self.update_ts.zero_()
+            self.active_mask.zero_()
+            return
+        if len(nids) == 0:
+            return
+        nids = nids.to(self.device).long().reshape(-1)
+        if int(nids.min()) < 0 or int(nids.max()) >= self.n:
+            raise ValueError(f'Memory.clear: a node id outside [0, {self.n})')
+        self.vals.index_fill_(0, nids, 0)
+        self.update_ts.index_fill_(0, nids, 0)
+        self.active_mask.index_fill_(0, nids, False)
 
     def grow(self, n: int, reserve: Optional[int] = None) -> bool:
         """Rows for node ids [self.n, n): zero state, as in a freshly built Memory(n, dim) (online admission of new ids,

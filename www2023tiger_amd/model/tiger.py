@@ -1770,6 +1770,55 @@ class TIGE(nn.Module):
         self.release_edge_rows(keep_from=keep_from, _graph=trimmed)  # (swaps graph and table together, or raises)
         return self.graph
 
+    @torch.no_grad()
+    def erase(self, nodes=None, eids=None, *, release_edge_rows: bool = False, keep_from=None):
+        """Take particular nodes and particular events out of a model that keeps observing (a closed account, a de-listed
+        item, a cancelled or fraudulent transaction) -> the new graph.  The graph is replaced by `graph.without(nodes,
+        eids, eid_rows=rows of the edge table)` through the setter (the restarter follows, snapshot stamps go stale):
+        every entry whose owner or neighbour is one of `nodes`, or whose eid is one of `eids`, is gone, so
+        `walk_candidates`, `trending`, `fill_candidates`, `exclude_seen`, the samplers and the sequence restarter's
+        histories no longer see it.  For every id of `nodes` the rows of both memories (vals, update_ts, active_mask) and
+        the mailbox row (values, time, has_msg bit) are put back to those of a freshly built model - zeros, no message -
+        and nothing else is touched; derived tables (eager updates, query rows) are rebuilt before their next use.
+        (`reset()` clears a mailbox row's bit and leaves its values behind it, where nothing reads them; an erase zeroes
+        them too: the last message of a closed account does not stay in device memory.)
+        nodes / eids: int sequences or tensors, duplicates are fine, an eid that names no entry is a no-op.
+        release_edge_rows=True: the erase is followed by `release_edge_rows(keep_from)`, exactly as in `forget` - the rows
+        that only retracted events named leave the table, the eids are renumbered, the result is `model.last_release`.
+        THE LIMITS:
+          * Rows of OTHER nodes are not touched.  What an erased node or a retracted event contributed to a partner's
+            recurrent memory or to its pending mail cannot be separated out again and stays.
+          * A StaticRestarter's trained per-node embedding is not reset.
+          * The caller's duties are those of `forget` and `release_edge_rows`: captured device graphs and resident
+            evaluation runs built before the call read the old graph (and table) - rebuild them; CatalogueSnapshots held
+            from before are stale; eids held by the caller are in the old numbering after a release.
+          * An erased id that a later `observe` brings back starts as a node never seen.
+        Refused before anything changes: a partitioned model, training mode, and what `Graph.without` refuses (an id
+        outside [0, num_node), node id 0 - the padding id -, a negative eid, both arguments None); with the flag also
+        what `release_edge_rows` refuses, and then nothing at all has changed."""
+        self._refuse_partitioned('erase')
+        if self.training:
+            raise RuntimeError('erase: nodes and events are taken out in eval() mode (the streaming state of a served model)')
+        fg = self.raw_feat_getter
+        rows = None if eids is None or fg.efeats is None else int(fg.efeats.shape[0])
+        child = self.graph.without(nodes, eids, eid_rows=rows)  # (validates; nothing has changed if it raises)
+        ids = None
+        if nodes is not None:
+            ids = torch.as_tensor(nodes).to(self.device).long().reshape(-1)
+        if release_edge_rows:
+            self.release_edge_rows(keep_from=keep_from, _graph=child)  # (swaps graph and table together, or raises)
+        else:
+            self.graph = child
+        if ids is not None and ids.numel():
+            self.left_memory.clear(ids)
+            self.right_memory.clear(ids)
+            S = self.msg_store
+            S.node_msg_vals.index_fill_(0, ids, 0)
+            S.node_msg_ts.index_fill_(0, ids, 0)
+            S.clear(ids)
+        self._touch()
+        return self.graph
+
     last_release = None  # the EdgeRowsRelease of the latest release_edge_rows / forget(release_edge_rows=True)
 
     def release_edge_rows(self, keep_from=None, pin=None, *, slack=None, _graph=None):

@@ -32,7 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from www2023tiger_amd._lib import TgTcsr, check, lib, ptr  # noqa: E402
-from www2023tiger_amd.hip_ops import stream_ptr  # noqa: E402
+from www2023tiger_amd.hip_ops import stream_ptr, tcsr_arrays as out_arrays  # noqa: E402
 
 SHAPES = {
     'c2': dict(n_u=8227, n_i=1000, E=157474, T=2.68e6, appends=(200, 1024)),
@@ -52,11 +52,6 @@ def device_stream(cfg, dev):
         return (src, dst, ts, torch.arange(1, E + 1, device=dev)), N
     st = bench.make_stream(cfg['n_u'], cfg['n_i'], cfg['E'], cfg['T'], seed=0, with_efeats=False)
     return tuple(torch.from_numpy(st[k]).to(dev) for k in ('src', 'dst', 'ts', 'eids')), st['n_nodes']
-
-
-def out_arrays(N, P, dev):
-    return (torch.empty(N + 1, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.float64, device=dev),
-            torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev))
 
 
 def pct(xs, q):

@@ -53,14 +53,7 @@ def device_graph(ev, N, dev):
     ws = torch.empty(max(bw, 16), dtype=torch.uint8, device=dev)
     check(lib.tg_tcsr_build_device(E, *(ptr(a) for a in ev), N, *(ptr(a) for a in out), ptr(ws), bw, stream_ptr(dev)), 'build')
     torch.cuda.synchronize()
-    g = Graph.__new__(Graph)
-    g._init_common(N, 'recent_edges', 0, 0.0, dev)
-    g._time_ordered = True
-    g._t_last = float(ev[2][-1]) if E else -np.inf
-    g._dev = out
-    g._root.dev = out
-    g._set_struct()
-    return g
+    return Graph._from_device_arrays(out, float(ev[2][-1]) if E else -np.inf, True, strategy='recent_edges', seed=0)
 
 
 def timed(fn):

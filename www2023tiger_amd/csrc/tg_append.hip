@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "tg_step.h"
+#include "tg_tcsr.h"
 
 namespace tg {
 
@@ -35,24 +36,6 @@ constexpr int AP_WIN = 4096;               // cut points of one copy tile staged
 
 __device__ __forceinline__ int64_t entry_owner(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, uint32_t j) {
   return (j & 1u) ? dst[j >> 1] : src[j >> 1];
-}
-
-// first index in [lo, hi) with a[i] > x (upper) / a[i] >= x (lower); a ascending
-__device__ __forceinline__ uint32_t upper_bound_u32(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t x) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t x) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // steps 1-2, m <= AP_SMALL: one workgroup, bitonic sort of M2 = pow2 >= m keys in LDS (padding keys sort last)
@@ -160,10 +143,7 @@ __global__ void __launch_bounds__(AP_THREADS) k_append_apply(AppendArgs a) {
     if (p >= p1) break;
     uint32_t shift = lo;
     if (nwin) shift += staged ? upper_bound_u32(win, 0u, nwin, (uint32_t)p) : upper_bound_u32(a.INS, lo, hi, (uint32_t)p) - lo;
-    const uint64_t q = p + shift;
-    a.ts_out[q] = a.g.ts[p];
-    a.nbr_out[q] = a.g.nbr[p];
-    a.eid_out[q] = a.g.eid[p];
+    move_entry(a.g, (int64_t)p, a.ts_out, a.nbr_out, a.eid_out, (int64_t)(p + shift));
   }
 }
 

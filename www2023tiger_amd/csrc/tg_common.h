@@ -140,6 +140,15 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave
   __syncthreads();
   return base + inc - v;
 }
+// Sum of totals[0 .. n_front) on every thread of a 256-thread block: workgroup b of a two-launch scan (one total per
+// workgroup from the first launch) sums the totals of the workgroups in front of it - no third scan launch.
+__device__ __forceinline__ uint32_t block_sum_front(const uint32_t* totals, uint32_t n_front, uint32_t* s_wave /*[4]*/) {
+  uint32_t mine = 0;
+  for (uint32_t i = threadIdx.x; i < n_front; i += TG_SCAN_BLOCK) mine += totals[i];
+  uint32_t sum;
+  block_excl_scan(mine, s_wave, &sum);
+  return sum;
+}
 
 // 8 flag bytes (each 0/1) -> 8 bits
 __device__ __forceinline__ uint64_t pack8(uint64_t x) { return ((x & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56; }

@@ -11,8 +11,8 @@
 //          into a flag word instead.  Marks and flag are zeroed by a memset node in front.
 //   scan A (k_er_scan_rows, one workgroup per 2048 rows): a thread loads its 8 marks as one 8-byte word, adds row 0 and
 //          the tail, counts; exclusive scan inside the workgroup, one total per workgroup.
-//   scan B (k_er_scan_emit, the same grid): workgroup b sums the b totals in front of it (as k_trim_plan_ptr does - no
-//          third scan launch) and writes remap, the inverse list old_of[new] and n_live (-1 if the flag is set; then
+//   scan B (k_er_scan_emit, the same grid): workgroup b sums the b totals in front of it (block_sum_front: no third
+//          scan launch) and writes remap, the inverse list old_of[new] and n_live (-1 if the flag is set; then
 //          remap is not written at all).
 //   apply  (k_er_copy_rows, one workgroup per tile of whole OUTPUT rows, about 4096 float4): the tile's old_of values
 //          are staged once in LDS; the lanes then sweep the tile's float4s in output order - stores are contiguous over
@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "tg_step.h"
+#include "tg_tcsr.h"
 
 namespace tg {
 
@@ -93,10 +94,7 @@ __global__ void __launch_bounds__(ER_THREADS) k_er_scan_emit(const uint8_t* __re
     if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1) *n_live = -1;
     return;
   }
-  uint32_t mine = 0;
-  for (unsigned i = threadIdx.x; i < blockIdx.x; i += ER_THREADS) mine += blk[i];
-  uint32_t base;
-  block_excl_scan(mine, s_w, &base);  // (the total: live rows in front of this chunk)
+  const uint32_t base = block_sum_front(blk, blockIdx.x, s_w);  // live rows in front of this chunk
   const int64_t slot = (int64_t)blockIdx.x * ER_THREADS + threadIdx.x;
   const int64_t r0 = slot * ER_MARKS;
   if (r0 < n_rows) {
@@ -220,8 +218,7 @@ extern "C" int tg_edge_rows_plan(const tg_tcsr* g, int64_t n_rows, int64_t keep_
   if (keep_from < 0 || keep_from > n_rows || n_pin < 0 || n_pin > 0xffffffffLL || (n_pin > 0 && !pin)) return TG_EINVAL;
   if (!remap || !n_live_dev || (reinterpret_cast<uintptr_t>(remap) & 15)) return TG_EINVAL;
   const ErLayout l = er_layout(n_rows);
-  if (!ws || ws_bytes < l.total) return TG_EWORKSPACE;  // before the first launch
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, l.total)) return rc;  // before the first launch
   hipStream_t st = as_stream(stream);
   char* base = static_cast<char*>(ws);
   uint8_t* marks = reinterpret_cast<uint8_t*>(base + l.marks);
@@ -254,8 +251,7 @@ extern "C" int tg_edge_rows_apply(const tg_tcsr* g, const float* table, int64_t 
   if (table && (d_e < 4 || d_e % 4 != 0 || !table_out)) return TG_EINVAL;
   if (table && ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(table_out)) & 15)) return TG_EINVAL;
   const ErLayout l = er_layout(n_rows);
-  if (!ws || ws_bytes < l.total) return TG_EWORKSPACE;
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, l.total)) return rc;
   hipStream_t st = as_stream(stream);
   if (table) {
     ErCopyArgs a{};

@@ -5,17 +5,17 @@
 // An entry p of row v is DROPPED iff node_bits has bit v (the owner is erased), node_bits has bit nbr[p] (the partner is
 // erased) or eid_bits has bit eid[p] & 0x7FFFFFFF (the event is retracted; an eid >= n_rows is never matched).  Every other
 // entry is kept with its time, neighbour, eid (bit 31 included) and order.  Unlike a trim (tg_trim.hip: every row keeps a
-// suffix) an arbitrary subset of every row goes, so this is a stable stream compaction over the ENTRIES; the rows follow
+// suffix; what the two share is in tg_tcsr.h) an arbitrary subset of every row goes, so this is a stable stream compaction over the ENTRIES; the rows follow
 // from where their first old entry lands.  All passes are entry-parallel over tiles of ES_TILE = 2048 OLD entries: a hub
 // row is spread over as many workgroups as it has tiles.
 //   flags  (k_erase_flags, one workgroup per tile): lane l takes entries base + l + 256 i: loads coalesce.  The owner of
 //           an entry is an upper bound in indptr; the workgroup searches once for the owners of its first and last entry
-//           and stages that window of indptr in LDS (up to ES_WIN rows; a tile that spans more - thousands of empty rows
-//           - searches global memory).  No owner is looked for without node_bits.  The keep flags leave as ballot words,
+//           and stages that window of indptr in LDS (row_window, tg_tcsr.h: up to ES_WIN rows; a tile that spans more -
+//           thousands of empty rows - searches global memory).  No owner is looked for without node_bits.  The keep flags leave as ballot words,
 //           1 bit per entry in entry order (32 words of 64 bits per tile, bits past num_entry are 0), and one kept-count
 //           per tile.
 //   bases  (k_erase_bases, one workgroup per 256 tiles): workgroup b sums the counts of the tiles in front of its chunk
-//           (as k_trim_plan_ptr does - no third scan launch) and scans its own: base[s] = kept entries in front of tile s,
+//           (block_sum_front: no third scan launch) and scans its own: base[s] = kept entries in front of tile s,
 //           s in [0, n_tile]; base[n_tile] is the total.
 //   ptr    (k_erase_ptr, one workgroup per 256 of the num_node + 1 row bounds): indptr_out[v] = base of indptr[v]'s
 //           tile + the popcount of the keep bits in front of indptr[v] inside that tile (at most 31 words and a part).
@@ -28,7 +28,7 @@
 // chunk), integer work and bit copies: device, host twin and numpy agree bit for bit.
 #include <algorithm>
 
-#include "tg_search.h"
+#include "tg_tcsr.h"
 #include "tg_step.h"
 
 namespace tg {
@@ -54,22 +54,10 @@ __global__ void __launch_bounds__(ES_THREADS) k_erase_flags(EraseFlagArgs a) {
   const uint32_t t = threadIdx.x, lane = t & (TG_WAVE - 1), wv = t / TG_WAVE;
   const int64_t N = a.g.num_node, P = a.g.num_entry;
   const int64_t p0 = (int64_t)blockIdx.x * ES_TILE, p1 = min(p0 + ES_TILE, P);
-  int64_t lo = 0, hi = 0;
-  uint32_t nwin = 0;
-  bool staged = true;  // block-uniform
-  if (a.node_bits) {
-    // owner(p) = (first v in [1, N) with indptr[v] > p, else N) - 1: a row of the graph whatever indptr holds
-    lo = upper_bound_i64(a.g.indptr, 1, N, p0) - 1;
-    // (most tiles span a few rows: the owner of the last entry is galloped for from the first one's)
-    int64_t reach = 1;
-    while (lo + reach < N && a.g.indptr[lo + reach] <= p1 - 1) reach <<= 1;
-    hi = upper_bound_i64(a.g.indptr, lo + 1, min(lo + reach + 1, N), p1 - 1) - 1;
-    staged = hi - lo <= (int64_t)ES_WIN;
-    if (staged) {
-      nwin = (uint32_t)(hi - lo);
-      for (uint32_t i = t; i < nwin; i += ES_THREADS) win[i] = (uint32_t)a.g.indptr[lo + 1 + i];
-      __syncthreads();
-    }
+  RowWindow w{};
+  if (a.node_bits) {  // (no owner is looked for without node_bits: no window, no search)
+    w = row_window<ES_THREADS>(a.g.indptr, N, p0, p1 - 1, win, ES_WIN);
+    if (w.staged) __syncthreads();
   }
   uint32_t kept = 0;  // (the same value on every lane of a wavefront)
 #pragma unroll
@@ -79,8 +67,7 @@ __global__ void __launch_bounds__(ES_THREADS) k_erase_flags(EraseFlagArgs a) {
     if (p < p1) {
       keep = true;
       if (a.node_bits) {
-        const int64_t v = staged ? lo + (int64_t)upper_bound_lds(win, nwin, (uint32_t)p)
-                                 : upper_bound_i64(a.g.indptr, lo + 1, hi + 1, p) - 1;
+        const int64_t v = w.owner(p);
         const int64_t u = (int64_t)a.g.nbr[p];
         if (bm_test(a.node_bits, v)) keep = false;
         if (u >= 0 && u < N && bm_test(a.node_bits, u)) keep = false;  // (an id that is no node: no bit to read)
@@ -109,10 +96,7 @@ __global__ void __launch_bounds__(ES_THREADS) k_erase_bases(int64_t n_tile, cons
                                                             uint32_t* __restrict__ base) {
   __shared__ uint32_t s_w[ES_WAVES];
   const int64_t s0 = (int64_t)blockIdx.x * ES_THREADS;
-  uint32_t mine = 0;
-  for (int64_t i = threadIdx.x; i < s0; i += ES_THREADS) mine += cnt[i];
-  uint32_t front;
-  block_excl_scan(mine, s_w, &front);  // (the total: kept entries in front of this chunk)
+  const uint32_t front = block_sum_front(cnt, (uint32_t)s0, s_w);  // kept entries in front of this chunk (s0 <= n_tile < 2^22)
   const int64_t s = s0 + threadIdx.x;
   uint32_t total;
   const uint32_t r = block_excl_scan(s < n_tile ? cnt[s] : 0u, s_w, &total);
@@ -179,9 +163,7 @@ __global__ void __launch_bounds__(ES_THREADS) k_erase_apply(EraseApplyArgs a) {
     const int64_t p = p0 + (int64_t)i * ES_THREADS + t;
     const int64_t q = q0 + (int64_t)s_pref[j] + (int64_t)__popcll(w & ((1ull << lane) - 1ull));
     if (p >= a.g.num_entry || q >= a.P_out) continue;  // (a workspace that is no plan of this graph: nothing out of bounds)
-    a.ts_out[q] = a.g.ts[p];
-    a.nbr_out[q] = a.g.nbr[p];
-    a.eid_out[q] = a.g.eid[p];
+    move_entry(a.g, p, a.ts_out, a.nbr_out, a.eid_out, q);
   }
 }
 
@@ -199,14 +181,6 @@ static EraseLayout erase_layout(int64_t num_entry) {
   return l;
 }
 
-// (the range checks of a trim: tg_trim.hip)
-static int erase_args(const tg_tcsr* g) {
-  if (!g || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || g->num_entry > 0xffffffffLL || !g->indptr)
-    return TG_EINVAL;
-  if (g->num_entry > 0 && (!g->ts || !g->nbr || !g->eid)) return TG_EINVAL;
-  return TG_OK;
-}
-
 static inline bool host_bit(const int64_t* bits, int64_t id) { return ((uint64_t)bits[id >> 6] >> (id & 63)) & 1ull; }
 
 }  // namespace tg
@@ -220,11 +194,10 @@ extern "C" size_t tg_tcsr_erase_workspace_bytes(int64_t num_node, int64_t num_en
 
 extern "C" int tg_tcsr_erase_plan(const tg_tcsr* g, const int64_t* node_bits, const int64_t* eid_bits, int64_t n_rows,
                                   int64_t* indptr_out, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = erase_args(g)) return rc;
+  if (int rc = tcsr_args(g)) return rc;
   if (!indptr_out || n_rows < 0) return TG_EINVAL;
   const EraseLayout l = erase_layout(g->num_entry);
-  if (!ws || ws_bytes < l.total) return TG_EWORKSPACE;  // before the first launch
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, l.total)) return rc;  // before the first launch
   hipStream_t st = as_stream(stream);
   char* base = static_cast<char*>(ws);
   uint64_t* words = reinterpret_cast<uint64_t*>(base + l.words);
@@ -243,12 +216,11 @@ extern "C" int tg_tcsr_erase_plan(const tg_tcsr* g, const int64_t* node_bits, co
 
 extern "C" int tg_tcsr_erase_apply(const tg_tcsr* g, const int64_t* indptr_out, int64_t num_entry_out, double* ts_out,
                                    int32_t* nbr_out, int32_t* eid_out, const void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = erase_args(g)) return rc;
+  if (int rc = tcsr_args(g)) return rc;
   if (!indptr_out || num_entry_out < 0 || num_entry_out > g->num_entry) return TG_EINVAL;
   if (num_entry_out > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
   const EraseLayout l = erase_layout(g->num_entry);
-  if (!ws || ws_bytes < l.total) return TG_EWORKSPACE;
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, l.total)) return rc;
   if (num_entry_out == 0) return TG_OK;
   const char* base = static_cast<const char*>(ws);
   EraseApplyArgs a{*g, reinterpret_cast<const uint64_t*>(base + l.words), reinterpret_cast<const uint32_t*>(base + l.base),
@@ -261,7 +233,7 @@ extern "C" int tg_tcsr_erase_apply(const tg_tcsr* g, const int64_t* indptr_out, 
 extern "C" int tg_tcsr_erase_host(const tg_tcsr* g, const int64_t* node_bits, const int64_t* eid_bits, int64_t n_rows,
                                   int64_t* indptr_out, double* ts_out, int32_t* nbr_out, int32_t* eid_out,
                                   int64_t* num_entry_out) {
-  if (int rc = erase_args(g)) return rc;
+  if (int rc = tcsr_args(g)) return rc;
   if (!indptr_out || !num_entry_out || n_rows < 0) return TG_EINVAL;
   if (g->num_entry > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
   int64_t q = 0;

@@ -218,10 +218,7 @@ __global__ void __launch_bounds__(TG_SCAN_BLOCK) k_involved_pack(InvolvedEmitArg
 // workgroup b lists the words of block b of k_involved_pack
 __global__ void __launch_bounds__(TG_SCAN_BLOCK) k_involved_emit(InvolvedEmitArgs a) {
   __shared__ uint32_t s_w[TG_SCAN_BLOCK / TG_WAVE];
-  uint32_t mine = 0;
-  for (unsigned i = threadIdx.x; i < blockIdx.x; i += TG_SCAN_BLOCK) mine += a.blk[i];
-  uint32_t base;
-  block_excl_scan(mine, s_w, &base);  // (the total: set bits in front of this block)
+  const uint32_t base = block_sum_front(a.blk, blockIdx.x, s_w);  // set bits in front of this block
   const int lane = lane_id();
   const int64_t w0 = (int64_t)blockIdx.x * TG_SCAN_BLOCK, w1 = min(a.W, w0 + TG_SCAN_BLOCK);
   for (int64_t w = w0 + (threadIdx.x >> 6); w < w1; w += TG_SCAN_BLOCK / TG_WAVE)

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "tg_sample.h"
+#include "tg_tcsr.h"
 
 namespace tg {
 
@@ -442,8 +443,7 @@ extern "C" int tg_trending(const tg_tcsr* g, double t_lo, double t_hi, const int
   int64_t n = 0;
   if (int rc = trend_args(g, t_lo, t_hi, among, M, T, ids, counts, n_valid, n_distinct, &n)) return rc;
   const TrendPlan p = trend_plan(n, T);
-  if (!ws || ws_bytes < p.bytes) return TG_EWORKSPACE;
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, p.bytes)) return rc;
   hipStream_t st = as_stream(stream);
   unsigned char* base = static_cast<unsigned char*>(ws);
   uint64_t* keys = reinterpret_cast<uint64_t*>(base);

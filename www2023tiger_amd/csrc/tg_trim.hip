@@ -7,21 +7,21 @@
 //   plan A (k_trim_plan_rows, one workgroup per 256 nodes): s and the kept length per node (with a horizon: 16 lanes per
 //           node search the cut together, sixteen nodes per round; with a cap alone: one thread per node, no search), an
 //           exclusive scan of the lengths inside the workgroup, one total per workgroup.
-//   plan B (k_trim_plan_ptr, the same grid): workgroup b sums the b totals in front of it (as k_involved_emit does - no
-//           third scan launch), writes indptr_out (indptr_out[num_node] = kept entries) and turns the row starts into
+//   plan B (k_trim_plan_ptr, the same grid): workgroup b sums the b totals in front of it (block_sum_front: no third
+//           scan launch), writes indptr_out (indptr_out[num_node] = kept entries) and turns the row starts into
 //           shift[v] = s_v - indptr_out[v] >= 0, non-decreasing in v.
 //   apply  (k_trim_apply, one workgroup per 2048 KEPT entries): lane l takes kept entry q = base + l, its owner is an
 //           upper bound in indptr_out, its old position q + shift[owner].  The workgroup searches once for the owners of
-//           its first and last entry and stages that window of indptr_out and shift in LDS (up to TR_WIN rows; a tile that
-//           spans more - tens of thousands of empty rows - searches global memory).  Loads and stores coalesce whatever was
-//           dropped, and a hub row is spread over as many workgroups as it has tiles.
+//           its first and last entry and stages that window of indptr_out (row_window, tg_tcsr.h) and shift in LDS (up to
+//           TR_WIN rows; a tile that spans more - tens of thousands of empty rows - searches global memory).  Loads and
+//           stores coalesce whatever was dropped, and a hub row is spread over as many workgroups as it has tiles.
 // No atomics (the result does not depend on the launch geometry), no grid is capped (every workgroup owns one chunk / tile),
 // integer work and one float64 comparison: device, host twin and numpy agree bit for bit.
 #include <algorithm>
 #include <cmath>
 
 #include "tg_sample.h"
-#include "tg_search.h"
+#include "tg_tcsr.h"
 #include "tg_step.h"
 
 namespace tg {
@@ -73,10 +73,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_trim_plan_ptr(int64_t num_node, 
                                                               const uint32_t* __restrict__ blk,
                                                               int64_t* __restrict__ indptr_out) {
   __shared__ uint32_t s_w[TR_THREADS / TG_WAVE];
-  uint32_t mine = 0;
-  for (unsigned i = threadIdx.x; i < blockIdx.x; i += TR_THREADS) mine += blk[i];
-  uint32_t base;
-  block_excl_scan(mine, s_w, &base);  // (the total: kept entries in front of this chunk)
+  const uint32_t base = block_sum_front(blk, blockIdx.x, s_w);  // kept entries in front of this chunk
   const int64_t v = (int64_t)blockIdx.x * TR_THREADS + threadIdx.x;
   if (v < num_node) {
     const uint32_t o = base + rank[v];
@@ -98,19 +95,10 @@ __global__ void __launch_bounds__(TR_THREADS) k_trim_apply(TrimApplyArgs a) {
   __shared__ uint32_t win[TR_WIN];     // indptr_out[lo + 1 .. hi]: where the rows after the first one begin
   __shared__ uint32_t sh[TR_WIN + 1];  // shift[lo .. hi]
   const uint32_t t = threadIdx.x;
-  const int64_t N = a.g.num_node;
   const int64_t q0 = (int64_t)blockIdx.x * TR_TILE, q1 = min(q0 + TR_TILE, a.P);
-  // owner(q) = (first v in [1, N) with indptr_out[v] > q, else N) - 1: a row of the graph whatever indptr_out holds
-  const int64_t lo = upper_bound_i64(a.indptr_out, 1, N, q0) - 1;
-  // (most tiles span a few rows: the owner of the last entry is galloped for from the first one's)
-  int64_t reach = 1;
-  while (lo + reach < N && a.indptr_out[lo + reach] <= q1 - 1) reach <<= 1;
-  const int64_t hi = upper_bound_i64(a.indptr_out, lo + 1, min(lo + reach + 1, N), q1 - 1) - 1;
-  const uint32_t nwin = (uint32_t)min(hi - lo, (int64_t)TR_WIN + 1);
-  const bool staged = hi - lo <= (int64_t)TR_WIN;  // block-uniform
-  if (staged) {
-    for (uint32_t i = t; i < nwin; i += TR_THREADS) win[i] = (uint32_t)a.indptr_out[lo + 1 + i];
-    for (uint32_t i = t; i <= nwin; i += TR_THREADS) sh[i] = a.shift[lo + i];
+  const RowWindow w = row_window<TR_THREADS>(a.indptr_out, a.g.num_node, q0, q1 - 1, win, TR_WIN);
+  if (w.staged) {
+    for (uint32_t i = t; i <= w.nwin; i += TR_THREADS) sh[i] = a.shift[w.lo + i];
     __syncthreads();
   }
 #pragma unroll
@@ -118,13 +106,11 @@ __global__ void __launch_bounds__(TR_THREADS) k_trim_apply(TrimApplyArgs a) {
     const int64_t q = q0 + (int64_t)i * TR_THREADS + t;  // lane l takes entry base + l: loads and stores coalesce
     if (q >= q1) break;
     uint32_t s;
-    if (staged) s = sh[upper_bound_lds(win, nwin, (uint32_t)q)];
-    else s = a.shift[upper_bound_i64(a.indptr_out, lo + 1, hi + 1, q) - 1];
+    if (w.staged) s = sh[w.slot(q)];
+    else s = a.shift[w.searched(q)];
     const int64_t p = q + (int64_t)s;
     if (p >= a.g.num_entry) continue;  // (an indptr_out that is no plan of this graph: nothing is read out of bounds)
-    a.ts_out[q] = a.g.ts[p];
-    a.nbr_out[q] = a.g.nbr[p];
-    a.eid_out[q] = a.g.eid[p];
+    move_entry(a.g, p, a.ts_out, a.nbr_out, a.eid_out, q);
   }
 }
 
@@ -140,13 +126,6 @@ static TrimLayout trim_layout(int64_t num_node) {
   return l;
 }
 
-static int trim_args(const tg_tcsr* g) {
-  if (!g || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || g->num_entry > 0xffffffffLL || !g->indptr)
-    return TG_EINVAL;
-  if (g->num_entry > 0 && (!g->ts || !g->nbr || !g->eid)) return TG_EINVAL;
-  return TG_OK;
-}
-
 }  // namespace tg
 
 using namespace tg;
@@ -158,11 +137,10 @@ extern "C" size_t tg_tcsr_trim_workspace_bytes(int64_t num_node) {
 
 extern "C" int tg_tcsr_trim_plan(const tg_tcsr* g, double t_cut, int64_t keep_last, int64_t* indptr_out, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (int rc = trim_args(g)) return rc;
+  if (int rc = tcsr_args(g)) return rc;
   if (!indptr_out || std::isnan(t_cut)) return TG_EINVAL;
   const TrimLayout l = trim_layout(g->num_node);
-  if (!ws || ws_bytes < l.total) return TG_EWORKSPACE;  // before the first launch
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, l.total)) return rc;  // before the first launch
   hipStream_t st = as_stream(stream);
   char* base = static_cast<char*>(ws);
   uint32_t* shift = reinterpret_cast<uint32_t*>(base + l.shift);
@@ -180,12 +158,11 @@ extern "C" int tg_tcsr_trim_plan(const tg_tcsr* g, double t_cut, int64_t keep_la
 
 extern "C" int tg_tcsr_trim_apply(const tg_tcsr* g, const int64_t* indptr_out, int64_t num_entry_out, double* ts_out,
                                   int32_t* nbr_out, int32_t* eid_out, const void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = trim_args(g)) return rc;
+  if (int rc = tcsr_args(g)) return rc;
   if (!indptr_out || num_entry_out < 0 || num_entry_out > g->num_entry) return TG_EINVAL;
   if (num_entry_out > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
   const TrimLayout l = trim_layout(g->num_node);
-  if (!ws || ws_bytes < l.total) return TG_EWORKSPACE;
-  if (reinterpret_cast<uintptr_t>(ws) & 15) return TG_EINVAL;
+  if (int rc = ws_check(ws, ws_bytes, l.total)) return rc;
   if (num_entry_out == 0) return TG_OK;
   TrimApplyArgs a{*g, indptr_out, reinterpret_cast<const uint32_t*>(static_cast<const char*>(ws) + l.shift), num_entry_out,
                   ts_out, nbr_out, eid_out};
@@ -196,7 +173,7 @@ extern "C" int tg_tcsr_trim_apply(const tg_tcsr* g, const int64_t* indptr_out, i
 // The host twin: plain C++ over host pointers.
 extern "C" int tg_tcsr_trim_host(const tg_tcsr* g, double t_cut, int64_t keep_last, int64_t* indptr_out, double* ts_out,
                                  int32_t* nbr_out, int32_t* eid_out, int64_t* num_entry_out) {
-  if (int rc = trim_args(g)) return rc;
+  if (int rc = tcsr_args(g)) return rc;
   if (!indptr_out || !num_entry_out || std::isnan(t_cut)) return TG_EINVAL;
   if (g->num_entry > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
   int64_t q = 0;

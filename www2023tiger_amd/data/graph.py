@@ -22,7 +22,7 @@ import torch
 from torch import Tensor
 
 from .._lib import TgTcsr, check, lib, ptr
-from ..hip_ops import stream_ptr
+from ..hip_ops import stream_ptr, tcsr_arrays, tcsr_compacted, tcsr_compacted_host
 
 
 class _HostRoot:
@@ -120,8 +120,7 @@ class Graph:
         if old.host is not None or old.events is None or not self._time_ordered:
             self._host_of(old)
             n = len(src)
-            h = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(len(old.host[1]) + 2 * n, dtype=np.float64),
-                 np.empty(len(old.host[1]) + 2 * n, dtype=np.int32), np.empty(len(old.host[1]) + 2 * n, dtype=np.int32))
+            h = tcsr_arrays(self.num_node, len(old.host[1]) + 2 * n)
             # (the root may cover fewer ids than this graph: a chain that admitted new ones - `extended(num_node=)`)
             g = TgTcsr(old.num_node, len(old.host[1]), *(ptr(a) for a in old.host))
             check(lib.tg_tcsr_append_grow_host(C.byref(g), self.num_node, n, ptr(src), ptr(dst), ptr(ts), ptr(eids),
@@ -154,8 +153,7 @@ class Graph:
     def _build_host(self, events, num_node):
         src, dst, ts, eids = events
         E = len(src)
-        h = (np.empty(num_node + 1, dtype=np.int64), np.empty(2 * E, dtype=np.float64),
-             np.empty(2 * E, dtype=np.int32), np.empty(2 * E, dtype=np.int32))
+        h = tcsr_arrays(num_node, 2 * E)
         check(lib.tg_tcsr_build_host(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), num_node, *(ptr(a) for a in h)),
               'tg_tcsr_build_host')
         return h
@@ -183,14 +181,13 @@ class Graph:
     def _build_on_device(self, dev):
         src, dst, ts, eids = (torch.from_numpy(a).to(dev) for a in self._events)
         E = src.numel()
-        out = (torch.empty(self.num_node + 1, dtype=torch.int64, device=dev),
-               torch.empty(2 * E, dtype=torch.float64, device=dev), torch.empty(2 * E, dtype=torch.int32, device=dev),
-               torch.empty(2 * E, dtype=torch.int32, device=dev))
+        out = tcsr_arrays(self.num_node, 2 * E, dev)
         nbytes = int(lib.tg_tcsr_build_device_workspace_bytes(E, self.num_node))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        check(lib.tg_tcsr_build_device(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), self.num_node, *(ptr(t) for t in out),
-                                       ptr(ws), nbytes, stream_ptr(dev)), 'tg_tcsr_build_device')
-        torch.cuda.current_stream(dev).synchronize()  # the inputs and the workspace die with this scope
+        with torch.cuda.device(dev):
+            check(lib.tg_tcsr_build_device(E, ptr(src), ptr(dst), ptr(ts), ptr(eids), self.num_node, *(ptr(t) for t in out),
+                                           ptr(ws), nbytes, stream_ptr(dev)), 'tg_tcsr_build_device')
+            torch.cuda.current_stream(dev).synchronize()  # the inputs and the workspace die with this scope
         return out
 
     @classmethod
@@ -237,6 +234,44 @@ class Graph:
             st = np.concatenate([key.astype(np.uint32), np.array([pos], dtype=np.uint32)]).view(np.int32)
             self._mt = torch.from_numpy(st.copy()).to(self.device)
         return self._mt
+
+    # ---- deriving a graph from a graph ------------------------------------------------
+    def _child(self, num_node=None) -> 'Graph':
+        """A NEW Graph that carries this one over: strategy / seed / alpha / device, the SAME `rng` object, the time-ordered
+        flag and the latest event time; num_node unless overridden (`extended`); a serial of its own and no arrays yet."""
+        child = Graph.__new__(Graph)
+        child._init_common(self.num_node if num_node is None else num_node, self.strategy, self.seed, self.alpha, self._device,
+                           rng=self.rng)
+        child._time_ordered = self._time_ordered
+        child._t_last = self._t_last
+        return child
+
+    def _adopt_device(self, arrays, parent: Optional['Graph'] = None) -> 'Graph':
+        """Make the device arrays this graph's own (host view: downloaded on first use); the MT19937 state is the parent's."""
+        self._dev = self._root.dev = tuple(arrays)
+        self._set_struct()
+        if parent is not None:
+            self._mt = parent._mt_state()
+        return self
+
+    def _adopt_host(self, arrays, events, parent: 'Graph') -> 'Graph':
+        """Make the host arrays this graph's own, and `events` (if not None) the event list they are the T-CSR of.  The
+        device MT19937 state is the parent's IF IT HAS ONE, else None: derived from the shared `rng` on first use.  (The child of
+        `extended` adopts nothing - it shares `_root` and `_log` - and takes that state on the device path only, never here.)"""
+        self._host = tuple(arrays)
+        if events is not None:
+            self._events = events
+        if parent._mt is not None:
+            self._mt = parent._mt
+        return self
+
+    @classmethod
+    def _from_device_arrays(cls, arrays, t_last, time_ordered: bool, strategy='recent_nodes', seed=None) -> 'Graph':
+        """a device-resident Graph over T-CSR arrays built on their device (no event list, as a graph trimmed there)"""
+        self = cls.__new__(cls)
+        self._init_common(arrays[0].numel() - 1, strategy, seed, 0.0, arrays[0].device)
+        self._time_ordered, self._t_last = bool(time_ordered), t_last
+        return self._adopt_device(arrays)
 
     # ---- online ingestion -----------------------------------------------------------
     def extended(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None, num_node=None) -> 'Graph':
@@ -321,23 +356,21 @@ class Graph:
             old_entries = len(self._host[1]) if self._host is not None else 2 * len(self._root.events[0])
         if old_entries + 2 * n >= 2 ** 32:
             raise ValueError('extended: the device T-CSR holds fewer than 2^32 entries')
-        child = Graph.__new__(Graph)
-        child._init_common(n_out, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
-        child._time_ordered = self._time_ordered
+        child = self._child(n_out)
         child._t_last = t_last
         if self._dev is not None:  # device-resident parent: extend on the device
-            dev = self.device
+            dev = self._dev[0].device
             g = self.tcsr
             d_batch = batch if on_dev and batch[0].device == dev else tuple(torch.as_tensor(b).to(dev) for b in batch)
             batch = d_batch  # kept as uploaded (`last_batch`); the host view downloads it if it is ever asked for
             P = old_entries + 2 * n
-            out = (torch.empty(n_out + 1, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.float64, device=dev),
-                   torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev))
+            out = tcsr_arrays(n_out, P, dev)
             nbytes = int(lib.tg_tcsr_append_grow_workspace_bytes(old_entries, n, self.num_node, n_out))
             ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
             # (inputs and workspace come from the caching allocator: their memory is reused in stream order, no wait needed)
-            check(lib.tg_tcsr_append_grow(C.byref(g), n_out, n, *(ptr(b) for b in d_batch), *(ptr(t) for t in out), ptr(ws),
-                                          nbytes, stream_ptr(dev)), 'tg_tcsr_append')
+            with torch.cuda.device(dev):
+                check(lib.tg_tcsr_append_grow(C.byref(g), n_out, n, *(ptr(b) for b in d_batch), *(ptr(t) for t in out),
+                                              ptr(ws), nbytes, stream_ptr(dev)), 'tg_tcsr_append')
             child._dev = out
             child._set_struct()
             child._mt = self._mt_state()
@@ -377,45 +410,17 @@ class Graph:
         keep = -1 if keep_last is None else operator.index(keep_last)
         if keep_last is not None and keep < 0:
             raise ValueError(f'trimmed: keep_last = {keep} is negative')
-        child = Graph.__new__(Graph)
-        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
-        child._time_ordered = self._time_ordered
-        child._t_last = self._t_last
+        child = self._child()
         if self._dev is not None:  # device-resident parent: plan, one read-back, allocate exactly, apply
-            dev = self.device
-            g = self.tcsr
-            indptr = torch.empty(self.num_node + 1, dtype=torch.int64, device=dev)
-            nbytes = int(lib.tg_tcsr_trim_workspace_bytes(self.num_node))
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                check(lib.tg_tcsr_trim_plan(C.byref(g), t_cut, keep, ptr(indptr), ptr(ws), nbytes, stream_ptr(dev)),
-                      'tg_tcsr_trim_plan')
-                P = int(indptr[-1])  # the one read-back
-                out = (indptr, torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
-                       torch.empty(P, dtype=torch.int32, device=dev))
-                # (parent arrays and workspace belong to the caching allocator: reused in stream order, no wait needed)
-                check(lib.tg_tcsr_trim_apply(C.byref(g), ptr(indptr), P, *(ptr(t) for t in out[1:]), ptr(ws), nbytes,
-                                             stream_ptr(dev)), 'tg_tcsr_trim_apply')
-            child._dev = out
-            child._set_struct()
-            child._mt = self._mt_state()
-            child._root.dev = out
-        else:
-            h = self._host_tcsr()
-            P0 = len(h[1])
-            out = (np.empty(self.num_node + 1, dtype=np.int64), np.empty(P0, dtype=np.float64),
-                   np.empty(P0, dtype=np.int32), np.empty(P0, dtype=np.int32))
-            kept = C.c_int64(0)
-            gs = TgTcsr(self.num_node, P0, *(ptr(a) for a in h))
-            check(lib.tg_tcsr_trim_host(C.byref(gs), t_cut, keep, *(ptr(a) for a in out), C.byref(kept)), 'tg_tcsr_trim_host')
-            child._host = (out[0],) + tuple(a[:kept.value].copy() for a in out[1:])  # (copies: the full-size arrays die)
-            ev = self._root.events
-            if keep_last is None and ev is not None:  # a horizon alone: still the T-CSR of an event list
-                m = ev[2] >= t_cut
-                child._events = tuple(np.ascontiguousarray(a[m]) for a in ev)
-            if self._mt is not None:
-                child._mt = self._mt
-        return child
+            plan = ('tg_tcsr_trim_plan', lambda g, *out: lib.tg_tcsr_trim_plan(g, t_cut, keep, *out))
+            return child._adopt_device(tcsr_compacted(self, lambda g: lib.tg_tcsr_trim_workspace_bytes(g.num_node), plan,
+                                                      ('tg_tcsr_trim_apply', lib.tg_tcsr_trim_apply)), self)
+        out = tcsr_compacted_host(self, 'tg_tcsr_trim_host', lambda g, *out: lib.tg_tcsr_trim_host(g, t_cut, keep, *out))
+        ev = self._root.events if keep_last is None else None  # a horizon alone: still the T-CSR of an event list
+        if ev is not None:
+            m = ev[2] >= t_cut
+            ev = tuple(np.ascontiguousarray(a[m]) for a in ev)
+        return child._adopt_host(out, ev, self)
 
     # ---- erasing nodes, retracting events ----------------------------------------------
     @staticmethod
@@ -472,10 +477,7 @@ class Graph:
             n_rows = operator.index(eid_rows)
             if n_rows < 0 or n_rows > 0x80000000:
                 raise ValueError(f'without: eid_rows = {n_rows} is outside [0, 2^31]')
-        child = Graph.__new__(Graph)
-        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
-        child._time_ordered = self._time_ordered
-        child._t_last = self._t_last
+        child = self._child()
         if self._dev is not None:  # device-resident parent: plan, one read-back, allocate exactly, apply
             dev = self._dev[0].device
             node_bits = eid_bits = None
@@ -487,18 +489,14 @@ class Graph:
                     eid_bits = hip_ops.new_bitmap(n_rows, dev)
                     hip_ops.bitmap_mark(torch.as_tensor(ed[0]).to(dev), eid_bits, n_rows)  # (ids >= n_rows are not marked)
             indptr, P, ws = hip_ops.tcsr_erase_plan(self, node_bits, eid_bits, n_rows if eid_bits is not None else 0)
-            out = (indptr,) + hip_ops.tcsr_erase_apply(self, indptr, P, ws)
-            child._dev = out
-            child._set_struct()
-            child._mt = self._mt_state()
-            child._root.dev = out
+            return child._adopt_device((indptr,) + hip_ops.tcsr_erase_apply(self, indptr, P, ws), self)
         else:
             to_np = lambda x: x.cpu().numpy() if torch.is_tensor(x) else x
             n_ids = to_np(nd[0]) if nd is not None else None
             e_ids = to_np(ed[0]) if ed is not None else None
             node_bits = hip_ops.host_bitmap(n_ids, self.num_node) if nd is not None else None
             eid_bits = hip_ops.host_bitmap(e_ids, n_rows) if ed is not None and n_rows > 0 else None
-            child._host = hip_ops.tcsr_erase_host(self, node_bits, eid_bits, n_rows if eid_bits is not None else 0)
+            out = hip_ops.tcsr_erase_host(self, node_bits, eid_bits, n_rows if eid_bits is not None else 0)
             ev = self._root.events
             if ev is not None:  # still the T-CSR of an event list: the filtered one
                 m = np.ones(len(ev[0]), dtype=bool)
@@ -506,10 +504,8 @@ class Graph:
                     m &= ~np.isin(ev[0], n_ids) & ~np.isin(ev[1], n_ids)
                 if eid_bits is not None:
                     m &= ~np.isin(ev[3], e_ids[e_ids < n_rows])
-                child._events = tuple(np.ascontiguousarray(a[m]) for a in ev)
-            if self._mt is not None:
-                child._mt = self._mt
-        return child
+                ev = tuple(np.ascontiguousarray(a[m]) for a in ev)
+            return child._adopt_host(out, ev, self)
 
     # ---- renumbered edge ids ---------------------------------------------------------
     def renumbered(self, remap, eid_out) -> 'Graph':
@@ -522,35 +518,26 @@ class Graph:
         A device-resident parent keeps eid_out on its device, a host-only parent as a numpy array (either is moved there
         if it is not); the event list is pushed through `remap` on the host path and dropped on the device path
         (`_events` None).  ValueError: eid_out is no int32 array of num_entry entries."""
-        child = Graph.__new__(Graph)
-        child._init_common(self.num_node, self.strategy, self.seed, self.alpha, self._device, rng=self.rng)
-        child._time_ordered = self._time_ordered
-        child._t_last = self._t_last
+        child = self._child()
         if self._dev is not None:
             d = self._dev
             eid_out = torch.as_tensor(eid_out)
             if eid_out.dtype != torch.int32 or eid_out.dim() != 1 or eid_out.numel() != d[3].numel():
                 raise ValueError(f'renumbered: eid_out must be an int32 array of {d[3].numel()} entries')
             eid_out = eid_out.to(d[3].device).contiguous()  # (a host twin's result for a device-resident graph is uploaded)
-            child._dev = (d[0], d[1], d[2], eid_out)
-            child._set_struct()
-            child._mt = self._mt_state()
-            child._root.dev = child._dev
+            return child._adopt_device((d[0], d[1], d[2], eid_out), self)
         else:
             h = self._host_tcsr()
             e = np.ascontiguousarray(eid_out.cpu().numpy() if torch.is_tensor(eid_out) else eid_out)
             if e.dtype != np.int32 or e.shape != h[3].shape:
                 raise ValueError(f'renumbered: eid_out must be an int32 array of {len(h[3])} entries')
-            child._host = (h[0], h[1], h[2], e)
-            ev = self._root.events
+            ev, events = self._root.events, None
             if ev is not None and remap is not None:
                 r = np.asarray(remap.cpu().numpy() if torch.is_tensor(remap) else remap)
                 new = r[ev[3]].astype(np.int64) if len(ev[3]) == 0 or int(ev[3].max()) < len(r) else None
                 if new is not None and (len(new) == 0 or new.min() >= 0):  # (every event's row survived: still an event list)
-                    child._events = (ev[0], ev[1], ev[2], new)
-            if self._mt is not None:
-                child._mt = self._mt
-        return child
+                    events = (ev[0], ev[1], ev[2], new)
+            return child._adopt_host((h[0], h[1], h[2], e), events, self)
 
     # ---- sampling -------------------------------------------------------------------
     def sample_device(self, nids: Tensor, ts: Tensor, n_neighbors: int, strategy: Optional[str] = None,

@@ -3,6 +3,7 @@
 Tensors are plumbing: they own device memory and name the stream; all work
 happens in libtiger_hip.so.
 """
+import ctypes as C_
 from typing import Optional, Tuple
 
 import torch
@@ -660,8 +661,7 @@ def edge_rows_host(graph, table, n_rows: int, keep_from: Optional[int] = None, p
     keep = n_rows if keep_from is None else int(keep_from)
     if n_rows < 1 or not 0 <= keep <= n_rows:
         raise ValueError(f'edge_rows_host: keep_from = {keep} for a table of {n_rows} rows')
-    h = graph._host_tcsr()
-    g = _lib.TgTcsr(graph.num_node, len(h[1]), *(ptr(a) for a in h))
+    g, h = _graph_struct('edge_rows_host', graph, torch.device('cpu'))
     p = None if pin is None else np.ascontiguousarray(np.asarray(pin, dtype=np.int64).reshape(-1))
     d_e, t_out = 0, None
     if table is not None:
@@ -679,6 +679,59 @@ def edge_rows_host(graph, table, n_rows: int, keep_from: Optional[int] = None, p
         raise ValueError(f'edge_rows_host: an entry of the graph or a pinned id names no row of the table ({n_rows} rows)')
     check(rc, 'tg_edge_rows_host')
     return remap, (None if t_out is None else t_out[:n_live.value].copy()), eid_out
+
+
+# ---- T-CSR maintenance: the arrays, and plan / one read-back / exact allocation / apply (trim, erase) -------------------------
+def tcsr_arrays(num_node: int, num_entry: int, device=None):
+    """The four arrays of a T-CSR, uninitialised: (indptr int64 [num_node + 1], ts float64, nbr int32, eid int32 [num_entry])
+    - tensors on `device`, numpy arrays without one."""
+    if device is None:
+        import numpy as np
+        return (np.empty(num_node + 1, dtype=np.int64), np.empty(num_entry, dtype=np.float64),
+                np.empty(num_entry, dtype=np.int32), np.empty(num_entry, dtype=np.int32))
+    return (torch.empty(num_node + 1, dtype=torch.int64, device=device),) + _entry_arrays(num_entry, device)
+
+
+def _entry_arrays(num_entry: int, device) -> Tuple[Tensor, Tensor, Tensor]:
+    return (torch.empty(num_entry, dtype=torch.float64, device=device), torch.empty(num_entry, dtype=torch.int32, device=device),
+            torch.empty(num_entry, dtype=torch.int32, device=device))
+
+
+def _tcsr_plan(g, dev, workspace_bytes, plan):
+    """plan = (name for `check`, fn(g, indptr_out, ws, ws_bytes, stream) -> rc), then the ONE read-back -> (indptr_out, kept, ws);
+    this half and `_tcsr_apply` run under the caller's torch.cuda.device(dev) (`tcsr_compacted` holds one over both)"""
+    indptr = torch.empty(g.num_node + 1, dtype=torch.int64, device=dev)
+    nbytes = int(workspace_bytes(g))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    check(plan[1](C_.byref(g), ptr(indptr), ptr(ws), nbytes, stream_ptr(dev)), plan[0])
+    return indptr, int(indptr[-1]), ws
+
+
+def _tcsr_apply(g, dev, indptr: Tensor, num_entry_out: int, ws: Tensor, apply) -> Tuple[Tensor, Tensor, Tensor]:
+    """apply = (name, fn with the signature of tg_tcsr_trim_apply) into arrays of exactly num_entry_out entries -> (ts, nbr, eid)"""
+    out = _entry_arrays(num_entry_out, dev)
+    # (parent arrays and workspace belong to the caching allocator: reused in stream order, no wait needed)
+    check(apply[1](C_.byref(g), ptr(indptr), num_entry_out, *(ptr(t) for t in out), ptr(ws), ws.numel(), stream_ptr(dev)), apply[0])
+    return out
+
+
+def tcsr_compacted(graph, workspace_bytes, plan, apply) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """A device-resident graph without some of its entries, on the current stream of the device its arrays live on:
+    workspace_bytes(g), plan, ONE int64 read back (the kept entries), arrays allocated exactly, apply -> (indptr, ts, nbr, eid)."""
+    g, dev = graph.tcsr, graph._dev[0].device
+    with torch.cuda.device(dev):
+        indptr, n, ws = _tcsr_plan(g, dev, workspace_bytes, plan)
+        return (indptr,) + _tcsr_apply(g, dev, indptr, n, ws, apply)
+
+
+def tcsr_compacted_host(graph, name: str, twin):
+    """The host twin of `tcsr_compacted`: twin(g, indptr_out, ts_out, nbr_out, eid_out, num_entry_out) -> rc writes into
+    full-size arrays over the graph's host arrays -> numpy (indptr, ts, nbr, eid) cut to the kept entries."""
+    g, h = _graph_struct(name, graph, torch.device('cpu'))
+    out = tcsr_arrays(graph.num_node, len(h[1]))
+    kept = C_.c_int64(0)
+    check(twin(C_.byref(g), *(ptr(a) for a in out), C_.byref(kept)), name)
+    return (out[0],) + tuple(a[:kept.value].copy() for a in out[1:])  # (copies: the full-size arrays die)
 
 
 # ---- erasing nodes and retracting events (tg_tcsr_erase_plan / _apply and their host twin) ----------------------------------
@@ -709,7 +762,6 @@ def tcsr_erase_plan(graph, node_bits: Optional[Tensor] = None, eid_bits: Optiona
     [num_node + 1], the number of kept entries, ws - the workspace `tcsr_erase_apply` wants back).  Reads ONE int64 back
     (the kept entries: what the child's arrays are allocated by).  ValueError for a negative n_rows or a bitmap of another
     dtype, size or device."""
-    import ctypes as C_
     dev = torch.device(graph.device if device is None else device)
     if dev.type == 'cpu':
         raise ValueError('tcsr_erase_plan runs on the device (host arrays: tcsr_erase_host)')
@@ -720,51 +772,31 @@ def tcsr_erase_plan(graph, node_bits: Optional[Tensor] = None, eid_bits: Optiona
     dev = graph._dev[0].device  # (with its index: what the bitmaps are compared with)
     node_bits = _erase_bits('tcsr_erase_plan: node_bits', node_bits, graph.num_node, dev)
     eid_bits = _erase_bits('tcsr_erase_plan: eid_bits', eid_bits, n_rows, dev)
-    indptr = torch.empty(graph.num_node + 1, dtype=torch.int64, device=dev)
-    nbytes = int(lib.tg_tcsr_erase_workspace_bytes(g.num_node, g.num_entry))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    plan = lambda g, *out: lib.tg_tcsr_erase_plan(g, ptr(node_bits), ptr(eid_bits), n_rows, *out)
     with torch.cuda.device(dev):
-        check(lib.tg_tcsr_erase_plan(C_.byref(g), ptr(node_bits), ptr(eid_bits), n_rows, ptr(indptr), ptr(ws), nbytes,
-                                     stream_ptr(dev)), 'tg_tcsr_erase_plan')
-        n = int(indptr[-1])  # the one read-back
-    return indptr, n, ws
+        return _tcsr_plan(g, dev, lambda g: lib.tg_tcsr_erase_workspace_bytes(g.num_node, g.num_entry), ('tg_tcsr_erase_plan', plan))
 
 
 def tcsr_erase_apply(graph, indptr_out: Tensor, num_entry_out: int, ws: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """Copy the kept entries of `graph` (tiger_hip.h: tg_tcsr_erase_apply) with the indptr and the workspace of
     `tcsr_erase_plan` -> (ts float64, nbr int32, eid int32), each of exactly num_entry_out entries."""
-    import ctypes as C_
     dev = indptr_out.device
     g, _ = _graph_struct('tcsr_erase_apply', graph, dev)
-    P = int(num_entry_out)
-    out = (torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
-           torch.empty(P, dtype=torch.int32, device=dev))
     with torch.cuda.device(dev):
-        # (parent arrays and workspace belong to the caching allocator: reused in stream order, no wait needed)
-        check(lib.tg_tcsr_erase_apply(C_.byref(g), ptr(indptr_out), P, *(ptr(t) for t in out), ptr(ws), ws.numel(),
-                                      stream_ptr(dev)), 'tg_tcsr_erase_apply')
-    return out
+        return _tcsr_apply(g, dev, indptr_out, int(num_entry_out), ws, ('tg_tcsr_erase_apply', lib.tg_tcsr_erase_apply))
 
 
 def tcsr_erase_host(graph, node_bits=None, eid_bits=None, n_rows: int = 0):
     """The host twin of plan + apply (tiger_hip.h: tg_tcsr_erase_host) over the graph's host arrays and numpy int64 bitmaps
     (`host_bitmap`) -> (indptr int64 [num_node + 1], ts float64, nbr int32, eid int32: numpy arrays of the kept entries).
     ValueError as `tcsr_erase_plan`."""
-    import ctypes as C_
     import numpy as np
     n_rows = int(n_rows)
     if n_rows < 0:
         raise ValueError(f'tcsr_erase_host: n_rows = {n_rows} is negative')
-    h = graph._host_tcsr()
     for what, bits, n in (('node_bits', node_bits, graph.num_node), ('eid_bits', eid_bits, n_rows)):
         if bits is not None and (not isinstance(bits, np.ndarray) or bits.dtype != np.int64 or bits.ndim != 1
                                  or not bits.flags.c_contiguous or len(bits) < bitmap_words(n)):
             raise ValueError(f'tcsr_erase_host: {what} over {n} ids is a contiguous numpy int64 array of {bitmap_words(n)} words')
-    P0 = len(h[1])
-    g = _lib.TgTcsr(graph.num_node, P0, *(ptr(a) for a in h))
-    out = (np.empty(graph.num_node + 1, dtype=np.int64), np.empty(P0, dtype=np.float64), np.empty(P0, dtype=np.int32),
-           np.empty(P0, dtype=np.int32))
-    kept = C_.c_int64(0)
-    check(lib.tg_tcsr_erase_host(C_.byref(g), ptr(node_bits), ptr(eid_bits), n_rows, *(ptr(a) for a in out), C_.byref(kept)),
-          'tg_tcsr_erase_host')
-    return (out[0],) + tuple(a[:kept.value].copy() for a in out[1:])  # (copies: the full-size arrays die)
+    return tcsr_compacted_host(graph, 'tg_tcsr_erase_host',
+                               lambda g, *out: lib.tg_tcsr_erase_host(g, ptr(node_bits), ptr(eid_bits), n_rows, *out))

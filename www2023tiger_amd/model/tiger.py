@@ -1763,11 +1763,14 @@ class TIGE(nn.Module):
         Refused before anything runs: a partitioned model, and what `Graph.trimmed` refuses (a NaN `before`, a negative
         `keep_last`); with the flag also what `release_edge_rows` refuses, and then nothing at all has changed."""
         self._refuse_partitioned('forget')
-        if not release_edge_rows:
-            self.graph = self.graph.trimmed(before=before, keep_last=keep_last)
-            return self.graph
-        trimmed = self.graph.trimmed(before=before, keep_last=keep_last)
-        self.release_edge_rows(keep_from=keep_from, _graph=trimmed)  # (swaps graph and table together, or raises)
+        return self._swap_graph(self.graph.trimmed(before=before, keep_last=keep_last), release_edge_rows, keep_from)
+
+    def _swap_graph(self, child, release_edge_rows: bool, keep_from):
+        """the tail of `forget` and `erase`: `child` becomes the graph, alone or together with the packed edge table"""
+        if release_edge_rows:
+            self.release_edge_rows(keep_from=keep_from, _graph=child)  # (swaps graph and table together, or raises)
+        else:
+            self.graph = child
         return self.graph
 
     @torch.no_grad()
@@ -1805,10 +1808,7 @@ class TIGE(nn.Module):
         ids = None
         if nodes is not None:
             ids = torch.as_tensor(nodes).to(self.device).long().reshape(-1)
-        if release_edge_rows:
-            self.release_edge_rows(keep_from=keep_from, _graph=child)  # (swaps graph and table together, or raises)
-        else:
-            self.graph = child
+        self._swap_graph(child, release_edge_rows, keep_from)
         if ids is not None and ids.numel():
             self.left_memory.clear(ids)
             self.right_memory.clear(ids)

@@ -30,6 +30,13 @@ starts (`TIGE.erase`: a closed account, a de-listed item, a cancelled transactio
 the erased nodes' memory and mailbox rows are reset, and the entries dropped are printed.  The offline replay beside it
 still has them, so the two lines are not held equal; an erased id that the test split brings back starts as a node never
 seen.
+--save_state PATH saves the served model after the online replay (`TIGE.save_online`: parameters, memories, mailbox, the
+feature tables with exactly their rows and the device graph - after a forget, a release of rows or an erase none of that
+can be rebuilt from the stream), together with the position in the test split; --save_after N stops the replay after N
+batches first.  --load_state PATH starts from such a file instead of train + validation (`TIGE.load_online` into the model
+`init_model` builds: the graph is checked by `tg_tcsr_verify` before anything reads it) and replays the rest of the split.
+A replay that is saved after N batches and one that loads the file write, between them, the lists of the uninterrupted
+replay, exactly.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -134,15 +141,17 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     return ids, scores, out
 
 
-def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None):
+def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None, first=0, stop=None):
     """recommend, then `ingest`, batch by batch over the test split -> (ids [n_test, k], dict of the metrics of
     eval_recommendation: position of the true destination in its list, folded the same way).  known: a callable -> the
-    (catalogue, col_of) of the batch, for a model whose node ids grow on the way (run_online(grow=True))"""
+    (catalogue, col_of) of the batch, for a model whose node ids grow on the way (run_online(grow=True)).  first / stop: the
+    events [first, stop) of the split alone (a replay that was saved, or will be)"""
     dev = model.device
     ids, pos = [], []
     place = torch.arange(k, device=dev)
-    for lo in range(0, len(test.src), bs):
-        src, dst, ts, eids = (np.ascontiguousarray(getattr(test, f)[lo:lo + bs]) for f in ('src', 'dst', 'ts', 'eids'))
+    stop = len(test.src) if stop is None else min(stop, len(test.src))
+    for lo in range(first, stop, bs):
+        src, dst, ts, eids = (np.ascontiguousarray(getattr(test, f)[lo:min(lo + bs, stop)]) for f in ('src', 'dst', 'ts', 'eids'))
         q, t, d = torch.from_numpy(src).to(dev), torch.from_numpy(ts.astype(np.float64)).to(dev), torch.from_numpy(dst).to(dev)
         if known is not None:
             catalogue, col_of = known()
@@ -154,17 +163,18 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=N
         pos.append(torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1))
         ids.append(i)
         ingest(src, dst, ts.astype(np.float64), eids)
-    pos = torch.cat(pos)
+    pos = torch.cat(pos) if pos else torch.zeros(0, dtype=torch.int64, device=dev)
     listed, p = pos >= 0, pos.clamp(min=0).double()
     n = max(1, pos.numel())
-    return torch.cat(ids).cpu().numpy(), dict(hit_rate=float(listed.sum()) / n, ndcg=float((listed / torch.log2(p + 2)).sum()) / n,
+    ids = torch.cat(ids).cpu().numpy() if ids else np.zeros((0, k), dtype=np.int64)
+    return ids, dict(hit_rate=float(listed.sum()) / n, ndcg=float((listed / torch.log2(p + 2)).sum()) / n,
                                               mrr_at_k=float((listed / (p + 1)).sum()) / n, n_events=pos.numel())
 
 
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
-               erase_nodes=None, retract_eids=None):
+               erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -184,7 +194,12 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     restarter.
     erase_nodes / retract_eids (int arrays): `erase(nodes=..., eids=...)` once, on the graph over train + validation,
     before the online replay; its metrics then carry 'erased': (entries kept, entries dropped), and the two replays are not
-    held equal (the offline one still has the nodes and events)."""
+    held equal (the offline one still has the nodes and events).
+    save_state (a path): after the online replay - of the first save_after batches, if given - the model is saved with
+    `save_online`'s content plus the position: torch.save(dict(state=model.online_state(), next_event=..., shifted=...)).
+    load_state (such a file): the online replay starts from it (`load_online`) instead of the graph over train +
+    validation, at the file's position.  With either, no offline replay is made and the online metrics carry 'ids': the
+    lists of the events replayed - a saved replay's followed by the loading one's are the uninterrupted replay's."""
     from www2023tiger_amd.data.graph import Graph
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -222,15 +237,26 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     catalogue = torch.from_numpy(np.unique(full_data.dst).astype(np.int64)).to(device)
     col_of = None if grow else hip_ops.catalogue_index(catalogue, model.n_nodes)
     start = model.save_memory_state()
+    partial = save_after is not None or load_state is not None
+    first, stop = 0, None if save_after is None else int(save_after) * bs
     with torch.no_grad():
         ids_off = None
-        if offline:
+        if offline and not partial:
             model.graph = full_graph
             ids_off, offline = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
                                        lambda s, d, t, e: model.stream_step(s, d, d, t, e))
             model.load_memory_state(start)
         # the edge table already holds the rows of the test events; a live system hands them to observe(efeats=...)
-        model.graph = seen()
+        shifted = [0]   # rows released so far: the eids of the events still to come moved down by as much
+        if load_state is None:
+            model.graph = seen()
+        else:   # (checks everything, the graph with tg_tcsr_verify, before anything changes; grows the tables if need be)
+            blob = torch.load(load_state, map_location='cpu', weights_only=True)
+            model.load_online(blob['state'])
+            first, shifted[0] = int(blob['next_event']), int(blob['shifted'])
+            if verbose:
+                print(f'loaded {load_state}: {model.n_nodes} node ids, {int(model.graph.tcsr.num_entry)} entries, '
+                      f'continuing at event {first} of the split')
         erasing = erase_nodes is not None or retract_eids is not None
         erased = None
         if erasing:
@@ -241,7 +267,6 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                 print(f'erase: {0 if erase_nodes is None else len(erase_nodes)} nodes, '
                       f'{0 if retract_eids is None else len(retract_eids)} eids: {erased[0]} entries kept, {erased[1]} dropped')
         forgot = []
-        shifted = [0]   # rows released so far: the eids of the events still to come moved down by as much
         rows = []
 
         admitted = []
@@ -279,10 +304,19 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                     print(f'batch {len(forgot) - 1}: edge table {rel.rows_before} rows -> {rel.rows}')
         forgetting = window is not None or keep_last is not None
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
-                                 observe_and_forget if forgetting else observe, known=known if grow else None)
+                                 observe_and_forget if forgetting else observe, known=known if grow else None,
+                                 first=first, stop=stop)
+        if save_state is not None:
+            done = len(test.src) if stop is None else min(stop, len(test.src))
+            torch.save(dict(state=model.online_state(), next_event=done, shifted=shifted[0]), save_state)
+            if verbose:
+                print(f'saved {save_state}: {model.n_nodes} node ids, {int(model.graph.tcsr.num_entry)} entries, '
+                      f'{done} events of the split replayed')
     need = max(n_neighbors, hist_len if restarter_type == 'seq' else 0)
     if ids_off is not None and not erasing and (not forgetting or (window is None and keep_last >= need and not exclude_seen)):
         assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
+    if partial or save_state is not None:
+        online = dict(online, ids=ids_on)
     if grow:
         online = dict(online, admitted=admitted)
     if erasing:
@@ -368,6 +402,11 @@ if __name__ == '__main__':
                     'before the replay (TIGE.erase); prints the entries dropped')
     ap.add_argument('--retract_eids', default=None, metavar='FILE', help='--online: a .npy of edge ids that are retracted '
                     'once before the replay (TIGE.erase); prints the entries dropped')
+    ap.add_argument('--save_state', default=None, metavar='PATH', help='--online: save the served model after the replay '
+                    '(TIGE.save_online and the position in the split)')
+    ap.add_argument('--save_after', type=int, default=None, metavar='N', help='--save_state: stop the replay after N batches')
+    ap.add_argument('--load_state', default=None, metavar='PATH', help='--online: start from a file of --save_state instead '
+                    'of train + validation (TIGE.load_online) and replay the rest of the split')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -389,7 +428,8 @@ if __name__ == '__main__':
                                                               release_rows=a.release_rows, grow=a.grow,
                                                               erase_nodes=None if a.erase_nodes is None else np.load(a.erase_nodes),
                                                               retract_eids=None if a.retract_eids is None
-                                                              else np.load(a.retract_eids))):
+                                                              else np.load(a.retract_eids), save_state=a.save_state,
+                                                              save_after=a.save_after, load_state=a.load_state)):
             if m is None:
                 continue
             print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "

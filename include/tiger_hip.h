@@ -202,6 +202,40 @@ int tg_tcsr_erase_host(const tg_tcsr* g, const int64_t* node_bits_host, const in
                        int64_t* indptr_out_host, double* ts_out_host, int32_t* nbr_out_host, int32_t* eid_out_host,
                        int64_t* num_entry_out);
 
+/* Is this a T-CSR the library may read?  (tg_verify.hip; loading a saved online graph.  graph.py:11-42: no counterpart -
+ * the reference builds its adjacency lists in the process that reads them.)  The samplers, tg_seen_mask, the walk, trending
+ * and the restarters' histories use indptr, nbr and eid as addresses without checking them; arrays that do not come from
+ * this library's own kernels go through here first.  out8 = {code, first[0..5], tmax_bits}: code = the OR of the classes
+ * below, first[c] = the SMALLEST index that violates class c or -1, tmax_bits = the bit pattern of the largest non-NaN ts
+ * (of -inf without one; +0 counts above -0).
+ *   1  ENDS       indptr[0] != 0 (index 0) or indptr[num_node] != num_entry (index num_node)
+ *   2  PTR_ORDER  v with indptr[v + 1] < indptr[v]
+ *   4  TS_ORDER   p > 0, not a row start, with ts[p] < ts[p - 1] (float64; a comparison with a NaN is no violation).  A
+ *                 row start is a p whose owner differs from that of p - 1.  Evaluated only when ENDS and PTR_ORDER are
+ *                 clean (the rows mean nothing otherwise): bit 0 and index -1 then.
+ *   8  TS_NAN     p with ts[p] != ts[p]
+ *   16 NBR_RANGE  p with nbr[p] < 0 or nbr[p] >= num_node
+ *   32 EID_RANGE  p with (eid[p] & 0x7fffffff) >= eid_rows; evaluated only when eid_rows >= 0
+ * Mirror entries are no invariant (a capped trim and an erase leave one side of an event) and are not checked.
+ * SAFE ON ANY ARRAY CONTENTS: every address the kernels form comes from a loop index bounded by num_node / num_entry as
+ * passed in; a value loaded from the arrays is only ever compared, never used as an index or an offset - a non-monotone
+ * indptr included.  (num_node / num_entry themselves must be the true lengths: the caller knows what it allocated.)
+ * tg_tcsr_verify: one launch over tiles of 2048 entries, one over the row bounds, one workgroup that folds the partial
+ * records in ws; no atomics, nothing read back: asynchronous on `stream`, the caller reads the 8 words of out8 (DEVICE,
+ * like every pointer; ws 16-byte aligned) when it wants them.  tg_tcsr_verify_workspace_bytes: 64 bytes per tile and per
+ * 256 row bounds; 0 for a bad count.  A short workspace returns TG_EWORKSPACE before anything is launched.  TG_EINVAL:
+ * num_node outside [1, 2^31), num_entry outside [0, 2^32), a missing array or out8.
+ * tg_tcsr_verify_host: the host twin, HOST pointers (those of `g` included), plain C++. */
+#define TG_VERIFY_ENDS 1
+#define TG_VERIFY_PTR_ORDER 2
+#define TG_VERIFY_TS_ORDER 4
+#define TG_VERIFY_TS_NAN 8
+#define TG_VERIFY_NBR_RANGE 16
+#define TG_VERIFY_EID_RANGE 32
+size_t tg_tcsr_verify_workspace_bytes(int64_t num_entry, int64_t num_node);
+int tg_tcsr_verify(const tg_tcsr* g, int64_t eid_rows, int64_t* out8, void* ws, size_t ws_bytes, void* stream);
+int tg_tcsr_verify_host(const tg_tcsr* g, int64_t eid_rows, int64_t* out8_host);
+
 /* Releasing edge-feature rows (tg_edge_rows.hip; online serving after a trim).  The reference never drops a row of its
  * tables (feature_getter.py:41-47, graph.py:11-42: built once over the whole stream).  A row r of the table
  * T [n_rows, d_e] (float32, d_e % 4 == 0) is LIVE iff r == 0 (the padding row), some entry of g has

@@ -198,6 +198,9 @@ SIGNATURES = {
     'tg_tcsr_erase_plan': (C.c_int, [P(TgTcsr), vp, vp, i64, vp, vp, sz, vp]),
     'tg_tcsr_erase_apply': (C.c_int, [P(TgTcsr), vp, i64, vp, vp, vp, vp, sz, vp]),
     'tg_tcsr_erase_host': (C.c_int, [P(TgTcsr), vp, vp, i64, vp, vp, vp, vp, vp]),
+    'tg_tcsr_verify_workspace_bytes': (sz, [i64, i64]),
+    'tg_tcsr_verify': (C.c_int, [P(TgTcsr), i64, vp, vp, sz, vp]),
+    'tg_tcsr_verify_host': (C.c_int, [P(TgTcsr), i64, vp]),
     'tg_edge_rows_workspace_bytes': (sz, [i64, i64]),
     'tg_edge_rows_plan': (C.c_int, [P(TgTcsr), i64, i64, vp, i64, vp, vp, vp, sz, vp]),
     'tg_edge_rows_apply': (C.c_int, [P(TgTcsr), vp, i64, i32, vp, i64, vp, vp, vp, sz, vp]),

@@ -75,6 +75,7 @@ class Graph:
         self._device = torch.device(device) if device is not None else None
         self._dev = None  # device tensors, built / uploaded lazily
         self._mt = None
+        self._mt_saved = None  # a host graph of `from_state_dict`: the saved device MT19937 state, uploaded on first use
         self._root = _HostRoot(self.num_node)  # the host view: `_events`, `_host` below
         self._log = None     # extended graphs: (parent's log, batch) - the batches appended to the root, newest first
         self._time_ordered = False
@@ -229,6 +230,8 @@ class Graph:
         return self._struct
 
     def _mt_state(self) -> Tensor:
+        if self._mt is None and self._mt_saved is not None:
+            self._mt = self._mt_saved.to(self.device)
         if self._mt is None:
             _, key, pos, _, _ = self.rng.get_state()
             st = np.concatenate([key.astype(np.uint32), np.array([pos], dtype=np.uint32)]).view(np.int32)
@@ -244,6 +247,7 @@ class Graph:
                            rng=self.rng)
         child._time_ordered = self._time_ordered
         child._t_last = self._t_last
+        child._mt_saved = self._mt_saved
         return child
 
     def _adopt_device(self, arrays, parent: Optional['Graph'] = None) -> 'Graph':
@@ -272,6 +276,100 @@ class Graph:
         self._init_common(arrays[0].numel() - 1, strategy, seed, 0.0, arrays[0].device)
         self._time_ordered, self._t_last = bool(time_ordered), t_last
         return self._adopt_device(arrays)
+
+    # ---- saving and restoring -------------------------------------------------------
+    STATE_FORMAT, STATE_VERSION = 'tiger-graph', 1
+
+    def state_dict(self) -> dict:
+        """This graph as a flat dict of CPU tensors and plain Python values (`torch.save`, `torch.load(weights_only=True)`;
+        graph.py:11-42 has no counterpart: the reference rebuilds its graph from the data set).  The four arrays of THIS
+        graph - a chain child of `extended` as well as a child of `trimmed` / `without` / `renumbered`, copied from the
+        device for a device-resident graph, from the host view otherwise -, num_node, the latest event time (a 0-d device
+        value is resolved: one read-back), the time-ordered flag, strategy / seed / alpha, the state of `rng` and, if the
+        graph has one, the device MT19937 state.  Not saved: the event list and `last_batch`."""
+        if self._dev is not None:
+            arrays = tuple(t.detach().to('cpu', copy=True) for t in self._dev)
+        else:
+            arrays = tuple(torch.from_numpy(np.array(a, copy=True)) for a in self._host_tcsr())
+        kind, key, pos, has_gauss, gauss = self.rng.get_state()
+        sd = dict(format=self.STATE_FORMAT, version=self.STATE_VERSION,
+                  indptr=arrays[0], ts=arrays[1], nbr=arrays[2], eid=arrays[3], num_node=int(self.num_node),
+                  t_last=float(self._t_last), time_ordered=bool(self._time_ordered),
+                  strategy=self.strategy, seed=None if self.seed is None else int(self.seed), alpha=float(self.alpha),
+                  rng_kind=str(kind), rng_key=torch.from_numpy(key.astype(np.int64)), rng_pos=int(pos),
+                  rng_has_gauss=int(has_gauss), rng_cached_gaussian=float(gauss),
+                  mt_state=None if self._mt is None else self._mt.detach().to('cpu', copy=True))
+        return sd
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device=None, verify: bool = True, eid_rows: Optional[int] = None) -> 'Graph':
+        """The root Graph a `state_dict` describes.  device: where it lives - device-resident there (its host view is
+        downloaded on first use); None: the current GPU, or a host graph when there is none (as with device='cpu').  `rng` is
+        restored with `set_state` and the device MT19937 state is the saved one, so 'uniform' draws continue the saved
+        stream; the graph has a `serial` of its own and no event list.
+        verify=True refuses, BEFORE any array reaches a sampler (ValueError): an unknown format / version, arrays of other
+        dtypes or shapes, lengths that do not fit each other or num_node, any non-zero code of `hip_ops.tcsr_verify` (the
+        host twin without a device; the message names class and index: TCSR_VERIFY_TEXT), with eid_rows an edge id that is
+        no row of the caller's edge table, and a saved latest time BELOW the largest time of the arrays.  (ABOVE is legal:
+        `trimmed` / `without` carry the parent's latest time on purpose.)  verify=False trusts the caller, as
+        `extended(validate=False)` does."""
+        from .. import hip_ops
+        if not isinstance(sd, dict) or sd.get('format') != cls.STATE_FORMAT:
+            raise ValueError(f"from_state_dict: not a saved graph (format {sd.get('format') if isinstance(sd, dict) else type(sd).__name__!r})")
+        if sd.get('version') != cls.STATE_VERSION:
+            raise ValueError(f"from_state_dict: version {sd.get('version')!r} of the format is unknown (this library reads {cls.STATE_VERSION})")
+        missing = [k for k in ('indptr', 'ts', 'nbr', 'eid', 'num_node', 't_last', 'time_ordered', 'strategy', 'seed', 'alpha',
+                               'rng_kind', 'rng_key', 'rng_pos', 'rng_has_gauss', 'rng_cached_gaussian', 'mt_state') if k not in sd]
+        if missing:
+            raise ValueError(f'from_state_dict: the saved graph lacks {missing}')
+        arrays = tuple(sd[k] for k in ('indptr', 'ts', 'nbr', 'eid'))
+        if device is None:
+            dev = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else None
+        else:
+            dev = torch.device(device)
+            dev = None if dev.type == 'cpu' else dev
+        key, mt = sd['rng_key'], sd['mt_state']
+        if verify:
+            if not all(torch.is_tensor(a) for a in arrays):
+                raise ValueError('from_state_dict: indptr, ts, nbr and eid must be tensors')
+            n, _ = hip_ops._verify_arrays('from_state_dict', arrays, False)
+            if isinstance(sd['num_node'], bool) or not isinstance(sd['num_node'], int) or sd['num_node'] != n:
+                raise ValueError(f"from_state_dict: num_node = {sd['num_node']!r}, but indptr has {n} rows")
+            if not isinstance(sd['strategy'], str) or not isinstance(sd['t_last'], float):
+                raise ValueError('from_state_dict: strategy must be a str and t_last a float')
+            if (not torch.is_tensor(key) or key.dtype != torch.int64 or tuple(key.shape) != (624,) or int(key.min()) < 0
+                    or int(key.max()) > 0xFFFFFFFF or sd['rng_kind'] != 'MT19937' or not 0 <= int(sd['rng_pos']) <= 624):
+                raise ValueError('from_state_dict: the saved rng state is no MT19937 state')
+            if mt is not None and (not torch.is_tensor(mt) or mt.dtype != torch.int32 or tuple(mt.shape) != (625,)
+                                   or not 0 <= int(mt[624]) <= 624):
+                raise ValueError('from_state_dict: the saved device MT19937 state is no int32 [625] state')
+        rng = np.random.RandomState()
+        rng.set_state((str(sd['rng_kind']), key.numpy().astype(np.uint32), int(sd['rng_pos']), int(sd['rng_has_gauss']),
+                       float(sd['rng_cached_gaussian'])))
+        if dev is not None:
+            with torch.cuda.device(dev):
+                arrays = tuple(a.to(dev).contiguous() for a in arrays)
+        else:
+            arrays = tuple(np.array(a.numpy(), copy=True) for a in arrays)
+        if verify:  # the arrays go nowhere else before this
+            code, first, t_max = (hip_ops.tcsr_verify if dev is not None else hip_ops.tcsr_verify_host)(arrays, eid_rows)
+            if code:
+                raise ValueError('from_state_dict: ' + hip_ops.TCSR_VERIFY_TEXT(code, first))
+            if not sd['t_last'] >= t_max:
+                raise ValueError(f"from_state_dict: the saved latest time {sd['t_last']} is below the largest time of the "
+                                 f'entries ({t_max})')
+        self = cls.__new__(cls)
+        self._init_common(int(sd['num_node']), sd['strategy'], sd['seed'], sd['alpha'], dev, rng=rng)
+        self._time_ordered, self._t_last = bool(sd['time_ordered']), float(sd['t_last'])
+        if dev is not None:
+            self._adopt_device(arrays)
+            if mt is not None:
+                self._mt = mt.to(dev).contiguous()
+        else:
+            self._host = arrays
+            if mt is not None:
+                self._mt_saved = mt.clone()  # uploaded by `_mt_state` on first use
+        return self
 
     # ---- online ingestion -----------------------------------------------------------
     def extended(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None, num_node=None) -> 'Graph':

@@ -800,3 +800,87 @@ def tcsr_erase_host(graph, node_bits=None, eid_bits=None, n_rows: int = 0):
             raise ValueError(f'tcsr_erase_host: {what} over {n} ids is a contiguous numpy int64 array of {bitmap_words(n)} words')
     return tcsr_compacted_host(graph, 'tg_tcsr_erase_host',
                                lambda g, *out: lib.tg_tcsr_erase_host(g, ptr(node_bits), ptr(eid_bits), n_rows, *out))
+
+
+# ---- is this a T-CSR the library may read? (tg_tcsr_verify and its host twin) -----------------------------------------------
+TCSR_VERIFY_CLASSES = ('ENDS', 'PTR_ORDER', 'TS_ORDER', 'TS_NAN', 'NBR_RANGE', 'EID_RANGE')
+_TCSR_VERIFY_WHAT = ('indptr[0] != 0 or indptr[num_node] != num_entry, at row bound {i}',
+                     'indptr decreases after row {i}',
+                     'the times of a row decrease at entry {i}',
+                     'the time of entry {i} is NaN',
+                     'the neighbour of entry {i} is no node id',
+                     'the edge id of entry {i} is no row of the edge table')
+
+
+def TCSR_VERIFY_TEXT(code: int, first=None) -> str:
+    """The message of a non-zero tcsr_verify code: every violated class by name, with its smallest violating index."""
+    parts = []
+    for c, (name, what) in enumerate(zip(TCSR_VERIFY_CLASSES, _TCSR_VERIFY_WHAT)):
+        if code >> c & 1:
+            parts.append(f'{name}: ' + what.format(i=first[c] if first is not None else '?'))
+    return 'no T-CSR the library may read - ' + '; '.join(parts) if parts else 'a T-CSR the library may read'
+
+
+def _verify_arrays(what: str, arrays, is_np: bool):
+    """four arrays of the T-CSR dtypes, 1-d, contiguous, ts / nbr / eid of one length -> (num_node, num_entry); ValueError"""
+    import numpy as np
+    if len(arrays) != 4:
+        raise ValueError(f'{what}: a T-CSR is (indptr, ts, nbr, eid)')
+    want = (np.int64, np.float64, np.int32, np.int32) if is_np else (torch.int64, torch.float64, torch.int32, torch.int32)
+    for a, dt, name in zip(arrays, want, ('indptr', 'ts', 'nbr', 'eid')):
+        ok = isinstance(a, np.ndarray) and a.flags.c_contiguous if is_np else torch.is_tensor(a) and a.is_contiguous()
+        if not ok or a.dtype != dt or a.ndim != 1:
+            raise ValueError(f'{what}: {name} must be a contiguous 1-d {"numpy array" if is_np else "tensor"} of {dt}')
+    n, P = int(arrays[0].shape[0]) - 1, int(arrays[1].shape[0])
+    if n < 1 or n > 0x7FFFFFFF or P > 0xFFFFFFFF:
+        raise ValueError(f'{what}: num_node = {n}, num_entry = {P} is outside what a T-CSR holds')
+    if int(arrays[2].shape[0]) != P or int(arrays[3].shape[0]) != P:
+        raise ValueError(f'{what}: ts, nbr and eid must have one entry each ({P}, {arrays[2].shape[0]}, {arrays[3].shape[0]})')
+    return n, P
+
+
+def _verify_result(out8):
+    import numpy as np
+    w = [int(x) for x in out8]
+    return w[0], w[1:7], float(np.array([w[7]], dtype=np.int64).view(np.float64)[0])
+
+
+def tcsr_verify(arrays_or_graph, eid_rows: Optional[int] = None):
+    """Is this a T-CSR the library may read (tiger_hip.h: tg_tcsr_verify)?  A Graph (its device arrays) or the four device
+    tensors (indptr int64 [N + 1], ts float64, nbr int32, eid int32 [P]) -> (code, first[6], t_max): code = the OR of the
+    violated classes (TCSR_VERIFY_CLASSES, bit c = class c; 0: clean), first[c] = the smallest violating index or -1, t_max
+    = the largest non-NaN time (-inf without one).  eid_rows: the rows of the edge table (None: the eids are not checked).
+    On the arrays' device and the current stream, ONE read-back of the 8 result words.  Safe on any array CONTENTS; dtypes,
+    shapes and lengths are checked here (ValueError)."""
+    if hasattr(arrays_or_graph, 'tcsr'):
+        g, keep = arrays_or_graph.tcsr, arrays_or_graph._dev
+        dev = keep[0].device
+    else:
+        keep = tuple(arrays_or_graph)
+        n, P = _verify_arrays('tcsr_verify', keep, False)
+        dev = keep[0].device
+        if dev.type == 'cpu' or any(a.device != dev for a in keep):
+            raise ValueError('tcsr_verify runs on the device the four arrays share (host arrays: tcsr_verify_host)')
+        g = _lib.TgTcsr(n, P, *(ptr(a) for a in keep))
+    rows = -1 if eid_rows is None else int(eid_rows)
+    with torch.cuda.device(dev):
+        out8 = torch.empty(8, dtype=torch.int64, device=dev)
+        nbytes = int(lib.tg_tcsr_verify_workspace_bytes(g.num_entry, g.num_node))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.tg_tcsr_verify(C_.byref(g), rows, ptr(out8), ptr(ws), nbytes, stream_ptr(dev)), 'tg_tcsr_verify')
+        return _verify_result(out8.tolist())
+
+
+def tcsr_verify_host(arrays_or_graph, eid_rows: Optional[int] = None):
+    """`tcsr_verify` over numpy arrays (or a Graph's host view) with the host twin (tiger_hip.h: tg_tcsr_verify_host)."""
+    import numpy as np
+    if hasattr(arrays_or_graph, '_host_tcsr'):
+        keep = arrays_or_graph._host_tcsr()
+        n, P = arrays_or_graph.num_node, len(keep[1])
+    else:
+        keep = tuple(arrays_or_graph)
+        n, P = _verify_arrays('tcsr_verify_host', keep, True)
+    g = _lib.TgTcsr(n, P, *(ptr(a) for a in keep))
+    out8 = np.empty(8, dtype=np.int64)
+    check(lib.tg_tcsr_verify_host(C_.byref(g), -1 if eid_rows is None else int(eid_rows), ptr(out8)), 'tg_tcsr_verify_host')
+    return _verify_result(out8)

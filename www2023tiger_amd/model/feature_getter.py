@@ -166,6 +166,47 @@ class NumericalFeature(nn.Module):
         self.efeats = res._store[:res.rows]
         self.n_edges = res.rows
 
+    def install_rows(self, nfeats: Optional[Tensor] = None, efeats: Optional[Tensor] = None) -> bool:
+        """Replace the node and / or the edge table by the given rows (TIGE.load_online: the tables of a saved online model)
+        -> whether a table's data pointer moved (it does: the caller drops whatever caches it, TIGE.invalidate_struct).
+        Each new table is the leading view of a backing store with the usual head-room - a zeroed one that is half as large
+        again for the node table (`append_node_rows`), n + max(16, n // 4) rows for the edge table (`compact_edge_rows`) -
+        so the next append copies the new rows and nothing else; `n_nodes` / `n_edges` follow.  None leaves a table as it
+        is.  Refused, with nothing changed: a table the getter does not have, rows of another width or dtype (ValueError),
+        tables in pinned host memory (register_buffer=False: NotImplementedError)."""
+        from .memory import grow_capacity
+        if not self.pin_mem:
+            raise NotImplementedError('install_rows: the tables live in pinned host memory (register_buffer=False)')
+        for name, new in (('nfeats', nfeats), ('efeats', efeats)):
+            cur = getattr(self, name)
+            if new is None:
+                continue
+            if cur is None:
+                raise ValueError(f'install_rows: the feature getter has no {name} table')
+            if not torch.is_tensor(new) or new.dim() != 2 or new.shape[1] != cur.shape[1] or new.dtype != cur.dtype:
+                what = f'{new.dtype} {tuple(new.shape)}' if torch.is_tensor(new) else type(new).__name__
+                raise ValueError(f'install_rows: {name} {what} for a {cur.dtype} table of width {cur.shape[1]}')
+        moved = False
+        if nfeats is not None:
+            cur, n = self.nfeats, nfeats.shape[0]
+            store = torch.zeros(grow_capacity(n, n, None), cur.shape[1], dtype=cur.dtype, device=cur.device)
+            store[:n] = nfeats.to(cur.device)
+            self.__dict__.setdefault('_stores', {})['nfeats'] = store
+            self.nfeats = store[:n]
+            self.n_nodes = n
+            self._version_ = getattr(self, '_version_', 0) + 1
+            self._nz_cache = None  # (keyed by the table's address: a freed store's address can come back)
+            moved = True
+        if efeats is not None:
+            cur, n = self.efeats, efeats.shape[0]
+            store = torch.empty(n + max(16, n // 4), cur.shape[1], dtype=cur.dtype, device=cur.device)
+            store[:n] = efeats.to(cur.device)
+            self._ef_store = store
+            self.efeats = store[:n]
+            self.n_edges = n
+            moved = True
+        return moved
+
     def _lookup(self, table, ids, width):
         if table is None:
             return torch.zeros(*ids.shape, width, device=ids.device)

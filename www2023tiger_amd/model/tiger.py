@@ -1856,6 +1856,158 @@ class TIGE(nn.Module):
         self.last_release = res
         return res
 
+    # ---- saving and restoring an online model ----------------------------------------------
+    ONLINE_FORMAT, ONLINE_VERSION = 'tiger-online-state', 1
+    _MAILBOX = ('node_msg_vals', 'node_msg_ts', 'has_msg_bits')
+
+    def _online_fingerprint(self) -> dict:
+        """what a load cannot change: the shapes and choices the modules were constructed with"""
+        fg, r = self.raw_feat_getter, getattr(self, 'restarter_fn', None)
+        return dict(model=type(self).__name__, dim=int(self.nfeat_dim), efeat_dim=int(self.efeat_dim),
+                    has_nfeats=fg.nfeats is not None, has_efeats=fg.efeats is not None, n_layers=int(self.n_layers),
+                    n_neighbors=int(self.n_neighbors), n_head=int(self.n_head), msg_src=self.msg_src, upd_src=self.upd_src,
+                    msg_tsfm_type=self.msg_tsfm_type, mem_update_type=self.mem_update_type, hit_type=self.hit_type,
+                    restarter=None if r is None else type(r).__name__, hist_len=int(getattr(r, 'hist_len', 0)))
+
+    @torch.no_grad()
+    def online_state(self) -> dict:
+        """Everything a served model is made of, as a dict of CPU tensors and plain values (`torch.save`-able, loadable
+        with weights_only=True; the reference - tiger.py, memory.py:127-129, feature_getter.py:41-51 - rebuilds graph,
+        mailbox and tables from the data set and has no counterpart): the module's `state_dict()` (parameters, both
+        memories with active_mask, restarter), the mailbox's three buffers, the node / edge feature tables with EXACTLY
+        their rows (the leading views, not the backing stores; None where the model has none), n_nodes, the graph's
+        `state_dict()` and a fingerprint of what a load cannot change.  After `forget` / `release_edge_rows` / `erase` /
+        `grow_nodes` none of this can be rebuilt by replaying the stream.  NOT saved: optimiser state, `uptodate` bitmaps,
+        CatalogueSnapshots, eids the caller holds.  Refused: a partitioned model (its tables are indexed by row)."""
+        self._refuse_partitioned('online_state')
+        self._poll_train_errors()
+        fg, S = self.raw_feat_getter, self.msg_store
+        cpu = lambda t: None if t is None else t.detach().to('cpu', copy=True)
+        return dict(format=self.ONLINE_FORMAT, version=self.ONLINE_VERSION, fingerprint=self._online_fingerprint(),
+                    n_nodes=int(self.n_nodes), state_dict={k: cpu(v) for k, v in self.state_dict().items()},
+                    mailbox={k: cpu(getattr(S, k)) for k in self._MAILBOX},
+                    nfeats=cpu(fg.nfeats), efeats=cpu(fg.efeats), graph=self.graph.state_dict())
+
+    def save_online(self, f):
+        """`torch.save(self.online_state(), f)`; f: a path or a file object"""
+        torch.save(self.online_state(), f)
+
+    @torch.no_grad()
+    def load_online(self, f_or_state, *, device=None, verify: bool = True):
+        """Become the model that `save_online` / `online_state` saved -> the new graph.  f_or_state: a path, a file object
+        or the dict of `online_state`.  The model is one built by the usual constructor on ANY graph and ANY tables of
+        the right widths (a fresh process builds it on a stub); device: where the loaded graph lives (default: the
+        model's device).  A model that saves at any point of an online run and a freshly built model that loads the file
+        continue bit for bit as the uninterrupted model does: embeddings, both memories, mailbox, graph arrays,
+        `recommend` lists and 'uniform' draws, through later `observe` / `forget` / `erase` / `release_edge_rows` / growth.
+        Everything is checked first: format / version, the fingerprint (dim, widths, n_layers, n_neighbors, n_head,
+        msg_src / upd_src, function types, restarter class and hist_len), key set, dtypes and shapes of the saved
+        state_dict against the model's (per-node tables may hold more rows), the graph (`Graph.from_state_dict` with the
+        rows of the saved edge table: tg_tcsr_verify; verify=False trusts the file's graph), mailbox and table shapes
+        against the saved n_nodes, the spare bits of has_msg_bits.  Then: per-node tables grow to the saved n_nodes (the
+        `grow_nodes` machinery; its refusals apply - a StaticRestarter model must be built with the saved row count), the
+        tables are replaced (`NumericalFeature.install_rows`), state_dict and mailbox are loaded, the graph goes in through
+        the setter (the restarter follows) and derived tables and stamps are dropped.  CatalogueSnapshots, captured
+        device graphs, StepBuffers and resident runs held from before are stale: the caller's part, as for `forget`.
+        Refused before anything changes - IF THE CALL RAISES, EVERY BUFFER, TABLE AND THE GRAPH ARE WHAT THEY WERE: a
+        partitioned model, training mode, tables in pinned host memory (register_buffer=False), a stream capture in
+        progress, a saved n_nodes below the model's, and every check above (ValueError)."""
+        from ..data.graph import Graph
+        what = 'load_online'
+        self._refuse_partitioned(what)
+        if self.training:
+            raise RuntimeError(f'{what}: an online state is loaded in eval() mode (the streaming state of a served model)')
+        fg, S = self.raw_feat_getter, self.msg_store
+        if not fg.pin_mem:
+            raise NotImplementedError(f'{what}: the feature tables live in pinned host memory (register_buffer=False)')
+        if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: tables cannot be replaced while a stream is being captured into a graph')
+        st = f_or_state if isinstance(f_or_state, dict) else torch.load(f_or_state, map_location='cpu', weights_only=True)
+        if not isinstance(st, dict) or st.get('format') != self.ONLINE_FORMAT:
+            raise ValueError(f'{what}: not a saved online state')
+        if st.get('version') != self.ONLINE_VERSION:
+            raise ValueError(f"{what}: version {st.get('version')!r} of the format is unknown (this library reads "
+                             f'{self.ONLINE_VERSION})')
+        missing = [k for k in ('fingerprint', 'n_nodes', 'state_dict', 'mailbox', 'nfeats', 'efeats', 'graph') if k not in st]
+        if missing:
+            raise ValueError(f'{what}: the saved state lacks {missing}')
+        mine = self._online_fingerprint()
+        if st['fingerprint'] != mine:
+            theirs = st['fingerprint'] if isinstance(st['fingerprint'], dict) else {}
+            diff = {k: (theirs.get(k), v) for k, v in mine.items() if theirs.get(k) != v}
+            raise ValueError(f'{what}: the saved model is another model - (saved, this one): {diff}')
+        n = st['n_nodes']
+        if isinstance(n, bool) or not isinstance(n, int):
+            raise ValueError(f'{what}: n_nodes = {n!r}')
+        if n < self.n_nodes:
+            raise ValueError(f'{what}: the saved model has {n} node ids, this one {self.n_nodes} (node ids are never released: '
+                             'build the model on at most the saved count)')
+        # -- the state_dict: keys, dtypes, shapes (per-node tables hold the saved count of rows)
+        own, sd = self.state_dict(), st['state_dict']
+        if not isinstance(sd, dict) or set(sd) != set(own):
+            odd = sorted(set(sd) ^ set(own))[:6] if isinstance(sd, dict) else type(sd).__name__
+            raise ValueError(f'{what}: the saved state_dict has other keys than the model\'s ({odd})')
+        per_node = tuple(f'{m}.{b}' for m in ('left_memory', 'right_memory', 'msg_memory', 'upd_memory')
+                         for b in ('vals', 'update_ts', 'active_mask'))
+        for k, cur in own.items():
+            v = sd[k]
+            want = (n,) + tuple(cur.shape[1:]) if k in per_node else tuple(cur.shape)
+            if not torch.is_tensor(v) or v.dtype != cur.dtype or tuple(v.shape) != want:
+                got = f'{v.dtype} {tuple(v.shape)}' if torch.is_tensor(v) else type(v).__name__
+                raise ValueError(f'{what}: state_dict[{k!r}] is {got}, the model wants {cur.dtype} {want}')
+        # -- mailbox and tables against the saved count
+        mb = st['mailbox']
+        shapes = dict(node_msg_vals=(n, S.dim), node_msg_ts=(n,), has_msg_bits=(hip_ops.bitmap_words(n),))
+        for k in self._MAILBOX:
+            v = mb.get(k) if isinstance(mb, dict) else None
+            if not torch.is_tensor(v) or v.dtype != getattr(S, k).dtype or tuple(v.shape) != shapes[k]:
+                raise ValueError(f'{what}: mailbox[{k!r}] must be {getattr(S, k).dtype} {shapes[k]}')
+        bits = np.unpackbits(mb['has_msg_bits'].contiguous().numpy().view(np.uint8), bitorder='little')
+        if bits[n:].any():
+            raise ValueError(f'{what}: has_msg_bits marks node id {n + int(np.flatnonzero(bits[n:])[0])}, beyond the saved '
+                             f'{n} node ids')
+        tables = {}
+        for name, cur, rows in (('nfeats', fg.nfeats, n), ('efeats', fg.efeats, None)):
+            v = st[name]
+            if (v is None) != (cur is None):
+                raise ValueError(f'{what}: the saved model has {"a" if v is not None else "no"} {name} table, this one '
+                                 f'{"has one" if cur is not None else "none"}')
+            if v is None:
+                continue
+            if (not torch.is_tensor(v) or v.dtype != cur.dtype or v.dim() != 2 or v.shape[1] != cur.shape[1]
+                    or (rows is not None and v.shape[0] != rows) or v.shape[0] < 1):
+                raise ValueError(f'{what}: the saved {name} table does not fit (width {cur.shape[1]}'
+                                 + (f', {rows} rows)' if rows is not None else ')'))
+            tables[name] = v
+        if n > self.n_nodes:
+            self._grow_refusals(what, n, None, None)
+        # -- the graph: nothing of it reaches a sampler before tg_tcsr_verify has passed
+        dev = self.device if device is None else torch.device(device)
+        graph = Graph.from_state_dict(st['graph'], device=dev, verify=verify,
+                                      eid_rows=tables['efeats'].shape[0] if 'efeats' in tables else None)
+        if graph.num_node != n:
+            raise ValueError(f'{what}: the saved graph covers {graph.num_node} node ids, the saved model {n}')
+        # -- everything fits: from here on nothing is refused
+        if n > self.n_nodes:
+            self._grow(n, n - self.n_nodes, None, graph)  # (rows, counts, caches; swaps the graph in through the setter)
+        else:
+            self.graph = graph
+        fg.install_rows(tables.get('nfeats'), tables.get('efeats'))
+        self.load_state_dict(sd)
+        for k in self._MAILBOX:
+            getattr(S, k).copy_(mb[k])
+        S._version_ += 1
+        self._touch()
+        self.invalidate_struct()
+        # what was derived from the old state, graph or tables, as after a growth
+        eager = self._pending is not None
+        self._step_ws = {k: v for k, v in self._step_ws.items() if k == 'rng'}
+        self._gtab = self._ctab = self._gtab_stamp = None
+        self._pending = self._pending_stamp = None
+        if eager:
+            self.eager_updates()
+        return graph
+
     # ---- remaining reference methods -----------------------------------------------------
     @torch.no_grad()
     def update_right_memory(self, node_ids: Tensor, new_vals: Tensor, ts: Tensor):

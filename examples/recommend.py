@@ -37,6 +37,11 @@ batches first.  --load_state PATH starts from such a file instead of train + val
 `init_model` builds: the graph is checked by `tg_tcsr_verify` before anything reads it) and replays the rest of the split.
 A replay that is saved after N batches and one that loads the file write, between them, the lists of the uninterrupted
 replay, exactly.
+--keyed runs the online replay as a service meets its users: every node id of the data set is replaced by an external
+64-bit key (a fixed odd-multiplier scramble of the id), the model sits behind a device id map (`IdMap.from_keys` over the ids
+it was built on), every batch asks `TIGE.recommend_keys` and is ingested with `TIGE.observe_keys`, and the keys admitted are
+printed per batch.  The lists are keys (ids.npy holds int64 keys); without --grow they are the scramble of the offline
+replay's, exactly, and `run_online` asserts it.  With --save_state / --load_state the map's state travels in the same file.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -76,6 +81,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from www2023tiger_amd import hip_ops  # noqa: E402
+from www2023tiger_amd.data.idmap import INT64_MIN, IdMap  # noqa: E402
 from www2023tiger_amd.eval_utils import eval_recommendation  # noqa: E402
 from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
 
@@ -141,11 +147,61 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     return ids, scores, out
 
 
-def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None, first=0, stop=None):
+KEY_MULT = 0x9E3779B97F4A7C15   # odd: id -> id * KEY_MULT (mod 2^64) is a bijection of the 64-bit integers
+
+
+def scramble(ids) -> np.ndarray:
+    """--keyed: the external key of a node id of the data set (int64, wrapping product)"""
+    return (np.asarray(ids).astype(np.int64).astype(np.uint64) * np.uint64(KEY_MULT)).astype(np.int64)
+
+
+def unscramble(keys) -> np.ndarray:
+    return (np.asarray(keys).astype(np.int64).astype(np.uint64) * np.uint64(pow(KEY_MULT, -1, 1 << 64))).astype(np.int64)
+
+
+class _Keyed:
+    """--keyed: the model behind an id map.  The map is seeded with the keys of the ids the model was built on (`from_keys`:
+    they keep their dense ids); ids admitted later get the next dense id in the order of their first appearance, which is
+    not the data set's numbering - so the catalogue, too, is named by keys."""
+
+    def __init__(self, model, catalogue, nfeats, idmap=None):
+        self.model, self.nfeats = model, nfeats
+        self.idmap = idmap if idmap is not None else IdMap.from_keys(torch.from_numpy(scramble(np.arange(1, model.n_nodes))),
+                                                                     model.device)
+        self.cat_keys = torch.from_numpy(scramble(catalogue.cpu().numpy())).to(model.device)
+        self._n = self._cand = None
+
+    def candidates(self):
+        """the keys of the catalogue's items the model knows now, looked up again when ids were admitted"""
+        if self._n != self.model.n_nodes:
+            ids = self.idmap.lookup(self.cat_keys)
+            self._n, self._cand = self.model.n_nodes, self.cat_keys[(ids > 0) & (ids < self.model.n_nodes)].contiguous()
+        return self._cand
+
+    def ask(self, src, t, k, exclude_seen):
+        """-> keys [B, k], and which sources the model knows: a source nobody has seen yet is asked for as the last id and
+        scores as a miss (as in the replay by ids)"""
+        qk = torch.from_numpy(scramble(src)).to(self.model.device)
+        ids = self.idmap.lookup(qk)
+        known = (ids > 0) & (ids < self.model.n_nodes)
+        qk = torch.where(known, qk, self.idmap.key_of[self.model.n_nodes - 1])
+        keys, _, _ = self.model.recommend_keys(self.idmap, qk, t, None, k, cand_keys=self.candidates(), exclude_seen=exclude_seen)
+        return keys, known
+
+    def observe(self, s, d, t, e) -> int:
+        """-> ids admitted.  The feature rows of admitted ids are those of the data set's ids their keys stand for"""
+        n_old = self.model.n_nodes
+        rows = None if self.nfeats is None else (lambda keys: torch.from_numpy(self.nfeats[unscramble(keys.cpu().numpy())]))
+        self.model.observe_keys(self.idmap, torch.from_numpy(scramble(s)), torch.from_numpy(scramble(d)), t, e, nfeats=rows)
+        return self.model.n_nodes - n_old
+
+
+def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None, first=0, stop=None, keyed=None):
     """recommend, then `ingest`, batch by batch over the test split -> (ids [n_test, k], dict of the metrics of
     eval_recommendation: position of the true destination in its list, folded the same way).  known: a callable -> the
     (catalogue, col_of) of the batch, for a model whose node ids grow on the way (run_online(grow=True)).  first / stop: the
-    events [first, stop) of the split alone (a replay that was saved, or will be)"""
+    events [first, stop) of the split alone (a replay that was saved, or will be).  keyed (a _Keyed): the lists are asked
+    for and returned as keys"""
     dev = model.device
     ids, pos = [], []
     place = torch.arange(k, device=dev)
@@ -153,13 +209,17 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=N
     for lo in range(first, stop, bs):
         src, dst, ts, eids = (np.ascontiguousarray(getattr(test, f)[lo:min(lo + bs, stop)]) for f in ('src', 'dst', 'ts', 'eids'))
         q, t, d = torch.from_numpy(src).to(dev), torch.from_numpy(ts.astype(np.float64)).to(dev), torch.from_numpy(dst).to(dev)
-        if known is not None:
-            catalogue, col_of = known()
-            q = q.clamp(max=model.n_nodes - 1)   # a source nobody has seen yet is asked for as the last id (and scores as a miss)
-        i, _, _ = model.recommend(q, t, catalogue, k, exclude_seen=exclude_seen, col_of=col_of)
-        hit = (i == d[:, None]) & (i != 0)
-        if known is not None:
-            hit &= torch.from_numpy(src).to(dev)[:, None] < model.n_nodes
+        if keyed is not None:
+            i, asked = keyed.ask(src, t, k, exclude_seen)
+            hit = (i == torch.from_numpy(scramble(dst)).to(dev)[:, None]) & (i != INT64_MIN) & asked[:, None]
+        else:
+            if known is not None:
+                catalogue, col_of = known()
+                q = q.clamp(max=model.n_nodes - 1)   # a source nobody has seen yet is asked for as the last id (and scores as a miss)
+            i, _, _ = model.recommend(q, t, catalogue, k, exclude_seen=exclude_seen, col_of=col_of)
+            hit = (i == d[:, None]) & (i != 0)
+            if known is not None:
+                hit &= torch.from_numpy(src).to(dev)[:, None] < model.n_nodes
         pos.append(torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1))
         ids.append(i)
         ingest(src, dst, ts.astype(np.float64), eids)
@@ -174,7 +234,7 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=N
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
-               erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None):
+               erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -199,7 +259,10 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     `save_online`'s content plus the position: torch.save(dict(state=model.online_state(), next_event=..., shifted=...)).
     load_state (such a file): the online replay starts from it (`load_online`) instead of the graph over train +
     validation, at the file's position.  With either, no offline replay is made and the online metrics carry 'ids': the
-    lists of the events replayed - a saved replay's followed by the loading one's are the uninterrupted replay's."""
+    lists of the events replayed - a saved replay's followed by the loading one's are the uninterrupted replay's.
+    keyed: the online replay runs behind an id map on scrambled keys (`observe_keys` / `recommend_keys`; module docstring);
+    the online metrics carry 'ids' (int64 KEYS) and 'admitted': keys admitted per batch, and the saved file the map's state.
+    Without grow the lists are scramble(the offline replay's), and that is asserted under the conditions above."""
     from www2023tiger_amd.data.graph import Graph
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -254,9 +317,14 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
             blob = torch.load(load_state, map_location='cpu', weights_only=True)
             model.load_online(blob['state'])
             first, shifted[0] = int(blob['next_event']), int(blob['shifted'])
+            if keyed and 'idmap' not in blob:
+                raise ValueError(f'{load_state} was saved by a replay without --keyed: it holds no id map')
             if verbose:
                 print(f'loaded {load_state}: {model.n_nodes} node ids, {int(model.graph.tcsr.num_entry)} entries, '
                       f'continuing at event {first} of the split')
+        if keyed:
+            keyed = _Keyed(model, catalogue, nfeats if grow else None,
+                           None if load_state is None else IdMap.from_state_dict(blob['idmap'], device))
         erasing = erase_nodes is not None or retract_eids is not None
         erased = None
         if erasing:
@@ -279,6 +347,11 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
             return cache['items'], cache['col_of']
 
         def observe(s, d, t, e):
+            if keyed:
+                admitted.append(keyed.observe(s, d, t, e))
+                if verbose:
+                    print(f'batch {len(admitted) - 1}: {admitted[-1]} keys admitted, {keyed.idmap.size - 1} known')
+                return
             if not grow:
                 return model.observe(s, d, t, e)
             n_old, n_new = model.n_nodes, max(model.n_nodes, int(max(s.max(), d.max())) + 1)
@@ -305,19 +378,24 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         forgetting = window is not None or keep_last is not None
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
                                  observe_and_forget if forgetting else observe, known=known if grow else None,
-                                 first=first, stop=stop)
+                                 first=first, stop=stop, keyed=keyed or None)
         if save_state is not None:
             done = len(test.src) if stop is None else min(stop, len(test.src))
-            torch.save(dict(state=model.online_state(), next_event=done, shifted=shifted[0]), save_state)
+            blob = dict(state=model.online_state(), next_event=done, shifted=shifted[0])
+            if keyed:
+                blob['idmap'] = keyed.idmap.state_dict()
+            torch.save(blob, save_state)
             if verbose:
                 print(f'saved {save_state}: {model.n_nodes} node ids, {int(model.graph.tcsr.num_entry)} entries, '
                       f'{done} events of the split replayed')
     need = max(n_neighbors, hist_len if restarter_type == 'seq' else 0)
     if ids_off is not None and not erasing and (not forgetting or (window is None and keep_last >= need and not exclude_seen)):
-        assert np.array_equal(ids_on, ids_off) and online == offline, (online, offline)
-    if partial or save_state is not None:
+        # (keyed: the padding id 0 of a short list is INT64_MIN among keys)
+        want = np.where(ids_off == 0, INT64_MIN, scramble(ids_off)) if keyed else ids_off
+        assert np.array_equal(ids_on, want) and online == offline, (online, offline)
+    if partial or save_state is not None or keyed:
         online = dict(online, ids=ids_on)
-    if grow:
+    if grow or keyed:
         online = dict(online, admitted=admitted)
     if erasing:
         online = dict(online, erased=erased)
@@ -407,6 +485,8 @@ if __name__ == '__main__':
     ap.add_argument('--save_after', type=int, default=None, metavar='N', help='--save_state: stop the replay after N batches')
     ap.add_argument('--load_state', default=None, metavar='PATH', help='--online: start from a file of --save_state instead '
                     'of train + validation (TIGE.load_online) and replay the rest of the split')
+    ap.add_argument('--keyed', action='store_true', help='--online: every node id becomes an external 64-bit key; the model '
+                    'sits behind a device id map (observe_keys / recommend_keys) and ids.npy holds keys')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -429,9 +509,12 @@ if __name__ == '__main__':
                                                               erase_nodes=None if a.erase_nodes is None else np.load(a.erase_nodes),
                                                               retract_eids=None if a.retract_eids is None
                                                               else np.load(a.retract_eids), save_state=a.save_state,
-                                                              save_after=a.save_after, load_state=a.load_state)):
+                                                              save_after=a.save_after, load_state=a.load_state,
+                                                              keyed=a.keyed)):
             if m is None:
                 continue
+            if a.keyed and 'ids' in m:
+                np.save(os.path.join(a.out_dir, 'ids.npy'), m['ids'])   # int64 keys; INT64_MIN pads a short list
             print(f"{name}: HitRate@{a.k} {m['hit_rate']:.6f}  NDCG@{a.k} {m['ndcg']:.6f}  MRR@{a.k} {m['mrr_at_k']:.6f}  "
                   f"({m['n_events']} events)")
         sys.exit(0)

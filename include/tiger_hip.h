@@ -236,6 +236,58 @@ size_t tg_tcsr_verify_workspace_bytes(int64_t num_entry, int64_t num_node);
 int tg_tcsr_verify(const tg_tcsr* g, int64_t eid_rows, int64_t* out8, void* ws, size_t ws_bytes, void* stream);
 int tg_tcsr_verify_host(const tg_tcsr* g, int64_t eid_rows, int64_t* out8_host);
 
+/* The device id map (tg_idmap.hip; online serving behind external keys.  The reference numbers its nodes offline and has
+ * no counterpart of this).  External keys are int64, dense ids int32; `size` = ids in use, the padding id 0 included (a
+ * fresh map has size 1), and is kept by the caller.
+ *   slot_key [capacity]  open addressing, linear probing; TG_IDMAP_EMPTY (INT64_MIN) marks an empty slot
+ *   slot_id  [capacity]  -1 in an empty slot, the key's id in [1, size) otherwise
+ *   key_of   [key_rows]  dense id -> key; key_of[0] = INT64_MIN
+ * INT64_MIN is by definition the key of the padding id: looking it up or assigning it gives id 0, it is never inserted and
+ * is no error.  capacity: a power of two in [16, 2^32].  The home slot of a key is tg_idmap_hash(key) & (capacity - 1):
+ *   z = (uint64) key + 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *   hash = z ^ z >> 31                                                                    (the splitmix64 step)
+ * The mapping never depends on the hash or on which workgroup wins a slot; where a key sits in the table may.
+ * tg_idmap_lookup: ids_out[i] = the id of keys[i], -1 for a key the map does not hold, 0 for INT64_MIN.  Read-only, one
+ * launch.
+ * tg_idmap_assign: lookup-or-insert.  A key the map does not hold gets size + r, r = the rank of its FIRST occurrence in
+ * keys[] among the first occurrences of all such keys - what `for x in keys: d.setdefault(x, len(d))` gives, so a stream
+ * gets the same ids however it is cut into batches.  key_of[size .. new size) is written; out2 (DEVICE, int64 [2]) =
+ * {new size, error word}: the one read-back of a call.  One launch for n <= 256, four dependent launches above; no kernel
+ * waits for a value another workgroup writes, and every probe loop ends after `capacity` slots (TG_IDMAP_ERR_PROBE).
+ * ids_out and key_of are the same bits on every run; ws: tg_idmap_assign_workspace_bytes(n) bytes, 16-byte aligned
+ * (about 9 bytes per key; 0 for a bad n), contents irrelevant before and after.
+ * tg_idmap_rebuild: fills an EMPTY table (slot_key all TG_IDMAP_EMPTY, slot_id all -1) from key_of[1 .. size): growth and
+ * loading.  Two launches.  out2 = {size, error word}; error word 0 = clean, else ((0x7fffffff - row) << 8) | class for the
+ * SMALLEST offending row: TG_IDMAP_ERR_DUP (the row repeats the key of an earlier row), TG_IDMAP_ERR_EMPTY_KEY (INT64_MIN
+ * in a row >= 1).
+ * TG_EINVAL before any launch: a missing array, a capacity that is no power of two in [16, 2^32], size < 1, n < 0,
+ * size + n > 2^31 - 1, 2 (size + n) > capacity (the table stays at most half full: a probe never meets the bound on a
+ * table this library made), size + n > key_rows.  TG_EWORKSPACE: a short workspace.
+ * The _host twins: HOST pointers (those of `map` included), plain C++, the same results bit for bit (slot contents may
+ * differ in where a key sits). */
+#define TG_IDMAP_EMPTY INT64_MIN
+#define TG_IDMAP_ERR_PROBE 1     /* `capacity` slots probed without meeting the key or an empty slot */
+#define TG_IDMAP_ERR_DUP 2       /* rebuild: a key stands in two rows of key_of */
+#define TG_IDMAP_ERR_EMPTY_KEY 4 /* rebuild: INT64_MIN in a row >= 1 of key_of */
+#define TG_IDMAP_ERR_TABLE 8     /* a slot_id that is no id of this map: the table was not made by this library */
+typedef struct tg_idmap {
+  int64_t capacity;
+  int64_t key_rows;
+  int64_t* slot_key;
+  int32_t* slot_id;
+  int64_t* key_of;
+} tg_idmap;
+uint64_t tg_idmap_hash(int64_t key);
+size_t tg_idmap_assign_workspace_bytes(int64_t n);
+int tg_idmap_lookup(const tg_idmap* map, const int64_t* keys, int64_t n, int32_t* ids_out, void* stream);
+int tg_idmap_assign(const tg_idmap* map, int64_t size, const int64_t* keys, int64_t n, int32_t* ids_out, int64_t* out2,
+                    void* ws, size_t ws_bytes, void* stream);
+int tg_idmap_rebuild(const tg_idmap* map, int64_t size, int64_t* out2, void* stream);
+int tg_idmap_lookup_host(const tg_idmap* map, const int64_t* keys_host, int64_t n, int32_t* ids_out_host);
+int tg_idmap_assign_host(const tg_idmap* map, int64_t size, const int64_t* keys_host, int64_t n, int32_t* ids_out_host,
+                         int64_t* out2_host);
+int tg_idmap_rebuild_host(const tg_idmap* map, int64_t size, int64_t* out2_host);
+
 /* Releasing edge-feature rows (tg_edge_rows.hip; online serving after a trim).  The reference never drops a row of its
  * tables (feature_getter.py:41-47, graph.py:11-42: built once over the whole stream).  A row r of the table
  * T [n_rows, d_e] (float32, d_e % 4 == 0) is LIVE iff r == 0 (the padding row), some entry of g has

@@ -44,6 +44,15 @@ class TgTcsr(C.Structure):
     _fields_ = [('num_node', i64), ('num_entry', i64), ('indptr', vp), ('ts', vp), ('nbr', vp), ('eid', vp)]
 
 
+class TgIdmap(C.Structure):
+    """tiger_hip.h: tg_idmap - the device id map (external int64 keys -> dense int32 ids)"""
+    _fields_ = [('capacity', i64), ('key_rows', i64), ('slot_key', vp), ('slot_id', vp), ('key_of', vp)]
+
+
+TG_IDMAP_EMPTY = -(1 << 63)
+TG_IDMAP_ERR_PROBE, TG_IDMAP_ERR_DUP, TG_IDMAP_ERR_EMPTY_KEY, TG_IDMAP_ERR_TABLE = 1, 2, 4, 8
+
+
 class TgAdvIndex(C.Structure):
     """tiger_hip.h: tg_adv_index - the pair index of historical / inductive negative sampling"""
     _fields_ = [('next_ts', vp), ('first_ts', vp)]
@@ -201,6 +210,14 @@ SIGNATURES = {
     'tg_tcsr_verify_workspace_bytes': (sz, [i64, i64]),
     'tg_tcsr_verify': (C.c_int, [P(TgTcsr), i64, vp, vp, sz, vp]),
     'tg_tcsr_verify_host': (C.c_int, [P(TgTcsr), i64, vp]),
+    'tg_idmap_hash': (C.c_uint64, [i64]),
+    'tg_idmap_assign_workspace_bytes': (sz, [i64]),
+    'tg_idmap_lookup': (C.c_int, [P(TgIdmap), vp, i64, vp, vp]),
+    'tg_idmap_assign': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, vp, vp, sz, vp]),
+    'tg_idmap_rebuild': (C.c_int, [P(TgIdmap), i64, vp, vp]),
+    'tg_idmap_lookup_host': (C.c_int, [P(TgIdmap), vp, i64, vp]),
+    'tg_idmap_assign_host': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, vp]),
+    'tg_idmap_rebuild_host': (C.c_int, [P(TgIdmap), i64, vp]),
     'tg_edge_rows_workspace_bytes': (sz, [i64, i64]),
     'tg_edge_rows_plan': (C.c_int, [P(TgTcsr), i64, i64, vp, i64, vp, vp, vp, sz, vp]),
     'tg_edge_rows_apply': (C.c_int, [P(TgTcsr), vp, i64, i32, vp, i64, vp, vp, vp, sz, vp]),

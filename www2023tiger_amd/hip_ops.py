@@ -884,3 +884,88 @@ def tcsr_verify_host(arrays_or_graph, eid_rows: Optional[int] = None):
     out8 = np.empty(8, dtype=np.int64)
     check(lib.tg_tcsr_verify_host(C_.byref(g), -1 if eid_rows is None else int(eid_rows), ptr(out8)), 'tg_tcsr_verify_host')
     return _verify_result(out8)
+
+
+# ---- the device id map: external int64 keys -> dense int32 ids (tg_idmap_* and their host twins) ---------------------------
+IDMAP_EMPTY = _lib.TG_IDMAP_EMPTY
+_IDMAP_CLASSES = ((_lib.TG_IDMAP_ERR_PROBE, 'PROBE: a probe ran through the whole table'),
+                  (_lib.TG_IDMAP_ERR_DUP, 'DUP: the key stands in an earlier row too'),
+                  (_lib.TG_IDMAP_ERR_EMPTY_KEY, 'EMPTY_KEY: INT64_MIN is the key of the padding id 0 alone'),
+                  (_lib.TG_IDMAP_ERR_TABLE, 'TABLE: a slot holds no id of this map'))
+
+
+def IDMAP_ERR_TEXT(word: int) -> str:
+    """The message of a non-zero tg_idmap error word: the classes by name and, from a rebuild, the smallest offending row."""
+    word = int(word)
+    names = '; '.join(text for bit, text in _IDMAP_CLASSES if word & bit)
+    return names + (f', at row {0x7FFFFFFF - (word >> 8)} of key_of' if word >> 8 else '')
+
+
+def idmap_tables(capacity: int, key_rows: int, device) -> Tuple[Tensor, Tensor, Tensor]:
+    """an empty table of `capacity` slots and a reverse table of key_rows rows that holds the padding id alone"""
+    slot_key = torch.full((capacity,), IDMAP_EMPTY, dtype=torch.int64, device=device)
+    slot_id = torch.full((capacity,), -1, dtype=torch.int32, device=device)
+    key_of = torch.full((key_rows,), IDMAP_EMPTY, dtype=torch.int64, device=device)
+    return slot_key, slot_id, key_of
+
+
+def _idmap_struct(what: str, tables, keys: Optional[Tensor] = None):
+    slot_key, slot_id, key_of = tables
+    dev = slot_key.device
+    for t, dt, name in ((slot_key, torch.int64, 'slot_key'), (slot_id, torch.int32, 'slot_id'), (key_of, torch.int64, 'key_of')):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f'{what}: {name} must be a contiguous 1-d tensor of {dt} on {dev}')
+    if slot_id.numel() != slot_key.numel():
+        raise ValueError(f'{what}: slot_key and slot_id must have one entry per slot')
+    if keys is not None and not (torch.is_tensor(keys) and keys.dtype == torch.int64 and keys.dim() == 1
+                                 and keys.is_contiguous() and keys.device == dev):
+        raise ValueError(f'{what}: keys must be a contiguous 1-d int64 tensor on {dev}')
+    return _lib.TgIdmap(slot_key.numel(), key_of.numel(), ptr(slot_key), ptr(slot_id), ptr(key_of)), dev
+
+
+def idmap_lookup(tables, keys: Tensor) -> Tensor:
+    """tiger_hip.h: tg_idmap_lookup (tables on the CPU: its host twin) -> ids int32 [n]: -1 for a key the map does not
+    hold, 0 for INT64_MIN.  Read-only, no read-back."""
+    m, dev = _idmap_struct('idmap_lookup', tables, keys)
+    n = keys.numel()
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    if dev.type == 'cpu':
+        check(lib.tg_idmap_lookup_host(C_.byref(m), ptr(keys), n, ptr(ids)), 'tg_idmap_lookup_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_idmap_lookup(C_.byref(m), ptr(keys), n, ptr(ids), stream_ptr(dev)), 'tg_idmap_lookup')
+    return ids
+
+
+def idmap_assign(tables, size: int, keys: Tensor) -> Tuple[Tensor, int, int]:
+    """tiger_hip.h: tg_idmap_assign (tables on the CPU: its host twin) -> (ids int32 [n], new size, error word).  The tables
+    are updated in place; ONE read-back, of the two result words.  The entry refuses a table that would pass half full or
+    a key_of too short for size + n (TigerHipError): IdMap.assign grows first."""
+    m, dev = _idmap_struct('idmap_assign', tables, keys)
+    n = keys.numel()
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    out2 = torch.empty(2, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        check(lib.tg_idmap_assign_host(C_.byref(m), size, ptr(keys), n, ptr(ids), ptr(out2)), 'tg_idmap_assign_host')
+    else:
+        with torch.cuda.device(dev):
+            nbytes = int(lib.tg_idmap_assign_workspace_bytes(n))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            check(lib.tg_idmap_assign(C_.byref(m), size, ptr(keys), n, ptr(ids), ptr(out2), ptr(ws), nbytes, stream_ptr(dev)),
+                  'tg_idmap_assign')
+    new_size, err = out2.tolist()
+    return ids, int(new_size), int(err)
+
+
+def idmap_rebuild(tables, size: int, read_back: bool = True):
+    """tiger_hip.h: tg_idmap_rebuild (tables on the CPU: its host twin): fills the EMPTY table from key_of[1 .. size) -> the
+    error word (0: clean; IDMAP_ERR_TEXT), or with read_back=False the two device words {size, error word} unread - a
+    caller that knows its keys distinct (a growth) reads nothing."""
+    m, dev = _idmap_struct('idmap_rebuild', tables)
+    out2 = torch.empty(2, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        check(lib.tg_idmap_rebuild_host(C_.byref(m), size, ptr(out2)), 'tg_idmap_rebuild_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_idmap_rebuild(C_.byref(m), size, ptr(out2), stream_ptr(dev)), 'tg_idmap_rebuild')
+    return int(out2[1].item()) if read_back else out2

@@ -1749,6 +1749,95 @@ class TIGE(nn.Module):
         graph = self.graph if self.graph.num_node == num_node else self.graph.widened(num_node)
         return self._grow(num_node, nfeats, reserve, graph)
 
+    # ---- serving behind external keys (data/idmap.py: IdMap) ------------------------------------------------
+    def _device_keys(self, what: str, name: str, keys) -> Tensor:
+        keys = torch.as_tensor(keys)
+        if keys.dtype != torch.int64:
+            raise ValueError(f'{what}: {name} are int64 keys, not {keys.dtype}')
+        return keys.to(self.device).contiguous()
+
+    def _keyed_refusals(self, what: str, idmap, keys: Tensor):
+        """what an admission of the keys' new ids would be refused for and that can be told WITHOUT the ids - before a key
+        is assigned"""
+        self._refuse_partitioned(what)
+        if self.training:
+            raise RuntimeError(f'{what}: keys are admitted in eval() mode (the streaming state of a served model)')
+        if idmap.device != self.device:
+            raise ValueError(f'{what}: the id map lives on {idmap.device}, the model on {self.device}')
+        if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: assigning keys reads the new size back; it cannot be captured into a graph')
+        from .restarters import StaticRestarter
+        if isinstance(getattr(self, 'restarter_fn', None), StaticRestarter):
+            unknown = int((idmap.lookup(keys) < 0).sum()) if keys.numel() else 0
+            if unknown or idmap.size > self.n_nodes:
+                raise NotImplementedError(f'{what}: {unknown} keys are new, and the static restarter holds one TRAINED '
+                                          'embedding row per node; a new node has none')
+
+    def observe_keys(self, idmap, src_keys, dst_keys, ts, eids, **observe_kwargs):
+        """`observe` for a stream that names its nodes by external int64 keys: the batch's keys are assigned dense ids by
+        `idmap` (an IdMap on the model's device) in EVENT order - src[0], dst[0], src[1], dst[1], ... - and the batch is
+        observed with num_node = max(idmap.size, n_nodes) -> the step's StepBuffers.  A key the map does not hold gets
+        the next id in the order of first appearance, so a stream gets the same ids - and the model ends in the same
+        state, bit for bit - however it is cut into batches, and a model built on dense ids goes behind keys with
+        `IdMap.from_keys` without being renumbered.  One read-back (the new size) on top of observe's.
+        observe_kwargs: those of observe but num_node.  nfeats may be a CALLABLE: it is handed the keys (int64, device) of
+        the ids the model is about to admit, [n_nodes, idmap.size), and returns their feature rows.
+        Refused before a key is assigned: a partitioned model, training mode, a captured stream, a map on another
+        device, keys that are no int64, and - with a static restarter - a batch that holds a key the map does not.
+        Whatever else observe / grow_nodes refuse (a batch that goes back in time, an eid that is no row, feature rows of
+        another shape, ...) is refused AFTER the assignment: the model is untouched, but the keys stay assigned - a key
+        may precede its first event; the next observe_keys admits its id with the batch it arrives in."""
+        if 'num_node' in observe_kwargs:
+            raise TypeError('observe_keys: num_node follows from the id map')
+        src_keys = self._device_keys('observe_keys', 'src_keys', src_keys).reshape(-1)
+        dst_keys = self._device_keys('observe_keys', 'dst_keys', dst_keys).reshape(-1)
+        if src_keys.numel() != dst_keys.numel():
+            raise ValueError('observe_keys: src_keys and dst_keys must have one entry per event')
+        keys = torch.stack([src_keys, dst_keys], 1).reshape(-1)  # event order
+        self._keyed_refusals('observe_keys', idmap, keys)
+        ids = idmap.assign(keys).view(-1, 2).long()
+        num_node = max(idmap.size, self.n_nodes)
+        nfeats = observe_kwargs.pop('nfeats', None)
+        if callable(nfeats):
+            nfeats = nfeats(idmap.key_of[self.n_nodes:num_node])
+        return self.observe(ids[:, 0].contiguous(), ids[:, 1].contiguous(), torch.as_tensor(ts).to(self.device),
+                            torch.as_tensor(eids).to(self.device), num_node=num_node, nfeats=nfeats, **observe_kwargs)
+
+    def recommend_keys(self, idmap, src_keys, ts, cand, k: int, *, cand_keys=None, admit: bool = False, **recommend_kwargs):
+        """`recommend` behind external keys -> (keys int64 [B, k], scores float32 [B, k], n_valid int32 [B]); keys =
+        idmap.keys_of(ids), so positions past n_valid[i] hold INT64_MIN, the key of the padding id.
+        cand: a CatalogueSnapshot or a tensor of dense ids, as in recommend - or None with cand_keys=, a tensor of keys
+        ([C] or [B, C]) that is looked up: a candidate the map does not hold, or whose id the model has not admitted yet,
+        becomes the padding id 0 and is thereby left out.
+        The sources are looked up.  admit=False: a source the map (or the model) does not know raises ValueError saying
+        how many - one read-back - and nothing has changed.  admit=True: unknown sources are ASSIGNED (in their order in
+        src_keys) and the model grows to idmap.size (grow_nodes): a brand-new user is a zero-state node without history -
+        `recommend_walk`'s fill= is what gives such a user a list worth showing.  What an admission is refused for is
+        refused as in observe_keys."""
+        if (cand is None) == (cand_keys is None):
+            raise ValueError('recommend_keys: pass cand (a snapshot or dense ids) or cand_keys=, one of them')
+        src_keys = self._device_keys('recommend_keys', 'src_keys', src_keys).reshape(-1)
+        if idmap.device != self.device:
+            raise ValueError(f'recommend_keys: the id map lives on {idmap.device}, the model on {self.device}')
+        if cand_keys is not None:
+            cand_keys = self._device_keys('recommend_keys', 'cand_keys', cand_keys)
+        if admit:
+            self._keyed_refusals('recommend_keys', idmap, src_keys)
+            ids = idmap.assign(src_keys)
+            if idmap.size > self.n_nodes:
+                self.grow_nodes(idmap.size)
+        else:
+            ids = idmap.lookup(src_keys)
+            unknown = int(((ids < 0) | (ids >= self.n_nodes)).sum())
+            if unknown:
+                raise ValueError(f'recommend_keys: {unknown} of the {ids.numel()} sources are keys the model has never seen '
+                                 '(admit=True assigns them ids and grows the model)')
+        if cand_keys is not None:  # (after an admission: the model's count is the one the candidates are held against)
+            cand = idmap.lookup(cand_keys.reshape(-1)).long().view(cand_keys.shape)
+            cand = torch.where((cand < 0) | (cand >= self.n_nodes), torch.zeros_like(cand), cand)
+        out, scores, n_valid = self.recommend(ids.long(), ts, cand, k, **recommend_kwargs)
+        return idmap.keys_of(out, check=False), scores, n_valid
+
     def forget(self, before=None, keep_last=None, release_edge_rows: bool = False, keep_from=None):
         """Sliding-window expiry for a model that keeps observing: the graph is replaced by `graph.trimmed(before,
         keep_last)` (entries with a time strictly below `before`, and entries that are not among their node's last

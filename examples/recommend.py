@@ -42,6 +42,9 @@ replay, exactly.
 it was built on), every batch asks `TIGE.recommend_keys` and is ingested with `TIGE.observe_keys`, and the keys admitted are
 printed per batch.  The lists are keys (ids.npy holds int64 keys); without --grow they are the scramble of the offline
 replay's, exactly, and `run_online` asserts it.  With --save_state / --load_state the map's state travels in the same file.
+--churn FILE (with --keyed) names, per batch, the keys that leave behind it: their nodes are erased and their keys removed
+(`TIGE.erase_keys`), the released dense ids go to the keys later batches bring, and released / recycled / n_nodes are
+printed per batch - the model stays as large as its peak of live keys.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -234,7 +237,8 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=N
 def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
-               erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False):
+               erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False,
+               churn=None):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -262,8 +266,23 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     lists of the events replayed - a saved replay's followed by the loading one's are the uninterrupted replay's.
     keyed: the online replay runs behind an id map on scrambled keys (`observe_keys` / `recommend_keys`; module docstring);
     the online metrics carry 'ids' (int64 KEYS) and 'admitted': keys admitted per batch, and the saved file the map's state.
-    Without grow the lists are scramble(the offline replay's), and that is asserted under the conditions above."""
+    Without grow the lists are scramble(the offline replay's), and that is asserted under the conditions above.
+    churn (a path; keyed only): a text file of lines `batch key` - the keys that LEAVE behind that batch of the split
+    (`erase_keys`: their nodes are erased, their keys removed from the map, their dense ids handed out again to the keys
+    the next batches bring).  The replay prints, and its metrics carry per batch, 'released' (ids the map released) and
+    'recycled' (released ids handed out again), and 'n_nodes' at the end: with accounts that come and go the model stays
+    as large as its peak of live keys.  No offline replay is made."""
     from www2023tiger_amd.data.graph import Graph
+    if churn is not None and not keyed:
+        raise ValueError('churn names the nodes that leave by their keys: it needs --keyed')
+    leaving = {}
+    if churn is not None:
+        offline = False
+        with open(churn) as f:
+            for line in f:
+                line = line.split('#')[0].split()
+                if line:
+                    leaving.setdefault(int(line[0]), []).append(int(line[1]))
     device = torch.device(device)
     torch.manual_seed(seed)
     basic, (train_graph, full_graph), dls = init_data(
@@ -338,6 +357,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         rows = []
 
         admitted = []
+        released, recycled = [], []
         cache = {}
 
         def known():   # the items the model knows now (and their index), rebuilt when ids were admitted
@@ -348,9 +368,19 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
 
         def observe(s, d, t, e):
             if keyed:
+                free = keyed.idmap.n_free
                 admitted.append(keyed.observe(s, d, t, e))
                 if verbose:
                     print(f'batch {len(admitted) - 1}: {admitted[-1]} keys admitted, {keyed.idmap.size - 1} known')
+                if churn is not None:
+                    b = first // bs + len(admitted) - 1
+                    recycled.append(free - keyed.idmap.n_free)
+                    gone = leaving.get(b)
+                    released.append(0 if not gone else
+                                    int(model.erase_keys(keyed.idmap, torch.tensor(gone, dtype=torch.int64))[1].numel()))
+                    keyed._n = None   # (the catalogue's keys are looked up again: items may have left or come back)
+                    if verbose:
+                        print(f'batch {b}: {released[-1]} ids released, {recycled[-1]} recycled, n_nodes {model.n_nodes}')
                 return
             if not grow:
                 return model.observe(s, d, t, e)
@@ -397,6 +427,10 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         online = dict(online, ids=ids_on)
     if grow or keyed:
         online = dict(online, admitted=admitted)
+    if keyed:
+        online = dict(online, n_nodes=int(model.n_nodes))
+    if churn is not None:
+        online = dict(online, released=released, recycled=recycled)
     if erasing:
         online = dict(online, erased=erased)
     if forgetting:
@@ -487,6 +521,9 @@ if __name__ == '__main__':
                     'of train + validation (TIGE.load_online) and replay the rest of the split')
     ap.add_argument('--keyed', action='store_true', help='--online: every node id becomes an external 64-bit key; the model '
                     'sits behind a device id map (observe_keys / recommend_keys) and ids.npy holds keys')
+    ap.add_argument('--churn', default=None, metavar='FILE', help='--online --keyed: a text file of lines "batch key" - the '
+                    'keys that leave behind that batch (TIGE.erase_keys); their dense ids are handed out again, and the ids '
+                    'released and recycled and n_nodes are printed per batch')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -510,7 +547,7 @@ if __name__ == '__main__':
                                                               retract_eids=None if a.retract_eids is None
                                                               else np.load(a.retract_eids), save_state=a.save_state,
                                                               save_after=a.save_after, load_state=a.load_state,
-                                                              keyed=a.keyed)):
+                                                              keyed=a.keyed, churn=a.churn)):
             if m is None:
                 continue
             if a.keyed and 'ids' in m:

@@ -288,6 +288,52 @@ int tg_idmap_assign_host(const tg_idmap* map, int64_t size, const int64_t* keys_
                          int64_t* out2_host);
 int tg_idmap_rebuild_host(const tg_idmap* map, int64_t size, int64_t* out2_host);
 
+/* Removing keys and recycling dense ids (tg_idmap.hip; a service whose accounts come and go).  Entries added beside the
+ * ones above, which stay as they are; struct tg_idmap is unchanged.  State the caller keeps on top of `size`:
+ *   free_bits [free_words]  uint64 words over the dense ids, free_words >= ceil(size / 64); bit i set <=> id i was released
+ *                           and not handed out again <=> key_of[i] == INT64_MIN (1 <= i < size)
+ *   n_free                  the number of set bits
+ *   occupied                an upper bound on the slots in use, those of removed keys included: a removed slot keeps its
+ *                           slot_key (probe chains stay intact) and gets slot_id = -1; tg_idmap_lookup answers -1 for it and
+ *                           an assign treats its key as a new key.  `size` never shrinks: it is the high-water mark.
+ * tg_idmap_remove: ids_out[i] = the id keys[i] had (-1: the map does not hold it, 0: INT64_MIN); released_out[i] = that id
+ * at exactly ONE position per distinct released id, INT32_MAX elsewhere (which of a key's copies is not specified);
+ * out2 (DEVICE) = {distinct ids released, error bits}: the one read-back.  One launch for n <= 256, two above.
+ * ws: tg_idmap_remove_workspace_bytes(n).
+ * tg_idmap_assign_recycle: tg_idmap_assign for a map with n_free > 0 (n_free = 0 is legal and gives the same ids as
+ * tg_idmap_assign).  The new key of rank r - the r-th first occurrence among the new keys - gets the r-th SMALLEST free id
+ * while r < n_free and size + (r - n_free) after that: what a loop that pops a heap of free ids gives.
+ * free_list_out [min(n_free, n)] = the smallest free ids, ascending, as they were BEFORE the call: its first
+ * min(n_new, n_free) entries are the ids recycled by this call in the order they were given out.  out2 = {size + n_new,
+ * error bits}, n_new = the new keys: the caller's size grows by max(0, n_new - n_free), n_free falls by min(n_free, n_new),
+ * occupied grows by n_new.  Two launches for the select over the bitmap (tiles of 131 072 ids), then one for n <= 256 and
+ * four above.  ws: tg_idmap_assign_recycle_workspace_bytes(n, size).
+ * tg_idmap_rebuild_free: tg_idmap_rebuild for a key_of with holes; `live` = rows that hold a key, the padding row included.
+ * A row whose bit is set is skipped.  Reported by the smallest row: INT64_MIN under a clear bit (TG_IDMAP_ERR_EMPTY_KEY), a
+ * key under a set bit (TG_IDMAP_ERR_FREE).
+ * TG_EINVAL before any launch: what the entries above refuse for the struct, free_bits missing or free_words <
+ * ceil(size / 64), n_free outside [0, size), 2 (occupied + n) > capacity (rebuild_free: 2 live > capacity),
+ * size + max(0, n - n_free) > key_rows or > 2^31 - 1.  No kernel waits for another workgroup, every probe loop ends after
+ * `capacity` slots, and an id loaded from the table or the free list becomes an address only after a range check. */
+#define TG_IDMAP_ERR_FREE 16 /* free_bits and key_of (or n_free) disagree */
+size_t tg_idmap_remove_workspace_bytes(int64_t n);
+int tg_idmap_remove(const tg_idmap* map, int64_t size, uint64_t* free_bits, int64_t free_words, const int64_t* keys, int64_t n,
+                    int32_t* ids_out, int32_t* released_out, int64_t* out2, void* ws, size_t ws_bytes, void* stream);
+size_t tg_idmap_assign_recycle_workspace_bytes(int64_t n, int64_t size);
+int tg_idmap_assign_recycle(const tg_idmap* map, int64_t size, int64_t occupied, uint64_t* free_bits, int64_t free_words,
+                            int64_t n_free, const int64_t* keys, int64_t n, int32_t* ids_out, int32_t* free_list_out,
+                            int64_t* out2, void* ws, size_t ws_bytes, void* stream);
+int tg_idmap_rebuild_free(const tg_idmap* map, int64_t size, int64_t live, const uint64_t* free_bits, int64_t free_words,
+                          int64_t* out2, void* stream);
+int tg_idmap_remove_host(const tg_idmap* map, int64_t size, uint64_t* free_bits_host, int64_t free_words,
+                         const int64_t* keys_host, int64_t n, int32_t* ids_out_host, int32_t* released_out_host,
+                         int64_t* out2_host);
+int tg_idmap_assign_recycle_host(const tg_idmap* map, int64_t size, int64_t occupied, uint64_t* free_bits_host,
+                                 int64_t free_words, int64_t n_free, const int64_t* keys_host, int64_t n,
+                                 int32_t* ids_out_host, int32_t* free_list_out_host, int64_t* out2_host);
+int tg_idmap_rebuild_free_host(const tg_idmap* map, int64_t size, int64_t live, const uint64_t* free_bits_host,
+                               int64_t free_words, int64_t* out2_host);
+
 /* Releasing edge-feature rows (tg_edge_rows.hip; online serving after a trim).  The reference never drops a row of its
  * tables (feature_getter.py:41-47, graph.py:11-42: built once over the whole stream).  A row r of the table
  * T [n_rows, d_e] (float32, d_e % 4 == 0) is LIVE iff r == 0 (the padding row), some entry of g has

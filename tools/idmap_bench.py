@@ -98,6 +98,7 @@ def measure(n_map, n, shares, reps, dev, one_max=256):
         work.slot_key.copy_(base.slot_key)
         work.slot_id.copy_(base.slot_id)
         work.size = base.size
+        work.slots_used = base.slots_used   # (the host's count of used slots follows the table it describes)
     work.key_of.copy_(base.key_of)
     rows = []
     for share in shares:

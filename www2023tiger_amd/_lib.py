@@ -50,7 +50,7 @@ class TgIdmap(C.Structure):
 
 
 TG_IDMAP_EMPTY = -(1 << 63)
-TG_IDMAP_ERR_PROBE, TG_IDMAP_ERR_DUP, TG_IDMAP_ERR_EMPTY_KEY, TG_IDMAP_ERR_TABLE = 1, 2, 4, 8
+TG_IDMAP_ERR_PROBE, TG_IDMAP_ERR_DUP, TG_IDMAP_ERR_EMPTY_KEY, TG_IDMAP_ERR_TABLE, TG_IDMAP_ERR_FREE = 1, 2, 4, 8, 16
 
 
 class TgAdvIndex(C.Structure):
@@ -218,6 +218,14 @@ SIGNATURES = {
     'tg_idmap_lookup_host': (C.c_int, [P(TgIdmap), vp, i64, vp]),
     'tg_idmap_assign_host': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, vp]),
     'tg_idmap_rebuild_host': (C.c_int, [P(TgIdmap), i64, vp]),
+    'tg_idmap_remove_workspace_bytes': (sz, [i64]),
+    'tg_idmap_remove': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, i64, vp, vp, vp, vp, sz, vp]),
+    'tg_idmap_assign_recycle_workspace_bytes': (sz, [i64, i64]),
+    'tg_idmap_assign_recycle': (C.c_int, [P(TgIdmap), i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, sz, vp]),
+    'tg_idmap_rebuild_free': (C.c_int, [P(TgIdmap), i64, i64, vp, i64, vp, vp]),
+    'tg_idmap_remove_host': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, i64, vp, vp, vp]),
+    'tg_idmap_assign_recycle_host': (C.c_int, [P(TgIdmap), i64, i64, vp, i64, i64, vp, i64, vp, vp, vp]),
+    'tg_idmap_rebuild_free_host': (C.c_int, [P(TgIdmap), i64, i64, vp, i64, vp]),
     'tg_edge_rows_workspace_bytes': (sz, [i64, i64]),
     'tg_edge_rows_plan': (C.c_int, [P(TgTcsr), i64, i64, vp, i64, vp, vp, vp, sz, vp]),
     'tg_edge_rows_apply': (C.c_int, [P(TgTcsr), vp, i64, i32, vp, i64, vp, vp, vp, sz, vp]),

@@ -891,7 +891,8 @@ IDMAP_EMPTY = _lib.TG_IDMAP_EMPTY
 _IDMAP_CLASSES = ((_lib.TG_IDMAP_ERR_PROBE, 'PROBE: a probe ran through the whole table'),
                   (_lib.TG_IDMAP_ERR_DUP, 'DUP: the key stands in an earlier row too'),
                   (_lib.TG_IDMAP_ERR_EMPTY_KEY, 'EMPTY_KEY: INT64_MIN is the key of the padding id 0 alone'),
-                  (_lib.TG_IDMAP_ERR_TABLE, 'TABLE: a slot holds no id of this map'))
+                  (_lib.TG_IDMAP_ERR_TABLE, 'TABLE: a slot holds no id of this map'),
+                  (_lib.TG_IDMAP_ERR_FREE, 'FREE: the bitmap of free ids and key_of disagree'))
 
 
 def IDMAP_ERR_TEXT(word: int) -> str:
@@ -968,4 +969,81 @@ def idmap_rebuild(tables, size: int, read_back: bool = True):
     else:
         with torch.cuda.device(dev):
             check(lib.tg_idmap_rebuild(C_.byref(m), size, ptr(out2), stream_ptr(dev)), 'tg_idmap_rebuild')
+    return int(out2[1].item()) if read_back else out2
+
+
+# ---- removing keys and recycling dense ids (tg_idmap_remove / _assign_recycle / _rebuild_free and their host twins) --------
+def idmap_free_bits(key_rows: int, device) -> Tensor:
+    """the bitmap of free ids over key_rows dense ids, none free: 64-bit words (held as int64)"""
+    return torch.zeros((int(key_rows) + 63) // 64, dtype=torch.int64, device=device)
+
+
+def _idmap_bits(what: str, free_bits: Tensor, dev) -> Tensor:
+    if not (torch.is_tensor(free_bits) and free_bits.dtype == torch.int64 and free_bits.dim() == 1
+            and free_bits.is_contiguous() and free_bits.device == dev):
+        raise ValueError(f'{what}: free_bits must be a contiguous 1-d int64 tensor on {dev}')
+    return free_bits
+
+
+def idmap_remove(tables, size: int, free_bits: Tensor, keys: Tensor) -> Tuple[Tensor, Tensor, int, int]:
+    """tiger_hip.h: tg_idmap_remove (tables on the CPU: its host twin) -> (ids int32 [n]: the id each key had, -1 for a key
+    the map does not hold, 0 for INT64_MIN; released int32 [n]: each released id at one position, INT32_MAX elsewhere; the
+    number of distinct ids released; error bits).  Tables and bitmap are updated in place; ONE read-back."""
+    m, dev = _idmap_struct('idmap_remove', tables, keys)
+    _idmap_bits('idmap_remove', free_bits, dev)
+    n = keys.numel()
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    released = torch.empty(n, dtype=torch.int32, device=dev)
+    out2 = torch.empty(2, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        check(lib.tg_idmap_remove_host(C_.byref(m), size, ptr(free_bits), free_bits.numel(), ptr(keys), n, ptr(ids),
+                                       ptr(released), ptr(out2)), 'tg_idmap_remove_host')
+    else:
+        with torch.cuda.device(dev):
+            nbytes = int(lib.tg_idmap_remove_workspace_bytes(n))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            check(lib.tg_idmap_remove(C_.byref(m), size, ptr(free_bits), free_bits.numel(), ptr(keys), n, ptr(ids),
+                                      ptr(released), ptr(out2), ptr(ws), nbytes, stream_ptr(dev)), 'tg_idmap_remove')
+    n_released, err = out2.tolist()
+    return ids, released, int(n_released), int(err)
+
+
+def idmap_assign_recycle(tables, size: int, occupied: int, free_bits: Tensor, n_free: int,
+                         keys: Tensor) -> Tuple[Tensor, Tensor, int, int]:
+    """tiger_hip.h: tg_idmap_assign_recycle (tables on the CPU: its host twin) -> (ids int32 [n], free_list int32
+    [min(n_free, n)]: the smallest free ids before the call, ascending; n_new: the new keys of the batch; error bits).
+    Tables and bitmap are updated in place; ONE read-back, of the two result words."""
+    m, dev = _idmap_struct('idmap_assign_recycle', tables, keys)
+    _idmap_bits('idmap_assign_recycle', free_bits, dev)
+    n = keys.numel()
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    free_list = torch.empty(max(min(int(n_free), n), 0), dtype=torch.int32, device=dev)
+    out2 = torch.empty(2, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        check(lib.tg_idmap_assign_recycle_host(C_.byref(m), size, occupied, ptr(free_bits), free_bits.numel(), n_free, ptr(keys),
+                                               n, ptr(ids), ptr(free_list), ptr(out2)), 'tg_idmap_assign_recycle_host')
+    else:
+        with torch.cuda.device(dev):
+            nbytes = int(lib.tg_idmap_assign_recycle_workspace_bytes(n, size))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            check(lib.tg_idmap_assign_recycle(C_.byref(m), size, occupied, ptr(free_bits), free_bits.numel(), n_free, ptr(keys),
+                                              n, ptr(ids), ptr(free_list), ptr(out2), ptr(ws), nbytes, stream_ptr(dev)),
+                  'tg_idmap_assign_recycle')
+    end, err = out2.tolist()
+    return ids, free_list, int(end) - int(size), int(err)
+
+
+def idmap_rebuild_free(tables, size: int, live: int, free_bits: Tensor, read_back: bool = True):
+    """tiger_hip.h: tg_idmap_rebuild_free (tables on the CPU: its host twin): idmap_rebuild for a key_of with holes; live =
+    the rows that hold a key, the padding row included -> the error word, or with read_back=False the device words unread."""
+    m, dev = _idmap_struct('idmap_rebuild_free', tables)
+    _idmap_bits('idmap_rebuild_free', free_bits, dev)
+    out2 = torch.empty(2, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        check(lib.tg_idmap_rebuild_free_host(C_.byref(m), size, live, ptr(free_bits), free_bits.numel(), ptr(out2)),
+              'tg_idmap_rebuild_free_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_idmap_rebuild_free(C_.byref(m), size, live, ptr(free_bits), free_bits.numel(), ptr(out2),
+                                            stream_ptr(dev)), 'tg_idmap_rebuild_free')
     return int(out2[1].item()) if read_back else out2

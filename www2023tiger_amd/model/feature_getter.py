@@ -100,6 +100,39 @@ class NumericalFeature(nn.Module):
         self._version_ = getattr(self, '_version_', 0) + 1
         return moved
 
+    def set_node_rows(self, ids, rows, check: bool = True):
+        """Overwrite rows of the node table (a dense id that is handed out again, TIGE.erase_keys / observe_keys): ids [k]
+        int32 / int64, DISTINCT; `rows` [k, d_n], or the int 0 for zero rows.  The table's address does not move.  A model
+        that derives tables from the node table (eager updates, query rows) is told by TIGE.set_node_rows.  Refused, with
+        nothing changed: what `append_node_rows` refuses (no node table, a table in pinned host memory:
+        NotImplementedError; rows of another shape: ValueError), ids that are no 1-d integer tensor, an int other than 0,
+        an id outside [0, n_nodes) (ValueError; one read-back, check=False for ids the caller made itself)."""
+        if self.nfeats is None:
+            raise NotImplementedError('set_node_rows: the feature getter has no node table (n_nodes is its row count)')
+        if not self.pin_mem:
+            raise NotImplementedError('set_node_rows: the node table lives in pinned host memory (register_buffer=False)')
+        cur = self.nfeats
+        ids = torch.as_tensor(ids)
+        if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1:
+            raise ValueError('set_node_rows: ids must be a 1-d int32 or int64 tensor')
+        k = ids.numel()
+        if isinstance(rows, int):
+            if rows != 0:
+                raise ValueError(f'set_node_rows: rows = {rows} (a tensor of rows, or 0 for zero rows)')
+            rows = None
+        else:
+            rows = torch.as_tensor(rows)
+            if rows.dim() != 2 or rows.shape[0] != k or rows.shape[1] != cur.shape[1]:
+                raise ValueError(f'set_node_rows: rows {tuple(rows.shape)} for {k} ids of a node table of width {cur.shape[1]}')
+        ids = ids.to(cur.device).long()
+        if check and k and bool(((ids < 0) | (ids >= cur.shape[0])).any()):
+            raise ValueError(f'set_node_rows: an id outside [0, {cur.shape[0]})')
+        if k and rows is None:
+            cur.index_fill_(0, ids, 0)
+        elif k:
+            cur.index_copy_(0, ids, rows.to(cur.device, cur.dtype))
+        self._version_ = getattr(self, '_version_', 0) + 1
+
     def append_edge_rows(self, rows) -> bool:
         """Append rows [n, d_e] to the edge table (online ingestion, TIGE.observe) -> whether the table's data pointer moved
         (the caller then drops whatever caches it: TIGE.invalidate_struct).  The table is a leading view of a backing

@@ -1782,6 +1782,12 @@ class TIGE(nn.Module):
         `IdMap.from_keys` without being renumbered.  One read-back (the new size) on top of observe's.
         observe_kwargs: those of observe but num_node.  nfeats may be a CALLABLE: it is handed the keys (int64, device) of
         the ids the model is about to admit, [n_nodes, idmap.size), and returns their feature rows.
+        A map that holds FREE ids (after `erase_keys`) hands them out first: the ids to admit are then the recycled ids
+        below n_nodes given out by this call, in assignment order, followed by [n_nodes, idmap.size); nfeats holds one row
+        for each of them in that order (a callable is handed their keys).  The model grows with zero rows to idmap.size and
+        the rows are written in place (`set_node_rows`) BEFORE observe: if observe then refuses the batch, the keys stay
+        assigned, as without free ids, and so do their feature rows and the zero rows the growth added; what memories,
+        mailbox and graph held is untouched.
         Refused before a key is assigned: a partitioned model, training mode, a captured stream, a map on another
         device, keys that are no int64, and - with a static restarter - a batch that holds a key the map does not.
         Whatever else observe / grow_nodes refuse (a batch that goes back in time, an eid that is no row, feature rows of
@@ -1795,13 +1801,79 @@ class TIGE(nn.Module):
             raise ValueError('observe_keys: src_keys and dst_keys must have one entry per event')
         keys = torch.stack([src_keys, dst_keys], 1).reshape(-1)  # event order
         self._keyed_refusals('observe_keys', idmap, keys)
-        ids = idmap.assign(keys).view(-1, 2).long()
-        num_node = max(idmap.size, self.n_nodes)
         nfeats = observe_kwargs.pop('nfeats', None)
-        if callable(nfeats):
-            nfeats = nfeats(idmap.key_of[self.n_nodes:num_node])
+        if idmap.n_free == 0:
+            ids = idmap.assign(keys).view(-1, 2).long()
+            num_node = max(idmap.size, self.n_nodes)
+            if callable(nfeats):
+                nfeats = nfeats(idmap.key_of[self.n_nodes:num_node])
+        else:
+            ids, num_node = self._admit_recycled('observe_keys', idmap, keys, nfeats)
+            ids, nfeats = ids.view(-1, 2).long(), None
         return self.observe(ids[:, 0].contiguous(), ids[:, 1].contiguous(), torch.as_tensor(ts).to(self.device),
                             torch.as_tensor(eids).to(self.device), num_node=num_node, nfeats=nfeats, **observe_kwargs)
+
+    def _admit_recycled(self, what: str, idmap, keys: Tensor, nfeats):
+        """assign `keys` on a map that holds free ids and admit what the call gave out -> (ids int32 [n], num_node): the
+        recycled ids below n_nodes in assignment order, then [n_nodes, idmap.size).  nfeats (a tensor, a callable handed
+        the keys of those ids, or None for zero rows) is checked first; then the model grows with zero rows and the rows
+        are written in place (set_node_rows) - a recycled id's row is overwritten, not appended."""
+        n0 = self.n_nodes
+        ids, new_ids = idmap.assign(keys, return_new=True)
+        num_node = max(idmap.size, n0)
+        admit = torch.cat([new_ids[new_ids < n0].long(), torch.arange(n0, num_node, device=self.device)])
+        if callable(nfeats):
+            nfeats = nfeats(idmap.key_of[admit])
+        if nfeats is not None:
+            nfeats = torch.as_tensor(nfeats)
+            if nfeats.dim() != 2 or nfeats.shape[0] != admit.numel() or nfeats.shape[1] != self.nfeat_dim:
+                raise ValueError(f'{what}: nfeats {tuple(nfeats.shape)} for {admit.numel()} admitted node ids of width '
+                                 f'{self.nfeat_dim}')
+        if num_node > n0:
+            self.grow_nodes(num_node)
+        if admit.numel() and self.raw_feat_getter.nfeats is not None:
+            self.set_node_rows(admit, 0 if nfeats is None else nfeats, check=False)
+        return ids, num_node
+
+    def set_node_rows(self, ids, rows, check: bool = True):
+        """`NumericalFeature.set_node_rows(ids, rows)` on the model's node table, and the tables derived from it (eager
+        updates, centre / query rows) are rebuilt before their next use.  Its refusals."""
+        self.raw_feat_getter.set_node_rows(ids, rows, check=check)
+        self._touch()
+
+    def erase_keys(self, idmap, keys, *, eids=None, release_edge_rows: bool = False, keep_from=None):
+        """`erase` behind external keys, and the keys LEAVE the map (a closed account) -> (graph,
+        removed_ids): the new graph and the dense ids the map released, int32, ascending.  In this order:
+          1. the keys are looked up; a key the map does not hold is ignored, and so is INT64_MIN;
+          2. `erase(nodes = the ids the model has admitted, eids=eids, release_edge_rows=, keep_from=)` - it validates
+             everything, and nothing has changed if it raises;
+          3. the node-feature rows of the erased ids are zeroed (`set_node_rows(ids, 0)`): with step 2 every per-node row
+             is that of a freshly built model;
+          4. `idmap.remove(keys)`: the ids are free and are handed out again, the smallest first, by the next
+             `observe_keys` / `recommend_keys(admit=True)` - n_nodes stays at the peak of live keys (+ the free ones).
+        A key that was assigned but not yet admitted (its id is >= n_nodes: the batch that brought it was refused) is only
+        removed from the map.  A key that comes back later is a new key: a node never seen, possibly under another id.
+        `erase`'s LIMITS carry over unchanged: partners' memories and pending mail keep what the node contributed, and a
+        recycled id inherits nothing but that - no row of its own.  THE CALLER'S DUTIES are those of `erase`, and for
+        `uptodate` bitmaps held from lazy restarts: clear the bits of removed_ids (a recycled id is a node never seen).
+        Refused before anything changes: what `_keyed_refusals` refuses (a partitioned model, training mode, a map on
+        another device, a captured stream, a static restarter with unknown keys), keys that are no int64, a node table in
+        pinned host memory, and what `erase` refuses."""
+        keys = self._device_keys('erase_keys', 'keys', keys).reshape(-1)
+        self._keyed_refusals('erase_keys', idmap, keys)
+        fg = self.raw_feat_getter
+        if fg.nfeats is not None and not fg.pin_mem:
+            raise NotImplementedError('erase_keys: the node table lives in pinned host memory (register_buffer=False)')
+        ids = idmap.lookup(keys).long()
+        nodes = ids[(ids > 0) & (ids < self.n_nodes)]
+        graph = self.graph
+        if nodes.numel() or eids is not None:
+            graph = self.erase(nodes=nodes if nodes.numel() else None, eids=eids, release_edge_rows=release_edge_rows,
+                               keep_from=keep_from)
+        if nodes.numel() and fg.nfeats is not None:
+            self.set_node_rows(nodes, 0, check=False)   # (a fill: duplicates are fine)
+        _, removed = idmap.remove(keys)
+        return graph, removed
 
     def recommend_keys(self, idmap, src_keys, ts, cand, k: int, *, cand_keys=None, admit: bool = False, **recommend_kwargs):
         """`recommend` behind external keys -> (keys int64 [B, k], scores float32 [B, k], n_valid int32 [B]); keys =
@@ -1823,9 +1895,12 @@ class TIGE(nn.Module):
             cand_keys = self._device_keys('recommend_keys', 'cand_keys', cand_keys)
         if admit:
             self._keyed_refusals('recommend_keys', idmap, src_keys)
-            ids = idmap.assign(src_keys)
-            if idmap.size > self.n_nodes:
-                self.grow_nodes(idmap.size)
+            if idmap.n_free == 0:
+                ids = idmap.assign(src_keys)
+                if idmap.size > self.n_nodes:
+                    self.grow_nodes(idmap.size)
+            else:  # (ids that were released are handed out first: their rows are those of a node never seen)
+                ids, _ = self._admit_recycled('recommend_keys', idmap, src_keys, None)
         else:
             ids = idmap.lookup(src_keys)
             unknown = int(((ids < 0) | (ids >= self.n_nodes)).sum())

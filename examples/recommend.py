@@ -44,7 +44,9 @@ printed per batch.  The lists are keys (ids.npy holds int64 keys); without --gro
 replay's, exactly, and `run_online` asserts it.  With --save_state / --load_state the map's state travels in the same file.
 --churn FILE (with --keyed) names, per batch, the keys that leave behind it: their nodes are erased and their keys removed
 (`TIGE.erase_keys`), the released dense ids go to the keys later batches bring, and released / recycled / n_nodes are
-printed per batch - the model stays as large as its peak of live keys.
+printed per batch - the model stays as large as its peak of live keys.  --compact_at F (with --churn) goes further: when
+the share of free ids passes F behind an erase, `TIGE.compact_keys` renumbers the live keys densely and shrinks the map and
+every per-node table to them; rows before -> after are printed.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -238,7 +240,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
                erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False,
-               churn=None):
+               churn=None, compact_at=None):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -271,10 +273,19 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     (`erase_keys`: their nodes are erased, their keys removed from the map, their dense ids handed out again to the keys
     the next batches bring).  The replay prints, and its metrics carry per batch, 'released' (ids the map released) and
     'recycled' (released ids handed out again), and 'n_nodes' at the end: with accounts that come and go the model stays
-    as large as its peak of live keys.  No offline replay is made."""
+    as large as its peak of live keys.  No offline replay is made.
+    compact_at (a fraction F; with churn only): behind an erase, when n_free / size of the map passes F, the free ids are
+    taken OUT of the id space (`compact_keys`): the live keys are renumbered densely and the map, both memories, the mailbox,
+    the node table and the graph shrink to them.  The replay prints rows before -> after and its metrics carry 'compacted':
+    (batch, n_nodes before, n_nodes after).  This replay holds keys, never dense ids, between batches and no `uptodate`
+    bitmap; a caller that holds either passes them through the returned plan (`plan.translate`, `plan.bitmap`)."""
     from www2023tiger_amd.data.graph import Graph
     if churn is not None and not keyed:
         raise ValueError('churn names the nodes that leave by their keys: it needs --keyed')
+    if compact_at is not None and churn is None:
+        raise ValueError('compact_at compacts behind the erases of a churn file: it needs --churn')
+    if compact_at is not None and not 0 <= float(compact_at) < 1:
+        raise ValueError(f'compact_at = {compact_at} is a fraction of the map\'s ids in [0, 1)')
     leaving = {}
     if churn is not None:
         offline = False
@@ -357,7 +368,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         rows = []
 
         admitted = []
-        released, recycled = [], []
+        released, recycled, compacted = [], [], []
         cache = {}
 
         def known():   # the items the model knows now (and their index), rebuilt when ids were admitted
@@ -381,6 +392,13 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                     keyed._n = None   # (the catalogue's keys are looked up again: items may have left or come back)
                     if verbose:
                         print(f'batch {b}: {released[-1]} ids released, {recycled[-1]} recycled, n_nodes {model.n_nodes}')
+                    m = keyed.idmap
+                    if compact_at is not None and m.n_free and m.n_free / m.size > float(compact_at):
+                        rows_before, slots = model.n_nodes, m.capacity
+                        model.compact_keys(m)
+                        compacted.append((b, rows_before, int(model.n_nodes)))
+                        if verbose:
+                            print(f'batch {b}: compacted: {rows_before} rows -> {model.n_nodes}, map {slots} slots -> {m.capacity}')
                 return
             if not grow:
                 return model.observe(s, d, t, e)
@@ -431,6 +449,8 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         online = dict(online, n_nodes=int(model.n_nodes))
     if churn is not None:
         online = dict(online, released=released, recycled=recycled)
+    if compact_at is not None:
+        online = dict(online, compacted=compacted)
     if erasing:
         online = dict(online, erased=erased)
     if forgetting:
@@ -521,6 +541,10 @@ if __name__ == '__main__':
                     'of train + validation (TIGE.load_online) and replay the rest of the split')
     ap.add_argument('--keyed', action='store_true', help='--online: every node id becomes an external 64-bit key; the model '
                     'sits behind a device id map (observe_keys / recommend_keys) and ids.npy holds keys')
+    ap.add_argument('--compact_at', type=float, default=None, metavar='F', help='--online --keyed --churn FILE: behind an erase, '
+                    'when n_free / size of the id map passes F, the free ids are taken out of the id space '
+                    '(TIGE.compact_keys): map, memories, mailbox, node table and graph shrink to the live keys; rows before '
+                    '-> after are printed')
     ap.add_argument('--churn', default=None, metavar='FILE', help='--online --keyed: a text file of lines "batch key" - the '
                     'keys that leave behind that batch (TIGE.erase_keys); their dense ids are handed out again, and the ids '
                     'released and recycled and n_nodes are printed per batch')
@@ -547,7 +571,7 @@ if __name__ == '__main__':
                                                               retract_eids=None if a.retract_eids is None
                                                               else np.load(a.retract_eids), save_state=a.save_state,
                                                               save_after=a.save_after, load_state=a.load_state,
-                                                              keyed=a.keyed, churn=a.churn)):
+                                                              keyed=a.keyed, churn=a.churn, compact_at=a.compact_at)):
             if m is None:
                 continue
             if a.keyed and 'ids' in m:

@@ -366,6 +366,63 @@ int tg_edge_rows_host(const tg_tcsr* g, const float* table, int64_t n_rows, int3
                       const int64_t* pin, int64_t n_pin, int32_t* remap, float* table_out, int32_t* eid_out,
                       int64_t* n_live_out);
 
+/* Compacting the node id space (tg_node_compact.hip; online serving after erasures - DESIGN 7.20.  The reference numbers
+ * its nodes offline and never releases an id: no counterpart).  Entries added beside the ones above, which stay as they are.
+ * drop_bits [bit_words >= ceil(N / 64)]: 64-bit words over the ids [0, N), a set bit = the id leaves - the layout of
+ * free_bits above, so an id map's bitmap goes in as it is.  g->num_node <= N <= 2^31 - 1: ids at and beyond g->num_node
+ * own no row of the graph (keys that were assigned and never admitted) and are kept or dropped like any other.
+ * tg_node_compact_plan writes
+ *   remap      [N] int32: the number of kept ids below i if i is kept, else -1 (monotone: kept ids keep their order);
+ *   old_of     [room for N; n_new written] int32: the inverse list, ascending;
+ *   indptr_out [room for g->num_node + 1; n_new_graph + 1 written]: the bounds of the kept rows;
+ *   nbr_out    [g->num_entry] = remap[nbr[p]];  ts and eid do not move: the child shares them with its parent;
+ *   out4       (DEVICE, int64 [4]) = {n_new, n_new_graph = kept ids below g->num_node, error class, smallest offender}: the
+ *              one read-back of a call.
+ * Error classes (0: clean), reported in this order, each with its SMALLEST offender whatever the launch geometry:
+ *   TG_NODE_COMPACT_ID0   bit 0 is set (the padding id never leaves); offender 0
+ *   TG_NODE_COMPACT_SPARE a set bit at or beyond N in word ceil(N / 64) - 1; offender = that id
+ *   TG_NODE_COMPACT_ROW   a dropped id i < g->num_node with indptr[i + 1] != indptr[i]; offender = i
+ *   TG_NODE_COMPACT_NBR   an entry whose neighbour is dropped (or is no id of the graph); offender = the entry
+ * On an error the other outputs are not to be used.  A loaded nbr value is range-checked before it indexes remap.
+ * A memset of 32 bytes and four launches (tiles of 2048 words = 131 072 ids; 2048 entries); no kernel waits for another
+ * workgroup.  ws: tg_node_compact_workspace_bytes(N) bytes (0 for N outside [1, 2^31)), 16-byte aligned; a short one
+ * returns TG_EWORKSPACE before any launch.  TG_EINVAL: what tcsr_args refuses for g, N < g->num_node, a missing array.
+ *
+ * tg_node_rows_compact: ONE launch that compacts up to TG_NODE_ROWS_MAX per-node tables by old_of: for table t and
+ * j < n_rows_out, dst[j] = src[old_of[j]] (row_bytes bytes).  n_rows_out <= n_new may differ per table (the remap is
+ * monotone: the kept rows of a table of fewer rows are a prefix of old_of); n_rows_src = the rows of src, which an old_of
+ * value is checked against before it is read.  row_bytes: a multiple of 16 (16-byte loads and stores, contiguous per
+ * output tile; src and dst 16-byte aligned) or 8, 4 or 1.  src and dst must not overlap.  TG_EINVAL before the launch:
+ * n_tab outside [0, 8], another row width, row_bytes > 2^20, n_rows_out > n_new, a missing or misaligned pointer, overlap.
+ *
+ * tg_bitmap_compact: out bit j = in bit old_of[j] for j < n_out; `in` covers n_in ids; out has ceil(n_out / 64) words and
+ * the spare bits of its last word are zero.  One lane per output bit, the wavefront's ballot is the output word.
+ * The _host twins: HOST pointers (those of `g` and the descriptors included), plain C++, the same results bit for bit. */
+#define TG_NODE_COMPACT_ID0 1
+#define TG_NODE_COMPACT_SPARE 2
+#define TG_NODE_COMPACT_ROW 3
+#define TG_NODE_COMPACT_NBR 4
+#define TG_NODE_ROWS_MAX 8
+typedef struct tg_node_rows {
+  const void* src;
+  void* dst;
+  int64_t row_bytes;
+  int64_t n_rows_out; /* rows of dst that are written */
+  int64_t n_rows_src; /* rows of src */
+} tg_node_rows;
+size_t tg_node_compact_workspace_bytes(int64_t N);
+int tg_node_compact_plan(const tg_tcsr* g, const uint64_t* drop_bits, int64_t bit_words, int64_t N, int32_t* remap,
+                         int32_t* old_of, int64_t* indptr_out, int32_t* nbr_out, int64_t* out4, void* ws, size_t ws_bytes,
+                         void* stream);
+int tg_node_rows_compact(const tg_node_rows* tabs, int32_t n_tab, const int32_t* old_of, int64_t n_new, void* stream);
+int tg_bitmap_compact(const uint64_t* in, int64_t n_in, const int32_t* old_of, int64_t n_out, uint64_t* out, void* stream);
+int tg_node_compact_plan_host(const tg_tcsr* g, const uint64_t* drop_bits_host, int64_t bit_words, int64_t N,
+                              int32_t* remap_host, int32_t* old_of_host, int64_t* indptr_out_host, int32_t* nbr_out_host,
+                              int64_t* out4_host);
+int tg_node_rows_compact_host(const tg_node_rows* tabs, int32_t n_tab, const int32_t* old_of_host, int64_t n_new);
+int tg_bitmap_compact_host(const uint64_t* in_host, int64_t n_in, const int32_t* old_of_host, int64_t n_out,
+                           uint64_t* out_host);
+
 /* Graph.sample_temporal_neighbor(strategy='recent_edges') and Graph.get_history
  * (graph.py:67-127,150-155): per query the last K entries with ts < t (strict),
  * left padded with zeros.  out_dir may be NULL.  If mark_flags != NULL every query

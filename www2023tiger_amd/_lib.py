@@ -53,6 +53,15 @@ TG_IDMAP_EMPTY = -(1 << 63)
 TG_IDMAP_ERR_PROBE, TG_IDMAP_ERR_DUP, TG_IDMAP_ERR_EMPTY_KEY, TG_IDMAP_ERR_TABLE, TG_IDMAP_ERR_FREE = 1, 2, 4, 8, 16
 
 
+class TgNodeRows(C.Structure):
+    """tiger_hip.h: tg_node_rows - one per-node table of tg_node_rows_compact"""
+    _fields_ = [('src', vp), ('dst', vp), ('row_bytes', i64), ('n_rows_out', i64), ('n_rows_src', i64)]
+
+
+TG_NODE_COMPACT_ID0, TG_NODE_COMPACT_SPARE, TG_NODE_COMPACT_ROW, TG_NODE_COMPACT_NBR = 1, 2, 3, 4
+TG_NODE_ROWS_MAX = 8
+
+
 class TgAdvIndex(C.Structure):
     """tiger_hip.h: tg_adv_index - the pair index of historical / inductive negative sampling"""
     _fields_ = [('next_ts', vp), ('first_ts', vp)]
@@ -230,6 +239,13 @@ SIGNATURES = {
     'tg_edge_rows_plan': (C.c_int, [P(TgTcsr), i64, i64, vp, i64, vp, vp, vp, sz, vp]),
     'tg_edge_rows_apply': (C.c_int, [P(TgTcsr), vp, i64, i32, vp, i64, vp, vp, vp, sz, vp]),
     'tg_edge_rows_host': (C.c_int, [P(TgTcsr), vp, i64, i32, i64, vp, i64, vp, vp, vp, vp]),
+    'tg_node_compact_workspace_bytes': (sz, [i64]),
+    'tg_node_compact_plan': (C.c_int, [P(TgTcsr), vp, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_node_rows_compact': (C.c_int, [P(TgNodeRows), i32, vp, i64, vp]),
+    'tg_bitmap_compact': (C.c_int, [vp, i64, vp, i64, vp, vp]),
+    'tg_node_compact_plan_host': (C.c_int, [P(TgTcsr), vp, i64, i64, vp, vp, vp, vp, vp]),
+    'tg_node_rows_compact_host': (C.c_int, [P(TgNodeRows), i32, vp, i64]),
+    'tg_bitmap_compact_host': (C.c_int, [vp, i64, vp, i64, vp]),
     'tg_sample_recent_edges': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     'tg_sample_recent_nodes': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp]),
     'tg_sample_uniform': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),

@@ -10,7 +10,8 @@ thread may sample concurrently (each call allocates its own outputs and runs on
 the calling thread's current stream).  New events are ingested by `extended`, which
 returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was; old entries
 are dropped by `trimmed` (csrc/tg_trim.hip), which does the same, `without` takes particular nodes and events out
-(csrc/tg_erase.hip), and `renumbered` gives the entries the row numbers of a packed edge table (csrc/tg_edge_rows.hip).
+(csrc/tg_erase.hip), `renumbered` gives the entries the row numbers of a packed edge table (csrc/tg_edge_rows.hip), and
+`compacted` renumbers the node ids densely without the erased ones (csrc/tg_node_compact.hip).
 """
 import ctypes as C
 import itertools
@@ -636,6 +637,41 @@ class Graph:
                 if new is not None and (len(new) == 0 or new.min() >= 0):  # (every event's row survived: still an event list)
                     events = (ev[0], ev[1], ev[2], new)
             return child._adopt_host((h[0], h[1], h[2], e), events, self)
+
+    # ---- compacted node ids ------------------------------------------------------------
+    def compacted(self, plan) -> 'Graph':
+        """A NEW Graph over the densely renumbered node ids of `plan` (tg_node_compact_*: hip_ops.node_compact_plan /
+        node_compact_host OVER THIS GRAPH; graph.py:11-42 has no counterpart: the reference never releases a node id).  A
+        dropped id owns no entry and is nobody's neighbour (the plan refuses anything else), so no entry moves: the child
+        SHARES ts and eid with this graph (the same tensors / arrays) and owns plan.indptr - the bounds of the kept rows -
+        and plan.nbr = remap[nbr]; num_node = plan.n_graph_new.  This graph stays valid and unchanged.  The result equals,
+        bit for bit, `from_arrays` over this graph's events with src / dst passed through plan.remap
+        (max_node_id = num_node - 1).  strategy / seed / alpha / device, `rng` and device MT19937 state, the latest event
+        time and the time-ordered flag carry over; the child has a `serial` and a host origin of its own.  A
+        device-resident parent takes a device plan, a host-only parent a plan of the host twin; the event list is pushed
+        through remap on the host path and dropped on the device path (`_events` None).  ValueError: a plan with an error
+        class, of another graph size, or on the other side (device / host)."""
+        if plan.code:
+            from ..hip_ops import NODE_COMPACT_TEXT
+            raise ValueError('compacted: ' + NODE_COMPACT_TEXT(plan.code, plan.first, plan.n_old))
+        if plan.indptr is None or plan.n_graph_old != self.num_node:
+            raise ValueError(f'compacted: the plan covers a graph of {plan.n_graph_old if plan.indptr is not None else 0} '
+                             f'nodes, this graph has {self.num_node}')
+        child = self._child(plan.n_graph_new)
+        if self._dev is not None:
+            d = self._dev
+            if not torch.is_tensor(plan.nbr) or plan.nbr.device != d[2].device or plan.nbr.numel() != d[2].numel():
+                raise ValueError(f'compacted: a device-resident graph takes a plan of node_compact_plan over its '
+                                 f'{d[2].numel()} entries on {d[2].device}')
+            return child._adopt_device((plan.indptr, d[1], plan.nbr, d[3]), self)
+        h = self._host_tcsr()
+        if not isinstance(plan.nbr, np.ndarray) or plan.nbr.shape != h[2].shape:
+            raise ValueError(f'compacted: a host graph takes a plan of node_compact_host over its {len(h[2])} entries')
+        ev = self._root.events
+        if ev is not None:
+            r = plan.remap.numpy().astype(np.int64)
+            ev = (r[ev[0]], r[ev[1]], ev[2], ev[3])
+        return child._adopt_host((plan.indptr, h[1], plan.nbr, h[3]), ev, self)
 
     # ---- sampling -------------------------------------------------------------------
     def sample_device(self, nids: Tensor, ts: Tensor, n_neighbors: int, strategy: Optional[str] = None,

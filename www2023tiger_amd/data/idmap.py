@@ -39,7 +39,7 @@ class IdMap:
     and one for the padding id included: a removed slot keeps its key so that probe chains stay intact, and the table is
     rebuilt from key_of - purged of those slots, possibly at the SAME capacity - when slots_used + n would pass half of it.
     device 'cpu' runs the library's host twins over the same layout (tests, tools); there is no other fallback.
-    Not built: shrinking the tables (capacity, key_of and the model's rows stay at their high-water mark), keys for eids."""
+    `compact` takes the free ids out and shrinks the tables to the live keys.  Not built: keys for eids."""
 
     def __init__(self, device, capacity: int = 1024, reserve: Optional[int] = None):
         self.device = torch.device(device)
@@ -155,6 +155,41 @@ class IdMap:
             raise RuntimeError('IdMap.remove: ' + hip_ops.IDMAP_ERR_TEXT(err))
         self.n_free += n_released
         return ids, released.sort().values[:n_released]   # (INT32_MAX at the positions that released nothing)
+
+    def compact(self, plan=None):
+        """Take the free ids out: the live ids are renumbered densely in their order -> the NodeCompaction
+        (plan.translate gives the new id of an old one, -1 for a free one).  plan: a plan over THIS map's ids with drop_bits
+        = free_bits (TIGE.compact_keys passes the one it made for the model: one plan serves both sides); None: made here
+        (hip_ops.node_compact_plan over `size` ids without a graph; its host twin on the CPU).  key_of is gathered by
+        plan.old_of and the table rebuilt by tg_idmap_rebuild at _capacity_for(n_new) slots, so capacity SHRINKS; afterwards
+        size = slots_used = n_new, n_free = 0 and the bitmap is clear: the map saves the version-1 'tiger-idmap' dict
+        again and `assign` hands out size, size + 1, ...  Nothing free: the identity plan, nothing changes.  Everything is
+        built first and swapped in one step: if the call raises, the map has not changed.  ValueError: a plan over fewer
+        ids than `size`, or one that keeps another number of ids than the map has live."""
+        if plan is None:
+            make = hip_ops.node_compact_host if self.device.type == 'cpu' else hip_ops.node_compact_plan
+            plan = make(None, self.free_bits, self.size)
+        self._compact_adopt(self._compact_build(plan))
+        return plan
+
+    def _compact_build(self, plan):
+        """the new tables of `compact`, or None when nothing is free; the map has not changed"""
+        live = self.size - self.n_free
+        if plan.n_old < self.size or plan.rows_below(self.size) != live or plan.device != self.device:
+            raise ValueError(f'IdMap.compact: the plan covers {plan.n_old} ids on {plan.device}, the map has {self.size} '
+                             f'({live} live) on {self.device}')
+        if self.n_free == 0:
+            return None
+        rows = max(live, 16)
+        slot_key, slot_id, key_of = hip_ops.idmap_tables(_capacity_for(live), rows, self.device)
+        hip_ops.node_rows_compact([(self.key_of, key_of[:live])], plan.old_of)
+        hip_ops.idmap_rebuild((slot_key, slot_id, key_of), live, read_back=False)   # (live keys are distinct: nothing to read)
+        return slot_key, slot_id, key_of, hip_ops.idmap_free_bits(rows, self.device), live
+
+    def _compact_adopt(self, built):
+        if built is not None:
+            self.slot_key, self.slot_id, self.key_of, self.free_bits, live = built
+            self.size, self.n_free, self.slots_used = live, 0, live
 
     def is_free(self, ids: Tensor) -> Tensor:
         """-> bool, of the shape of ids: the id was released and not handed out again (a gather of the bitmap).  ValueError:

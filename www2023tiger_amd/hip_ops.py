@@ -1047,3 +1047,217 @@ def idmap_rebuild_free(tables, size: int, live: int, free_bits: Tensor, read_bac
             check(lib.tg_idmap_rebuild_free(C_.byref(m), size, live, ptr(free_bits), free_bits.numel(), ptr(out2),
                                             stream_ptr(dev)), 'tg_idmap_rebuild_free')
     return int(out2[1].item()) if read_back else out2
+
+
+# ---- compacting the node id space (tg_node_compact_plan / tg_node_rows_compact / tg_bitmap_compact and their host twins) ---
+NODE_COMPACT_CLASSES = ('ID0', 'SPARE', 'ROW', 'NBR')
+_NODE_COMPACT_WHAT = ('node id 0 is the padding id and never leaves',
+                      'bit {i} is set, at or beyond the {n} ids the bitmap covers',
+                      'node {i} is dropped but still owns entries of the graph: erase it first',
+                      'entry {i} of the graph names a dropped node as its neighbour: erase that node first')
+
+
+def NODE_COMPACT_TEXT(cls: int, first=None, n_ids=None) -> str:
+    """The message of a non-zero error class of node_compact_plan: the class by name and its smallest offender."""
+    cls = int(cls)
+    if not 1 <= cls <= len(NODE_COMPACT_CLASSES):
+        return 'a clean compaction plan' if cls == 0 else f'unknown error class {cls}'
+    what = _NODE_COMPACT_WHAT[cls - 1].format(i='?' if first is None else int(first), n='?' if n_ids is None else int(n_ids))
+    return f'{NODE_COMPACT_CLASSES[cls - 1]}: {what}'
+
+
+class NodeCompaction:
+    """What a compaction of the node id space did: remap int32 [n_old] - the new id of an old one, -1 for a
+    dropped id; monotone, so kept ids keep their order and remap[0] == 0 -, old_of int32 [n_new], its inverse list, ascending.
+    n_graph_old / n_graph_new: the ids the planned graph covered before and after (ids beyond it - keys assigned and never
+    admitted - own no row anywhere).  indptr / nbr: the arrays `Graph.compacted` adopts (None for a plan without a graph).
+    Tensors on the plan's device; a plan of the host twin holds CPU tensors (indptr / nbr numpy arrays)."""
+
+    def __init__(self, remap, old_of, n_old, n_new, n_graph_old=1, n_graph_new=1, indptr=None, nbr=None, code=0, first=-1):
+        self.remap, self.old_of = remap, old_of
+        self.n_old, self.n_new = int(n_old), int(n_new)
+        self.n_graph_old, self.n_graph_new = int(n_graph_old), int(n_graph_new)
+        self.indptr, self.nbr = indptr, nbr
+        self.code, self.first = int(code), int(first)
+
+    @property
+    def device(self):
+        return self.remap.device
+
+    @property
+    def identity(self) -> bool:
+        return self.n_new == self.n_old
+
+    def translate(self, ids: Tensor) -> Tensor:
+        """old ids -> new ids, of the shape and dtype of ids (a gather of remap on the plan's device): -1 for a dropped id.
+        ValueError: an id outside [0, n_old) (one read-back), ids that are no int32 / int64 tensor."""
+        ids = torch.as_tensor(ids, device=self.device)
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError('NodeCompaction.translate: ids are int32 or int64')
+        if ids.numel() and bool(((ids < 0) | (ids >= self.n_old)).any()):
+            raise ValueError(f'NodeCompaction.translate: an id outside [0, {self.n_old})')
+        return self.remap[ids.long()].to(ids.dtype)
+
+    def bitmap(self, bits: Tensor, n_ids: Optional[int] = None) -> Tensor:
+        """A `new_bitmap` over the new ids with the bits of `bits`, a bitmap over the old ones (an `uptodate` bitmap, the
+        mailbox's has_msg bits): new bit j = old bit old_of[j].  n_ids: the old ids `bits` covers (default: all it has words
+        for, at most n_old); the result covers the kept ids below it."""
+        return bitmap_compacted(bits, self, n_ids)
+
+    def rows_below(self, n_ids: int) -> int:
+        """the kept ids below n_ids <= n_old: the rows a table of n_ids rows keeps (a prefix of old_of: the remap is monotone)"""
+        n_ids = int(n_ids)
+        if not 0 <= n_ids <= self.n_old:
+            raise ValueError(f'NodeCompaction.rows_below: {n_ids} is outside [0, {self.n_old}]')
+        if n_ids == self.n_old:
+            return self.n_new
+        if n_ids == self.n_graph_old:
+            return self.n_graph_new
+        return int(torch.searchsorted(self.old_of, torch.tensor([n_ids], dtype=torch.int32, device=self.device))[0])
+
+
+def _drop_bitmap(what: str, drop_bits, N: int, dev, is_np: bool):
+    import numpy as np
+    W = (N + 63) // 64
+    if is_np:
+        ok = isinstance(drop_bits, np.ndarray) and drop_bits.dtype in (np.int64, np.uint64) and drop_bits.ndim == 1 \
+            and drop_bits.flags.c_contiguous and len(drop_bits) >= W
+    else:
+        ok = torch.is_tensor(drop_bits) and drop_bits.dtype == torch.int64 and drop_bits.dim() == 1 \
+            and drop_bits.is_contiguous() and drop_bits.numel() >= W and drop_bits.device == dev
+    if not ok:
+        raise ValueError(f'{what}: drop_bits over {N} ids is a contiguous 1-d int64 bitmap of at least {W} words'
+                         + ('' if is_np else f' on {dev}'))
+
+
+def node_compact_plan(graph, drop_bits: Tensor, n_ids: Optional[int] = None, strict: bool = True) -> NodeCompaction:
+    """Renumber the node ids densely without the ids of `drop_bits` (tiger_hip.h: tg_node_compact_plan).  drop_bits: 64-bit
+    words over n_ids ids (default graph.num_node; at least that), a set bit = the id leaves - an IdMap's free_bits goes in as
+    it is.  graph=None plans the ids alone (an id map without a model).  On the bitmap's device and the current stream, ONE
+    read-back of the four result words.  ValueError (strict=True): the error classes ID0 / SPARE / ROW / NBR with the
+    smallest offender (NODE_COMPACT_TEXT); strict=False leaves them in plan.code / plan.first, the arrays are then not to
+    be used."""
+    if not torch.is_tensor(drop_bits) or drop_bits.device.type == 'cpu':
+        raise ValueError('node_compact_plan runs on the device (host arrays: node_compact_host)')
+    dev = drop_bits.device
+    with torch.cuda.device(dev):
+        if graph is None:
+            keep = torch.zeros(2, dtype=torch.int64, device=dev)
+            g = _lib.TgTcsr(1, 0, ptr(keep), None, None, None)
+        else:
+            g, keep = _graph_struct('node_compact_plan', graph, dev)
+        N = int(g.num_node if n_ids is None else n_ids)
+        if N < g.num_node or N > 0x7FFFFFFF:
+            raise ValueError(f'node_compact_plan: n_ids = {N} must lie in [num_node = {g.num_node}, 2^31 - 1]')
+        _drop_bitmap('node_compact_plan', drop_bits, N, dev, False)
+        remap = torch.empty(N, dtype=torch.int32, device=dev)
+        old_of = torch.empty(N, dtype=torch.int32, device=dev)
+        indptr = torch.empty(g.num_node + 1, dtype=torch.int64, device=dev)
+        nbr = torch.empty(g.num_entry, dtype=torch.int32, device=dev)
+        out4 = torch.empty(4, dtype=torch.int64, device=dev)
+        nbytes = int(lib.tg_node_compact_workspace_bytes(N))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check_rc = lib.tg_node_compact_plan(C_.byref(g), ptr(drop_bits), drop_bits.numel(), N, ptr(remap), ptr(old_of), ptr(indptr),
+                                            ptr(nbr), ptr(out4), ptr(ws), nbytes, stream_ptr(dev))
+        check(check_rc, 'tg_node_compact_plan')
+        n_new, n_graph, code, first = out4.tolist()  # the one read-back
+    if code and strict:
+        raise ValueError('node_compact_plan: ' + NODE_COMPACT_TEXT(code, first, N))
+    return NodeCompaction(remap, old_of[:n_new], N, n_new, g.num_node, n_graph, indptr[:n_graph + 1] if graph is not None else None,
+                          nbr if graph is not None else None, code, first)
+
+
+def node_compact_host(graph, drop_bits, n_ids: Optional[int] = None, strict: bool = True) -> NodeCompaction:
+    """`node_compact_plan` with the host twin (tiger_hip.h: tg_node_compact_plan_host) over the graph's host arrays and a
+    numpy int64 bitmap (`host_bitmap`) -> a NodeCompaction of CPU tensors (indptr / nbr: numpy arrays)."""
+    import numpy as np
+    if torch.is_tensor(drop_bits):
+        drop_bits = drop_bits.numpy()
+    if graph is None:
+        keep = (np.zeros(2, dtype=np.int64),)
+        g = _lib.TgTcsr(1, 0, ptr(keep[0]), None, None, None)
+    else:
+        g, keep = _graph_struct('node_compact_host', graph, torch.device('cpu'))
+    N = int(g.num_node if n_ids is None else n_ids)
+    if N < g.num_node or N > 0x7FFFFFFF:
+        raise ValueError(f'node_compact_host: n_ids = {N} must lie in [num_node = {g.num_node}, 2^31 - 1]')
+    _drop_bitmap('node_compact_host', drop_bits, N, None, True)
+    remap, old_of = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+    indptr, nbr = np.empty(g.num_node + 1, dtype=np.int64), np.empty(g.num_entry, dtype=np.int32)
+    out4 = np.empty(4, dtype=np.int64)
+    check_rc = lib.tg_node_compact_plan_host(C_.byref(g), ptr(drop_bits), len(drop_bits), N, ptr(remap), ptr(old_of), ptr(indptr),
+                                             ptr(nbr), ptr(out4))
+    check(check_rc, 'tg_node_compact_plan_host')
+    n_new, n_graph, code, first = (int(x) for x in out4)
+    if code and strict:
+        raise ValueError('node_compact_host: ' + NODE_COMPACT_TEXT(code, first, N))
+    return NodeCompaction(torch.from_numpy(remap), torch.from_numpy(old_of[:n_new].copy()), N, n_new, g.num_node, n_graph,
+                          indptr[:n_graph + 1].copy() if graph is not None else None, nbr if graph is not None else None,
+                          code, first)
+
+
+def node_rows_compact(tables, old_of: Tensor):
+    """ONE launch that compacts up to 8 per-node tables by `old_of` (tiger_hip.h: tg_node_rows_compact; CPU tensors: its host
+    twin).  tables: (src, dst) pairs of contiguous tensors of one dtype and trailing shape on old_of's device; for j <
+    dst.shape[0] <= old_of.numel(): dst[j] = src[old_of[j]], bit for bit.  A row is the bytes of src[i]: a multiple of 16, or
+    8, 4 or 1.  dst may be the leading rows of a larger backing store; src and dst must not overlap.  ValueError: more than
+    8 tables, tensors of other shapes / dtypes / devices, another row width."""
+    tables = list(tables)
+    dev = old_of.device
+    if not (torch.is_tensor(old_of) and old_of.dtype == torch.int32 and old_of.dim() == 1 and old_of.is_contiguous()):
+        raise ValueError('node_rows_compact: old_of must be a contiguous 1-d int32 tensor')
+    if len(tables) > _lib.TG_NODE_ROWS_MAX:
+        raise ValueError(f'node_rows_compact: {len(tables)} tables in one call (at most {_lib.TG_NODE_ROWS_MAX})')
+    descs = (_lib.TgNodeRows * max(len(tables), 1))()
+    for i, (src, dst) in enumerate(tables):
+        if not (torch.is_tensor(src) and torch.is_tensor(dst) and src.dim() >= 1 and src.is_contiguous() and dst.is_contiguous()
+                and src.dtype == dst.dtype and src.shape[1:] == dst.shape[1:] and src.device == dev and dst.device == dev):
+            raise ValueError(f'node_rows_compact: table {i} must be a (src, dst) pair of contiguous tensors of one dtype and '
+                             f'row shape on {dev}')
+        row_bytes = src.element_size()
+        for s in src.shape[1:]:
+            row_bytes *= int(s)
+        if dst.shape[0] > old_of.numel() or src.shape[0] < 1:
+            raise ValueError(f'node_rows_compact: table {i} wants {dst.shape[0]} rows, old_of has {old_of.numel()}')
+        if row_bytes not in (1, 4, 8) and (row_bytes < 16 or row_bytes % 16):
+            raise ValueError(f'node_rows_compact: table {i} has rows of {row_bytes} bytes (a multiple of 16, or 8, 4 or 1)')
+        descs[i] = _lib.TgNodeRows(ptr(src), ptr(dst), row_bytes, dst.shape[0], src.shape[0])
+    if dev.type == 'cpu':
+        check(lib.tg_node_rows_compact_host(descs, len(tables), ptr(old_of), old_of.numel()), 'tg_node_rows_compact_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_node_rows_compact(descs, len(tables), ptr(old_of), old_of.numel(), stream_ptr(dev)), 'tg_node_rows_compact')
+
+
+def bitmap_compacted(bits: Tensor, plan, n_ids: Optional[int] = None) -> Tensor:
+    """A `new_bitmap` over the ids a compaction kept with the bits of `bits`, a bitmap over the old ids (tiger_hip.h:
+    tg_bitmap_compact; CPU tensors: its host twin): new bit j = old bit plan.old_of[j]; spare bits zero.  n_ids: the old
+    ids `bits` covers (default min(64 * words, plan.n_old)); the result covers plan.rows_below(n_ids) ids.  ValueError: bits
+    is no int64 bitmap on the plan's device, or holds fewer words than n_ids take."""
+    dev = plan.device
+    if not (torch.is_tensor(bits) and bits.dtype == torch.int64 and bits.dim() == 1 and bits.is_contiguous() and bits.device == dev):
+        raise ValueError(f'bitmap_compacted: bits must be a contiguous 1-d int64 bitmap on {dev}')
+    n_in = min(64 * bits.numel(), plan.n_old) if n_ids is None else int(n_ids)
+    if n_in < 0 or n_in > plan.n_old or bitmap_words(n_in) > bits.numel():
+        raise ValueError(f'bitmap_compacted: {bits.numel()} words for {n_in} ids of a plan over {plan.n_old}')
+    return bitmap_compact(bits, plan.old_of, n_in, plan.rows_below(n_in))
+
+
+def bitmap_compact(bits: Tensor, old_of: Tensor, n_in: int, n_out: int, out: Optional[Tensor] = None) -> Tensor:
+    """tiger_hip.h: tg_bitmap_compact (CPU tensors: its host twin) over a bitmap of n_in ids and the first n_out entries of
+    old_of -> `out` (a zeroed bitmap of at least bitmap_words(n_out) words, e.g. a store with head-room; allocated exactly
+    otherwise), its first bitmap_words(n_out) words written."""
+    dev = old_of.device
+    W = bitmap_words(n_out)
+    if out is None:
+        out = torch.zeros(W, dtype=torch.int64, device=dev)
+    if (bits.dtype != torch.int64 or bits.device != dev or bits.numel() < bitmap_words(n_in) or not bits.is_contiguous()
+            or old_of.dtype != torch.int32 or old_of.numel() < n_out or not old_of.is_contiguous()
+            or out.dtype != torch.int64 or out.device != dev or out.numel() < W or not out.is_contiguous()):
+        raise ValueError(f'bitmap_compact: int64 bitmaps over {n_in} and {n_out} ids and an int32 old_of of {n_out} entries on {dev}')
+    if dev.type == 'cpu':
+        check(lib.tg_bitmap_compact_host(ptr(bits), n_in, ptr(old_of), n_out, ptr(out)), 'tg_bitmap_compact_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_bitmap_compact(ptr(bits), n_in, ptr(old_of), n_out, ptr(out), stream_ptr(dev)), 'tg_bitmap_compact')
+    return out

@@ -100,6 +100,31 @@ class NumericalFeature(nn.Module):
         self._version_ = getattr(self, '_version_', 0) + 1
         return moved
 
+    def compact_node_rows(self, old_of, reserve: Optional[int] = None):
+        """Keep the node-table rows of the ids old_of (int32, ascending: NodeCompaction.old_of), renumbered densely
+        (TIGE.compact_nodes; Memory.compact: the same contract).  The table becomes the leading view of a NEW zeroed
+        backing store, `n_nodes` follows.  Refused, with nothing changed: what `append_node_rows` refuses."""
+        self._adopt_compacted(self._compact_build(old_of, reserve))
+
+    def _compact_build(self, old_of, reserve):
+        from .memory import compact_tables
+        if self.nfeats is None:
+            raise NotImplementedError('compact_node_rows: the feature getter has no node table (n_nodes is its row count)')
+        if not self.pin_mem:
+            raise NotImplementedError('compact_node_rows: the node table lives in pinned host memory (register_buffer=False)')
+        cur = self.nfeats
+        if not (torch.is_tensor(old_of) and old_of.dtype == torch.int32 and old_of.dim() == 1 and old_of.is_contiguous()
+                and old_of.device == cur.device and 1 <= old_of.numel() <= cur.shape[0]):
+            raise ValueError(f'compact_node_rows: old_of must be a contiguous 1-d int32 tensor of 1 to {cur.shape[0]} old ids '
+                             f'on {cur.device}')
+        return compact_tables([(self, 'nfeats')], old_of, reserve)
+
+    def _adopt_compacted(self, built):
+        from .memory import adopt_tables
+        adopt_tables(built)
+        self.n_nodes = built[0][3]
+        self._version_ = getattr(self, '_version_', 0) + 1
+
     def set_node_rows(self, ids, rows, check: bool = True):
         """Overwrite rows of the node table (a dense id that is handed out again, TIGE.erase_keys / observe_keys): ids [k]
         int32 / int64, DISTINCT; `rows` [k, d_n], or the int 0 for zero rows.  The table's address does not move.  A model

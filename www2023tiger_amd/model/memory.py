@@ -44,6 +44,38 @@ def grow_table(mod: nn.Module, name: str, rows: int, cap_rows: int) -> bool:
     return getattr(mod, name).data_ptr() != cur.data_ptr()
 
 
+def compact_tables(tables, old_of: Tensor, reserve: Optional[int] = None):
+    """The first half of a compaction of per-node tables (TIGE.compact_nodes): tables = (module, buffer name)
+    pairs, at most 8, every buffer with a row per OLD node id; old_of int32 [n_new], ascending - the old id of every new
+    one.  Each buffer gets a NEW zeroed backing store with the head-room of `grow_capacity` (reserve=: its rows) whose
+    leading n_new rows are store[j] = buffer[old_of[j]], all of them moved by ONE launch (hip_ops.node_rows_compact).
+    Nothing of the modules has changed yet -> what `adopt_tables` swaps in.  Peak memory is old table + new table."""
+    n_new = old_of.numel()
+    cap = grow_capacity(n_new, n_new, reserve)
+    built, pairs = [], []
+    for mod, name in tables:
+        cur = getattr(mod, name)
+        store = torch.zeros((cap,) + tuple(cur.shape[1:]), dtype=cur.dtype, device=cur.device)
+        built.append((mod, name, store, n_new))
+        pairs.append((cur, store[:n_new]))
+    hip_ops.node_rows_compact(pairs, old_of)
+    return built
+
+
+def adopt_tables(built):
+    """The second half: every buffer becomes the leading view of its new store (plain attribute stores: nothing can raise)"""
+    for mod, name, store, rows in built:
+        mod.__dict__.setdefault('_stores', {})[name] = store
+        setattr(mod, name, store[:rows])
+
+
+def _old_of(what: str, mod, old_of) -> Tensor:
+    if not (torch.is_tensor(old_of) and old_of.dtype == torch.int32 and old_of.dim() == 1 and old_of.is_contiguous()
+            and old_of.device == mod.device and 1 <= old_of.numel() <= mod.n):
+        raise ValueError(f'{what}: old_of must be a contiguous 1-d int32 tensor of 1 to {mod.n} old ids on {mod.device}')
+    return old_of
+
+
 class Memory(nn.Module):
     def __init__(self, n, dim):
         super().__init__()
@@ -98,6 +130,23 @@ class Memory(nn.Module):
         self.n = n
         self._version_ += 1
         return any(moved)
+
+    COMPACT_TABLES = ('vals', 'update_ts', 'active_mask')
+
+    def compact(self, old_of: Tensor, reserve: Optional[int] = None):
+        """Keep the rows of the ids old_of (int32, ascending: NodeCompaction.old_of), renumbered densely (TIGE.compact_nodes;
+        memory.py has no counterpart: the reference sizes its tables once).  vals, update_ts and active_mask become the
+        leading views of NEW zeroed backing stores with the head-room of `grow_capacity` (reserve=: their rows) and stay
+        buffers of exactly old_of.numel() rows under their names: `grow` keeps working and a checkpoint interchanges with
+        a module born with that many rows.  One launch moves the three tables.  ValueError: old_of is no int32 list of 1
+        to n ids on the module's device, reserve below its length."""
+        built = compact_tables([(self, name) for name in self.COMPACT_TABLES], _old_of('Memory.compact', self, old_of), reserve)
+        self._adopt_compacted(built)
+
+    def _adopt_compacted(self, built):
+        adopt_tables(built)
+        self.n = built[0][3]
+        self._version_ += 1
 
     def get(self, ids: Tensor) -> Tuple[Tensor, Tensor]:
         return hip_ops.gather_rows(self.vals, ids, self.update_ts)
@@ -156,6 +205,26 @@ class MessageStoreNoGradLastOnly(nn.Module):
         self.n = n
         self._version_ += 1
         return any(moved)
+
+    COMPACT_TABLES = ('node_msg_vals', 'node_msg_ts')
+
+    def compact(self, old_of: Tensor, reserve: Optional[int] = None):
+        """Keep the mailbox rows of the ids old_of, renumbered densely (Memory.compact: the same contract).  has_msg_bits
+        becomes the bitmap over the new ids - new bit j = old bit old_of[j], spare bits zero (tg_bitmap_compact) - at the
+        head of a store of the same capacity as the rows."""
+        old_of = _old_of('MessageStoreNoGradLastOnly.compact', self, old_of)
+        built = compact_tables([(self, name) for name in self.COMPACT_TABLES], old_of, reserve)
+        self._adopt_compacted(built, self._compacted_bits(old_of, built[0][2].shape[0]))
+
+    def _compacted_bits(self, old_of: Tensor, cap_rows: int) -> Tensor:
+        store = torch.zeros(hip_ops.bitmap_words(cap_rows), dtype=torch.int64, device=self.device)
+        hip_ops.bitmap_compact(self.has_msg_bits, old_of, self.n, old_of.numel(), out=store)
+        return store
+
+    def _adopt_compacted(self, built, bits_store: Tensor):
+        adopt_tables(built + [(self, 'has_msg_bits', bits_store, hip_ops.bitmap_words(built[0][3]))])
+        self.n = built[0][3]
+        self._version_ += 1
 
     # -- set view of the bitmap (host sync; diagnostic / compatibility only) --------
     def _has_msg_numpy(self) -> np.ndarray:

@@ -1749,6 +1749,155 @@ class TIGE(nn.Module):
         graph = self.graph if self.graph.num_node == num_node else self.graph.widened(num_node)
         return self._grow(num_node, nfeats, reserve, graph)
 
+    # ---- compacting the node id space ------------------------------------------------------------------------
+    def _compact_refusals(self, what: str):
+        """everything a compaction refuses that can be told before the plan, with nothing changed"""
+        self._refuse_partitioned(what)
+        if self.training:
+            raise RuntimeError(f'{what}: node ids are compacted in eval() mode (the streaming state of a served model)')
+        from .restarters import StaticRestarter
+        if isinstance(getattr(self, 'restarter_fn', None), StaticRestarter):
+            raise NotImplementedError(f'{what}: the static restarter holds one TRAINED embedding row per node; resizing a '
+                                      'parameter under an optimizer is not supported')
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'{what}: the model lives on {self.device}; node ids are compacted on the GPU')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: tables cannot be compacted while a stream is being captured into a graph')
+        fg = self.raw_feat_getter
+        if fg.nfeats is None:
+            raise NotImplementedError(f'{what}: the feature getter has no node table (n_nodes is its row count)')
+        if not fg.pin_mem:
+            raise NotImplementedError(f'{what}: the node table lives in pinned host memory (register_buffer=False)')
+        if not (fg.nfeats.shape[0] == self.left_memory.n == self.right_memory.n == self.msg_store.n == self.n_nodes):
+            raise RuntimeError(f'{what}: the per-node tables do not all hold n_nodes = {self.n_nodes} rows')
+        if self.graph.num_node > self.n_nodes:
+            raise RuntimeError(f'{what}: the graph covers {self.graph.num_node} node ids, more than n_nodes = {self.n_nodes}')
+
+    def _compact_plan(self, what: str, drop_bits: Tensor, n_ids: int):
+        """-> (the plan, the graph it was made over: the model's, widened to n_nodes if it covers fewer ids); the ROW / NBR
+        classes name the id and say what to do"""
+        g = self.graph if self.graph.num_node == self.n_nodes else self.graph.widened(self.n_nodes)
+        g.tcsr  # (a graph that was never sampled from has no device arrays yet)
+        plan = hip_ops.node_compact_plan(g, drop_bits, n_ids, strict=False)
+        if plan.code in (hip_ops._lib.TG_NODE_COMPACT_ROW, hip_ops._lib.TG_NODE_COMPACT_NBR):
+            node = plan.first if plan.code == hip_ops._lib.TG_NODE_COMPACT_ROW else int(g._dev[2][plan.first])
+            how = 'still owns entries of the graph' if plan.code == hip_ops._lib.TG_NODE_COMPACT_ROW else \
+                f'is still the neighbour of entry {plan.first} of the graph'
+            raise ValueError(f'{what}: node {node} is dropped but {how}: `erase` it first '
+                             f'({hip_ops.NODE_COMPACT_CLASSES[plan.code - 1]})')
+        if plan.code:
+            raise ValueError(f'{what}: ' + hip_ops.NODE_COMPACT_TEXT(plan.code, plan.first, n_ids))
+        return plan, g
+
+    def _compact(self, plan, graph, reserve):
+        """a compaction after its refusals: everything is BUILT first - child graph, new tables -, then swapped in one step"""
+        from .memory import compact_tables
+        self._poll_train_errors()  # (the step buffers are about to be dropped: a deferred invariant word is read first)
+        n_new = plan.n_graph_new
+        old_of = plan.old_of[:n_new]  # (monotone: the kept ids below n_nodes are a prefix)
+        L, R, S, fg = self.left_memory, self.right_memory, self.msg_store, self.raw_feat_getter
+        child = graph.compacted(plan)
+        built = compact_tables([(m, name) for m in (L, R, S) for name in m.COMPACT_TABLES], old_of, reserve)  # 8 tables, ONE launch
+        bits = S._compacted_bits(old_of, built[0][2].shape[0])
+        node_rows = fg._compact_build(old_of, reserve)
+        # ---- nothing has changed up to here; nothing below can raise ----
+        eager = self._pending is not None
+        L._adopt_compacted(built[0:3])
+        R._adopt_compacted(built[3:6])
+        S._adopt_compacted(built[6:8], bits)
+        fg._adopt_compacted(node_rows)
+        self.n_nodes = n_new
+        if getattr(self, 'restarter_fn', None) is not None:
+            self.restarter_fn.n_nodes = n_new
+        self.graph = child  # (the setter: the restarter follows; snapshot stamps go stale)
+        self._touch()
+        self.invalidate_struct()
+        self._step_ws = {k: v for k, v in self._step_ws.items() if k == 'rng'}
+        self._gtab = self._ctab = self._gtab_stamp = None
+        self._pending = self._pending_stamp = None
+        if eager:
+            self.eager_updates()
+
+    @torch.no_grad()
+    def compact_nodes(self, drop, reserve: Optional[int] = None, *, bitmap: bool = False):
+        """Take erased node ids OUT of the id space: the remaining ids are renumbered densely IN THEIR ORDER and everything
+        sized by n_nodes shrinks - both memories, the mailbox, the node table, the graph's indptr (tg_node_compact.hip;
+        DESIGN 7.20) -> the NodeCompaction (remap, old_of, n_old, n_new, translate, bitmap).  drop: int64 node ids
+        (a sequence or tensor; duplicates are fine) or, with bitmap=True, a bitmap over n_nodes ids (`hip_ops.new_bitmap`
+        words on the model's device, a set bit = the id leaves).  A dropped id must have been erased (`erase`): it owns no entry and is
+        nobody's neighbour.  Because the remap is monotone every "ascending id" / "ascending column" tie-break survives:
+        the compacted model is the uncompacted one under `remap`, bit for bit, for every product.
+        Everything is built first - plan (ONE read-back), child graph (`Graph.compacted`: ts / eid shared with the
+        parent), new tables (new zeroed backing stores with the head-room of `grow_capacity`, reserve=: their rows; the
+        eight tables of memories and mailbox move in ONE launch) - and then swapped in one step: if anything raises,
+        nothing has changed.  Peak memory is old table + new table (no in-place compaction).  Then, as `grow_nodes`:
+        n_nodes changes on the model, the restarter and the feature getter, the graph goes through the setter, step
+        buffers (but the dropout generator) and the eager-update and query tables are dropped and rebuilt before their
+        next use.  An empty `drop` returns the identity plan and changes nothing.
+        WHAT THE CALLER MUST DO AFTERWARDS: captured device graphs and resident evaluation runs are rebuilt; `uptodate`
+        bitmaps go through `plan.bitmap`; node ids it holds go through `plan.translate` (-1: dropped); StepBuffers and
+        CatalogueSnapshots from before are stale - a snapshot of the old numbering is REFUSED by `recommend` through its
+        stamp, never remapped; a `save_memory_state` from before no longer fits.
+        Refused before anything changes: a partitioned model, training mode, a model with a StaticRestarter (its rows are
+        trained parameters under an optimiser), a stream capture in progress, a node table in pinned host memory or no
+        node table, per-node tables (or a graph) that do not all hold n_nodes rows, id 0 or an id outside [0, n_nodes),
+        and a dropped id that still owns entries or is still a neighbour (the id is named: `erase` it first)."""
+        self._compact_refusals('compact_nodes')
+        n = self.n_nodes
+        if bitmap:
+            if not (torch.is_tensor(drop) and drop.dtype == torch.int64 and drop.dim() == 1 and drop.is_contiguous()
+                    and drop.device == self.device and drop.numel() >= hip_ops.bitmap_words(n)):
+                raise ValueError(f'compact_nodes: a bitmap over {n} ids is a contiguous int64 tensor of '
+                                 f'{hip_ops.bitmap_words(n)} words on {self.device}')
+            bits = drop
+        else:
+            ids = torch.as_tensor(drop)
+            if ids.numel() and (ids.dtype.is_floating_point or ids.dtype == torch.bool):
+                raise ValueError(f'compact_nodes: drop holds integer node ids (bitmap=True: a bitmap), not {ids.dtype}')
+            ids = ids.to(self.device, torch.int64).reshape(-1)
+            if ids.numel():
+                lo, hi = (int(x) for x in torch.aminmax(ids))
+                if lo < 0 or hi >= n:
+                    raise ValueError(f'compact_nodes: node ids must lie in [0, n_nodes) (n_nodes = {n})')
+                if lo == 0:
+                    raise ValueError('compact_nodes: node id 0 is the padding id and can never be dropped')
+            bits = hip_ops.new_bitmap(n, self.device)
+            if ids.numel():
+                hip_ops.bitmap_mark(ids, bits, n)
+        plan, graph = self._compact_plan('compact_nodes', bits, n)
+        if not plan.identity:
+            self._compact(plan, graph, reserve)
+        return plan
+
+    @torch.no_grad()
+    def compact_keys(self, idmap, reserve: Optional[int] = None):
+        """`compact_nodes` behind an id map: the ids the map holds FREE (after `erase_keys`) leave the model AND the map ->
+        the NodeCompaction.  ONE plan over max(idmap.size, n_nodes) ids with drop_bits = idmap.free_bits serves both sides.
+        Ids in [n_nodes, idmap.size) are assigned but never admitted (the batch that brought their key was refused): they
+        have no model rows and are kept or dropped like any other; the model's new n_nodes is the number of kept ids below
+        the old one, the map's new size the number below its old size.  The model side is validated and built before the
+        map is touched, and the map builds its new tables before it swaps them: if the call raises, neither has changed.
+        Afterwards idmap.size = live keys + 1, n_free = 0, its capacity has SHRUNK to what the live keys need, and
+        `observe_keys` / `recommend_keys` go on as before.  Nothing free: the identity plan, nothing changes.  The caller's
+        duties and the refusals are those of `compact_nodes`; also refused: a map on another device, a map that holds
+        fewer ids than the model has admitted."""
+        self._compact_refusals('compact_keys')
+        if idmap.device != self.device:
+            raise ValueError(f'compact_keys: the id map lives on {idmap.device}, the model on {self.device}')
+        if idmap.size < self.n_nodes:
+            raise ValueError(f'compact_keys: the id map holds {idmap.size} ids, the model has admitted {self.n_nodes}')
+        plan, graph = self._compact_plan('compact_keys', idmap.free_bits, idmap.size)
+        if plan.identity:
+            return plan
+        # the map's side is checked before the model changes (IdMap.compact repeats it)
+        if plan.rows_below(idmap.size) != idmap.size - idmap.n_free:
+            raise ValueError(f'compact_keys: the map\'s bitmap holds {idmap.size - plan.n_new} free ids, the map counts '
+                             f'{idmap.n_free}')
+        built_map = idmap._compact_build(plan)
+        self._compact(plan, graph, reserve)
+        idmap._compact_adopt(built_map)
+        return plan
+
     # ---- serving behind external keys (data/idmap.py: IdMap; DESIGN 7.18) ------------------------------------------------
     def _device_keys(self, what: str, name: str, keys) -> Tensor:
         keys = torch.as_tensor(keys)

@@ -47,6 +47,10 @@ replay's, exactly, and `run_online` asserts it.  With --save_state / --load_stat
 printed per batch - the model stays as large as its peak of live keys.  --compact_at F (with --churn) goes further: when
 the share of free ids passes F behind an erase, `TIGE.compact_keys` renumbers the live keys densely and shrinks the map and
 every per-node table to them; rows before -> after are printed.
+--late FRACTION [--late_by BATCHES] makes part of the feed arrive late: a seeded fraction of every test batch is held back
+and handed to `TIGE.observe_late` that many batches later (default 1) - merged into the device graph at the place its
+time gives it, never streamed into the memories.  The number of late events merged is printed, there is no offline line
+beside it, and at the end the graph is asserted equal to the graph over the whole stream (`run_online`).
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -240,7 +244,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
                erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False,
-               churn=None, compact_at=None):
+               churn=None, compact_at=None, late=None, late_by=1):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -278,8 +282,25 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     taken OUT of the id space (`compact_keys`): the live keys are renumbered densely and the map, both memories, the mailbox,
     the node table and the graph shrink to them.  The replay prints rows before -> after and its metrics carry 'compacted':
     (batch, n_nodes before, n_nodes after).  This replay holds keys, never dense ids, between batches and no `uptodate`
-    bitmap; a caller that holds either passes them through the returned plan (`plan.translate`, `plan.bitmap`)."""
+    bitmap; a caller that holds either passes them through the returned plan (`plan.translate`, `plan.bitmap`).
+    late (a fraction in [0, 1); the plain online replay only): a seeded fraction of every test batch is HELD BACK - never
+    the batch's first event - and handed to `observe_late` late_by batches later (what is still held at the end, behind
+    the last batch).  A late event is ranked on time but ingested late: it becomes part of the graph - neighbours,
+    histories, exclude_seen - from then on and is never streamed into the memories, so the lists differ from the offline
+    replay's and none is made.  The replay prints, and its metrics carry, 'late': the number of late events merged; the
+    final graph is asserted equal to the graph over the whole stream: indptr and ts exactly, nbr up to the order among
+    entries of one node at one time (a late entry stands behind the on-time ones of its time)."""
     from www2023tiger_amd.data.graph import Graph
+    forgetting = window is not None or keep_last is not None
+    if late is not None:
+        if not 0 <= float(late) < 1:
+            raise ValueError(f'late = {late} is a fraction of every batch in [0, 1)')
+        if int(late_by) < 1:
+            raise ValueError(f'late_by = {late_by}: a late event arrives at least one batch later')
+        if keyed or grow or forgetting or erase_nodes is not None or retract_eids is not None or save_state or load_state \
+                or save_after is not None:
+            raise ValueError('late: the plain online replay only (no --keyed, --grow, --window / --keep_last, erase, save / load)')
+        offline = False
     if churn is not None and not keyed:
         raise ValueError('churn names the nodes that leave by their keys: it needs --keyed')
     if compact_at is not None and churn is None:
@@ -423,10 +444,35 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                 rows.append((rel.rows_before, rel.rows))
                 if verbose:
                     print(f'batch {len(forgot) - 1}: edge table {rel.rows_before} rows -> {rel.rows}')
-        forgetting = window is not None or keep_last is not None
-        ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs,
-                                 observe_and_forget if forgetting else observe, known=known if grow else None,
+        held, n_late, rs_late = [], [0, 0], np.random.RandomState(seed)   # (due batch, s, d, t, e); merged, batches
+
+        def merge_due(upto):
+            while held and held[0][0] <= upto:
+                ev = held.pop(0)[1:]
+                model.observe_late(*ev)   # (the edge table already holds their rows: no efeats)
+                n_late[0] += len(ev[0])
+
+        def observe_some_late(s, d, t, e):
+            m = rs_late.uniform(size=len(s)) < float(late)
+            m[0] = False
+            observe(s[~m], d[~m], t[~m], e[~m])
+            b = n_late[1]
+            n_late[1] += 1
+            if m.any():
+                held.append((b + int(late_by), s[m], d[m], t[m], e[m]))
+            merge_due(b)
+        ingest = observe_and_forget if forgetting else (observe if late is None else observe_some_late)
+        ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=known if grow else None,
                                  first=first, stop=stop, keyed=keyed or None)
+        if late is not None:
+            merge_due(float('inf'))
+            if verbose:
+                print(f'late: {n_late[0]} of {online["n_events"]} events were held back and merged by observe_late')
+            got, want = (tuple(a.cpu().numpy() for a in g._tensors()) for g in (model.graph, full_graph))
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.int64), want[1].view(np.int64))
+            owner = np.repeat(np.arange(len(want[0]) - 1), np.diff(want[0]))
+            by_time = lambda a: a[2][np.lexsort((a[2], a[1], owner))]   # (ties of one node at one time: by neighbour)
+            assert np.array_equal(by_time(got), by_time(want))
         if save_state is not None:
             done = len(test.src) if stop is None else min(stop, len(test.src))
             blob = dict(state=model.online_state(), next_event=done, shifted=shifted[0])
@@ -453,6 +499,8 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         online = dict(online, compacted=compacted)
     if erasing:
         online = dict(online, erased=erased)
+    if late is not None:
+        online = dict(online, late=n_late[0])
     if forgetting:
         online = dict(online, forgot=forgot)
         if release_rows:
@@ -548,6 +596,9 @@ if __name__ == '__main__':
     ap.add_argument('--churn', default=None, metavar='FILE', help='--online --keyed: a text file of lines "batch key" - the '
                     'keys that leave behind that batch (TIGE.erase_keys); their dense ids are handed out again, and the ids '
                     'released and recycled and n_nodes are printed per batch')
+    ap.add_argument('--late', type=float, default=None, metavar='FRACTION', help='--online: hold a seeded fraction of every '
+                    'test batch back and hand it to TIGE.observe_late --late_by batches later; prints the late events merged')
+    ap.add_argument('--late_by', type=int, default=1, metavar='BATCHES', help='--late: how many batches later (default 1)')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -571,7 +622,8 @@ if __name__ == '__main__':
                                                               retract_eids=None if a.retract_eids is None
                                                               else np.load(a.retract_eids), save_state=a.save_state,
                                                               save_after=a.save_after, load_state=a.load_state,
-                                                              keyed=a.keyed, churn=a.churn, compact_at=a.compact_at)):
+                                                              keyed=a.keyed, churn=a.churn, compact_at=a.compact_at,
+                                                              late=a.late, late_by=a.late_by)):
             if m is None:
                 continue
             if a.keyed and 'ids' in m:

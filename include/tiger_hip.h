@@ -132,6 +132,30 @@ int tg_tcsr_append_grow_host(const tg_tcsr* g, int64_t num_node_out, int64_t n_n
                              const int64_t* dst_host, const double* ts_host, const int64_t* eid_host,
                              int64_t* indptr_out_host, double* ts_out_host, int32_t* nbr_out_host, int32_t* eid_out_host);
 
+/* Late events: the T-CSR of `g` MERGED with a batch in ANY order that holds ANY non-NaN times - before, inside or after
+ * the range of `g` (graph.py:11-42,226-241: no counterpart - the reference sorts every list once, over the whole stream, and
+ * has no way to admit an event afterwards).  Arguments, arrays, workspace and the TG_EWORKSPACE / TG_EINVAL conventions are
+ * those of tg_tcsr_append_grow; `g` is only read.  Row v of the output is the stable merge of the old row v with the
+ * batch's entries owned by v sorted stably by time (entry j = 2e: event e seen from src, j = 2e + 1: from dst):
+ * - at equal times every old entry stands before every new one;
+ * - new entries of equal time keep ascending j (a self loop's flag-0 entry before its flag-1 entry);
+ * - "equal" is the float64 == of tg_tcsr_build_host's comparator: -0.0 and +0.0 are equal for the ORDER, and the stored ts
+ *   keeps the bits it came with.
+ * That is, byte for byte, what tg_tcsr_build_host gives for [old events | batch] with num_node_out nodes whenever `g` is the
+ * T-CSR of an event list, and is defined row-wise as above when it is not (a trimmed or compacted parent).  A batch that
+ * obeys tg_tcsr_append's contract gives tg_tcsr_append's bytes.  Device: a sort of the 2 n_new entries by (owner, time, j) -
+ * one workgroup up to 4 096 entries, three stable radix sorts above -, one upper-bound search per new entry inside its old
+ * row, then the SAME launch as the append over the old entries: no atomics, no pass or memset over num_node beside the
+ * indptr write, every old entry read and written once.  The host twin checks ids and eids as tg_tcsr_append_grow_host does,
+ * and refuses a NaN time (TG_EINVAL); on the device a NaN is the caller's to refuse. */
+size_t tg_tcsr_merge_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node, int64_t num_node_out);
+int tg_tcsr_merge(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src, const int64_t* dst,
+                  const double* ts, const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
+                  int32_t* eid_out, void* ws, size_t ws_bytes, void* stream);
+int tg_tcsr_merge_host(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src_host,
+                       const int64_t* dst_host, const double* ts_host, const int64_t* eid_host, int64_t* indptr_out_host,
+                       double* ts_out_host, int32_t* nbr_out_host, int32_t* eid_out_host);
+
 /* Sliding-window expiry: the T-CSR of `g` without its expired entries, written to caller-owned arrays; `g` itself is only
  * read and num_node does not change.  None of the four entries has a counterpart in the reference, which builds its
  * adjacency lists once over the whole stream and never drops an entry (graph.py:11-42).  Per node v with old row

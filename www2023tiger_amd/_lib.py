@@ -208,6 +208,9 @@ SIGNATURES = {
     'tg_tcsr_append_grow_workspace_bytes': (sz, [i64, i64, i64, i64]),
     'tg_tcsr_append_grow': (C.c_int, [P(TgTcsr), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'tg_tcsr_append_grow_host': (C.c_int, [P(TgTcsr), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'tg_tcsr_merge_workspace_bytes': (sz, [i64, i64, i64, i64]),
+    'tg_tcsr_merge': (C.c_int, [P(TgTcsr), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_tcsr_merge_host': (C.c_int, [P(TgTcsr), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     'tg_tcsr_trim_workspace_bytes': (sz, [i64]),
     'tg_tcsr_trim_plan': (C.c_int, [P(TgTcsr), C.c_double, i64, vp, vp, sz, vp]),
     'tg_tcsr_trim_apply': (C.c_int, [P(TgTcsr), vp, i64, vp, vp, vp, vp, sz, vp]),

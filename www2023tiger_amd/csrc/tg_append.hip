@@ -19,6 +19,19 @@
 // is the empty row at the end of the old array - every read of indptr_old is clamped to index num_node (steps 2 and 3),
 // step 3 runs over num_node_out + 1 entries and the large path sorts on the key bits of num_node_out.  Same launches, no
 // pass over num_node_out beside step 3 itself; with num_node_out == num_node the clamps never bind and the grid is the old one.
+//
+// Late events (tg_tcsr_merge: a batch in ANY order with ANY non-NaN times; the reference has no counterpart either).  Row v of
+// the output is the stable merge of the old row v with v's new entries sorted stably by time: at equal times old entries
+// first, new ones in ascending j - what the stable per-node sort of tg_tcsr_build_host gives over [old events | batch].  Only
+// steps 1-2 differ:
+//   1'. sort the m entries by (owner, time key, j); the time key is the float64 as an orderable uint64 (sign bit flipped for
+//       t >= 0, all bits for t < 0) with -0.0 read as +0.0 IN THE KEY ONLY: the two are == to the host comparator, and the
+//       stored time keeps its bits.  m <= MG_SMALL: one workgroup, 128-bit unique keys in LDS; else three stable radix sorts
+//       (time key low word, high word, owner) through radix_sort_pairs, the keys re-derived from the payload j in between.
+//   2'. INS[s] = first p of row S[s] with ts_old[p] > t(s) (strict, on values): an upper bound galloped for from the row's
+//       end, where a late event usually belongs.  Non-decreasing in s: within a row by t, across rows by the rows' order.
+// Steps 3-5 are k_append_apply as it stands (old entry p -> p + #{INS <= p}: it stays behind every new entry cut in at or
+// before it and before every later one).  Nothing loaded from the batch is used as an address; indptr is the parent's.
 #include <algorithm>
 #include <vector>
 
@@ -28,6 +41,7 @@
 namespace tg {
 
 constexpr int AP_SMALL = 4096;             // new entries (2 n) the one-workgroup sort takes
+constexpr int MG_SMALL = 4096;             // the same for a merge: 16 bytes of key per entry, 64 KiB of LDS - the static limit
 constexpr int AP_SORT_THREADS = 1024;
 constexpr int AP_THREADS = 256;
 constexpr int AP_ITEMS = 8;
@@ -153,6 +167,136 @@ static int append_key_bits(int64_t num_node) {
   return (b + 3) / 4 * 4;
 }
 
+// ---- late events: steps 1'-2' ----
+// float64 -> uint64 whose unsigned order is the order of '<' on non-NaN values, with -0.0 and +0.0 on one key
+__device__ __forceinline__ uint64_t time_key(double t) {
+  if (t == 0.0) t = 0.0;  // (-0.0 == 0.0: the key of +0.0)
+  const uint64_t b = (uint64_t)__double_as_longlong(t);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// INS of one new entry: the upper bound of t in the old row of `own` (an owner the old graph lacks: the empty row at the end)
+__device__ __forceinline__ uint32_t merge_cut(const tg_tcsr& g, uint32_t own, double t) {
+  const int64_t b = g.indptr[min((int64_t)own, g.num_node)], e = g.indptr[min((int64_t)own + 1, g.num_node)];
+  int64_t lo = b, hi = e, step = 1;  // entries at or after hi are > t; the answer lies in [lo, hi]
+  while (hi - step >= b) {
+    if (g.ts[hi - step] > t) {
+      hi -= step;
+      step <<= 1;
+    } else {
+      lo = hi - step + 1;
+      break;
+    }
+  }
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (g.ts[mid] > t) hi = mid;
+    else lo = mid + 1;
+  }
+  return (uint32_t)lo;
+}
+
+// m <= MG_SMALL: one workgroup, bitonic sort of M2 = pow2 >= m unique keys (owner : time key : j) in LDS, then INS
+__global__ void __launch_bounds__(AP_SORT_THREADS) k_merge_sort_small(uint32_t m, uint32_t M2, const int64_t* __restrict__ src,
+                                                                     const int64_t* __restrict__ dst,
+                                                                     const double* __restrict__ ts, tg_tcsr g,
+                                                                     uint32_t* __restrict__ S, uint32_t* __restrict__ J,
+                                                                     uint32_t* __restrict__ INS) {
+  __shared__ uint64_t khi[MG_SMALL];  // owner << 32 | time key >> 32
+  __shared__ uint64_t klo[MG_SMALL];  // time key << 32 | j
+  const uint32_t t = threadIdx.x, T = blockDim.x;
+  for (uint32_t j = t; j < M2; j += T) {
+    uint64_t h = ~0ull, l = ~0ull;  // padding keys sort last
+    if (j < m) {
+      const uint64_t tk = time_key(ts[j >> 1]);
+      h = ((uint64_t)entry_owner(src, dst, j) << 32) | (tk >> 32);
+      l = (tk << 32) | j;
+    }
+    khi[j] = h;
+    klo[j] = l;
+  }
+  __syncthreads();
+  for (uint32_t k = 2; k <= M2; k <<= 1) {
+    for (uint32_t h = k >> 1; h > 0; h >>= 1) {
+      for (uint32_t i = t; i < (M2 >> 1); i += T) {
+        const uint32_t a = ((i & ~(h - 1)) << 1) | (i & (h - 1)), b = a + h;
+        const uint64_t xh = khi[a], yh = khi[b], xl = klo[a], yl = klo[b];
+        const bool up = (a & k) == 0;
+        if ((xh > yh || (xh == yh && xl > yl)) == up) {
+          khi[a] = yh;
+          khi[b] = xh;
+          klo[a] = yl;
+          klo[b] = xl;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t s = t; s < m; s += T) {
+    const uint32_t own = (uint32_t)(khi[s] >> 32), j = (uint32_t)klo[s];
+    S[s] = own;
+    J[s] = j;
+    INS[s] = merge_cut(g, own, ts[j >> 1]);
+  }
+}
+
+// large path: the key of a pass from the payload j (WORD 0: time key, low word - also writes the payload; 1: high word; 2: owner)
+template <int WORD>
+__global__ void k_merge_keys(uint32_t m, const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+                             const double* __restrict__ ts, uint32_t* __restrict__ k, uint32_t* __restrict__ v) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const uint32_t j = WORD == 0 ? (uint32_t)i : v[i];
+  if (WORD == 0) v[i] = j;
+  if (WORD == 2) k[i] = (uint32_t)entry_owner(src, dst, j);
+  else k[i] = (uint32_t)(time_key(ts[j >> 1]) >> (WORD == 1 ? 32 : 0));
+}
+__global__ void k_merge_ins(uint32_t m, const uint32_t* __restrict__ S, const uint32_t* __restrict__ J,
+                            const double* __restrict__ ts, tg_tcsr g, uint32_t* __restrict__ INS) {
+  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < m) INS[s] = merge_cut(g, S[s], ts[J[s] >> 1]);
+}
+
+// steps 3-5 for either entry: one launch of k_append_apply
+static int launch_apply(const char* what, const tg_tcsr* g, int64_t num_node_out, uint32_t m, const uint32_t* S,
+                        const uint32_t* J, const uint32_t* INS, const int64_t* src, const int64_t* dst, const double* ts,
+                        const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out, int32_t* eid_out,
+                        hipStream_t st) {
+  AppendArgs a{};
+  a.g = *g;
+  a.num_node_out = num_node_out;
+  a.m = m;
+  a.S = S;
+  a.J = J;
+  a.INS = INS;
+  a.src = src;
+  a.dst = dst;
+  a.eid = eid;
+  a.ts = ts;
+  a.indptr_out = indptr_out;
+  a.ts_out = ts_out;
+  a.nbr_out = nbr_out;
+  a.eid_out = eid_out;
+  a.nb_new = (uint32_t)cdiv(m, AP_THREADS);
+  a.nb_ptr = (uint32_t)cdiv(num_node_out + 1, AP_THREADS);
+  const uint32_t nb_copy = (uint32_t)cdiv(g->num_entry, AP_TILE);
+  hipLaunchKernelGGL(k_append_apply, dim3(a.nb_new + a.nb_ptr + nb_copy), dim3(AP_THREADS), 0, st, a);
+  return check_launch(what);
+}
+
+// what both entries refuse before anything else (device pointers are not read)
+static int append_args(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const void* src, const void* dst, const void* ts,
+                       const void* eid, const void* indptr_out, const void* ts_out, const void* nbr_out, const void* eid_out) {
+  if (!g || n_new < 0 || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || !g->indptr || !indptr_out)
+    return TG_EINVAL;
+  if (num_node_out < g->num_node || num_node_out > 0x7fffffffLL) return TG_EINVAL;
+  if ((uint64_t)g->num_entry + 2 * (uint64_t)n_new > 0xffffffffull) return TG_EINVAL;
+  if (g->num_entry > 0 && (!g->ts || !g->nbr || !g->eid)) return TG_EINVAL;
+  if (g->num_entry + 2 * n_new > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
+  if (n_new > 0 && (!src || !dst || !ts || !eid)) return TG_EINVAL;
+  return TG_OK;
+}
+
 }  // namespace tg
 
 using namespace tg;
@@ -173,13 +317,8 @@ extern "C" size_t tg_tcsr_append_workspace_bytes(int64_t num_entry_old, int64_t 
 extern "C" int tg_tcsr_append_grow(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src, const int64_t* dst,
                                    const double* ts, const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
                                    int32_t* eid_out, void* ws, size_t ws_bytes, void* stream) {
-  if (!g || n_new < 0 || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || !g->indptr || !indptr_out)
-    return TG_EINVAL;
-  if (num_node_out < g->num_node || num_node_out > 0x7fffffffLL) return TG_EINVAL;
-  if ((uint64_t)g->num_entry + 2 * (uint64_t)n_new > 0xffffffffull) return TG_EINVAL;
-  if (g->num_entry > 0 && (!g->ts || !g->nbr || !g->eid)) return TG_EINVAL;
-  if (g->num_entry + 2 * n_new > 0 && (!ts_out || !nbr_out || !eid_out)) return TG_EINVAL;
-  if (n_new > 0 && (!src || !dst || !ts || !eid)) return TG_EINVAL;
+  const int bad = append_args(g, num_node_out, n_new, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out);
+  if (bad != TG_OK) return bad;
   hipStream_t st = as_stream(stream);
   const uint32_t m = (uint32_t)(2 * n_new);
   uint32_t *S = nullptr, *J = nullptr, *INS = nullptr;
@@ -211,26 +350,8 @@ extern "C" int tg_tcsr_append_grow(const tg_tcsr* g, int64_t num_node_out, int64
       hipLaunchKernelGGL(k_append_ins, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, m, S, g->indptr, g->num_node, INS);
     }
   }
-  AppendArgs a{};
-  a.g = *g;
-  a.num_node_out = num_node_out;
-  a.m = m;
-  a.S = S;
-  a.J = J;
-  a.INS = INS;
-  a.src = src;
-  a.dst = dst;
-  a.eid = eid;
-  a.ts = ts;
-  a.indptr_out = indptr_out;
-  a.ts_out = ts_out;
-  a.nbr_out = nbr_out;
-  a.eid_out = eid_out;
-  a.nb_new = (uint32_t)cdiv(m, AP_THREADS);
-  a.nb_ptr = (uint32_t)cdiv(num_node_out + 1, AP_THREADS);
-  const uint32_t nb_copy = (uint32_t)cdiv(g->num_entry, AP_TILE);
-  hipLaunchKernelGGL(k_append_apply, dim3(a.nb_new + a.nb_ptr + nb_copy), dim3(AP_THREADS), 0, st, a);
-  return check_launch("tg_tcsr_append_grow");
+  return launch_apply("tg_tcsr_append_grow", g, num_node_out, m, S, J, INS, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out,
+                      st);
 }
 
 extern "C" int tg_tcsr_append(const tg_tcsr* g, int64_t n_new, const int64_t* src, const int64_t* dst, const double* ts,
@@ -287,4 +408,109 @@ extern "C" int tg_tcsr_append_host(const tg_tcsr* g, int64_t n_new, const int64_
                                    int32_t* eid_out) {
   if (!g) return TG_EINVAL;
   return tg_tcsr_append_grow_host(g, g->num_node, n_new, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out);
+}
+
+// ---- late events: a batch in any order, with any non-NaN times (steps 1'-2' above, then the append's apply launch) ----
+extern "C" size_t tg_tcsr_merge_workspace_bytes(int64_t num_entry_old, int64_t n_new, int64_t num_node, int64_t num_node_out) {
+  if (num_entry_old < 0 || n_new < 0 || num_node <= 0 || num_node_out < num_node || num_node_out > 0x7fffffffLL) return 0;
+  const size_t m = 2 * (size_t)n_new;
+  if (m == 0) return 0;
+  if (m <= (size_t)MG_SMALL) return 3 * align16(m * 4) + 256;
+  // two (key, payload) ping-pong pairs serve all three sorts: each pass derives its keys from the payload in place
+  return 5 * align16(m * 4) + radix_sort_scratch_bytes((uint32_t)m) + 256;
+}
+
+extern "C" int tg_tcsr_merge(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src, const int64_t* dst,
+                             const double* ts, const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
+                             int32_t* eid_out, void* ws, size_t ws_bytes, void* stream) {
+  const int bad = append_args(g, num_node_out, n_new, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out);
+  if (bad != TG_OK) return bad;
+  hipStream_t st = as_stream(stream);
+  const uint32_t m = (uint32_t)(2 * n_new);
+  uint32_t *S = nullptr, *J = nullptr, *INS = nullptr;
+  if (m) {  // every workspace check comes before the first launch
+    Carver cv(ws, ws_bytes);
+    if (m <= (uint32_t)MG_SMALL) {
+      S = cv.take<uint32_t>(m);
+      J = cv.take<uint32_t>(m);
+      INS = cv.take<uint32_t>(m);
+      if (!cv.ok) return TG_EWORKSPACE;
+      uint32_t M2 = 128;
+      while (M2 < m) M2 <<= 1;
+      const unsigned threads = std::min<unsigned>(AP_SORT_THREADS, M2 / 2);
+      hipLaunchKernelGGL(k_merge_sort_small, dim3(1), dim3(threads), 0, st, m, M2, src, dst, ts, *g, S, J, INS);
+    } else {
+      uint32_t* k0 = cv.take<uint32_t>(m);
+      uint32_t* v0 = cv.take<uint32_t>(m);
+      uint32_t* k1 = cv.take<uint32_t>(m);
+      uint32_t* v1 = cv.take<uint32_t>(m);
+      INS = cv.take<uint32_t>(m);
+      const size_t sb = radix_sort_scratch_bytes(m);
+      char* scratch = cv.take<char>(sb);
+      if (!cv.ok) return TG_EWORKSPACE;
+      const dim3 grid((unsigned)cdiv(m, 256)), block(256);
+      // least significant key first; every sort is stable, and the payload starts in ascending j
+      hipLaunchKernelGGL(k_merge_keys<0>, grid, block, 0, st, m, src, dst, ts, k0, v0);
+      int rc = radix_sort_pairs(m, 32, k0, v0, k1, v1, scratch, sb, st);
+      if (rc != TG_OK) return rc;
+      hipLaunchKernelGGL(k_merge_keys<1>, grid, block, 0, st, m, src, dst, ts, k0, v0);
+      rc = radix_sort_pairs(m, 32, k0, v0, k1, v1, scratch, sb, st);
+      if (rc != TG_OK) return rc;
+      hipLaunchKernelGGL(k_merge_keys<2>, grid, block, 0, st, m, src, dst, ts, k0, v0);
+      rc = radix_sort_pairs(m, append_key_bits(num_node_out), k0, v0, k1, v1, scratch, sb, st);
+      if (rc != TG_OK) return rc;
+      S = k0;
+      J = v0;
+      hipLaunchKernelGGL(k_merge_ins, grid, block, 0, st, m, S, J, ts, *g, INS);
+    }
+  }
+  return launch_apply("tg_tcsr_merge", g, num_node_out, m, S, J, INS, src, dst, ts, eid, indptr_out, ts_out, nbr_out, eid_out, st);
+}
+
+// The host twin: per row, the old row merged with the node's new entries (taken in ascending j, sorted stably by time);
+// a new entry goes first only where its time is strictly below the old one's.
+extern "C" int tg_tcsr_merge_host(const tg_tcsr* g, int64_t num_node_out, int64_t n_new, const int64_t* src, const int64_t* dst,
+                                  const double* ts, const int64_t* eid, int64_t* indptr_out, double* ts_out, int32_t* nbr_out,
+                                  int32_t* eid_out) {
+  if (!g || n_new < 0 || g->num_node <= 0 || g->num_node > 0x7fffffffLL || g->num_entry < 0 || !g->indptr || !indptr_out)
+    return TG_EINVAL;
+  if (num_node_out < g->num_node || num_node_out > 0x7fffffffLL) return TG_EINVAL;
+  if ((uint64_t)g->num_entry + 2 * (uint64_t)n_new > 0xffffffffull) return TG_EINVAL;
+  const int64_t N0 = g->num_node, N = num_node_out;
+  for (int64_t i = 0; i < n_new; ++i) {
+    if (src[i] < 0 || src[i] >= N || dst[i] < 0 || dst[i] >= N) return TG_EINVAL;
+    if (eid[i] < 0 || eid[i] > 0x7fffffffLL) return TG_EINVAL;
+    if (ts[i] != ts[i]) return TG_EINVAL;  // (a NaN has no place in a row)
+  }
+  std::vector<int64_t> add(N + 1, 0);
+  for (int64_t i = 0; i < n_new; ++i) {
+    add[src[i] + 1]++;
+    add[dst[i] + 1]++;
+  }
+  for (int64_t v = 0; v < N; ++v) add[v + 1] += add[v];  // add[v]: new entries of nodes below v
+  for (int64_t v = 0; v <= N; ++v) indptr_out[v] = g->indptr[std::min(v, N0)] + add[v];
+  std::vector<int64_t> bucket(2 * n_new), cur(add.begin(), add.end() - 1);  // the entries j of every owner, ascending
+  for (int64_t j = 0; j < 2 * n_new; ++j) bucket[cur[(j & 1) ? dst[j >> 1] : src[j >> 1]]++] = j;
+  for (int64_t v = 0; v < N; ++v) {
+    int64_t p = g->indptr[std::min(v, N0)], q = indptr_out[v];
+    const int64_t p1 = g->indptr[std::min(v + 1, N0)];
+    int64_t* b0 = bucket.data() + add[v];
+    int64_t* b1 = bucket.data() + add[v + 1];
+    std::stable_sort(b0, b1, [&](int64_t a, int64_t b) { return ts[a >> 1] < ts[b >> 1]; });
+    while (p < p1 || b0 < b1) {
+      if (b0 < b1 && (p == p1 || ts[*b0 >> 1] < g->ts[p])) {
+        const int64_t j = *b0++, e = j >> 1;
+        ts_out[q] = ts[e];
+        nbr_out[q] = (int32_t)((j & 1) ? src[e] : dst[e]);
+        eid_out[q] = (int32_t)((uint32_t)eid[e] | ((uint32_t)(j & 1) << 31));
+      } else {
+        ts_out[q] = g->ts[p];
+        nbr_out[q] = g->nbr[p];
+        eid_out[q] = g->eid[p];
+        ++p;
+      }
+      ++q;
+    }
+  }
+  return TG_OK;
 }

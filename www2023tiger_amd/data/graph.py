@@ -8,7 +8,8 @@ types, but the per-query Python loop (graph.py:94-146, "Bottleneck! Total time
 The object is immutable after construction, so the collator thread and the main
 thread may sample concurrently (each call allocates its own outputs and runs on
 the calling thread's current stream).  New events are ingested by `extended`, which
-returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was; old entries
+returns a NEW Graph (csrc/tg_append.hip) and leaves its parent as it was; late events - a batch in any order, at any
+times - by `merged`, which does the same (tg_tcsr_merge, same file); old entries
 are dropped by `trimmed` (csrc/tg_trim.hip), which does the same, `without` takes particular nodes and events out
 (csrc/tg_erase.hip), `renumbered` gives the entries the row numbers of a packed edge table (csrc/tg_edge_rows.hip), and
 `compacted` renumbers the node ids densely without the erased ones (csrc/tg_node_compact.hip).
@@ -373,6 +374,36 @@ class Graph:
         return self
 
     # ---- online ingestion -----------------------------------------------------------
+    def _num_node_arg(self, what: str, num_node):
+        """the num_node argument of `extended` / `merged` -> (is it 'auto', the count an int asks for - else this graph's)"""
+        auto = isinstance(num_node, str)
+        if auto and num_node != 'auto':
+            raise ValueError(f"{what}: num_node must be None, an int or 'auto', not {num_node!r}")
+        n_out = self.num_node
+        if num_node is not None and not auto:
+            n_out = operator.index(num_node)
+            if n_out < self.num_node:
+                raise ValueError(f'{what}: num_node = {n_out} is below the graph\'s {self.num_node} (node ids are never released)')
+            if n_out > 0x7FFFFFFF:
+                raise ValueError(f'{what}: node ids must fit in 31 bits')
+        return auto, n_out
+
+    @staticmethod
+    def _batch_arrays(what: str, src, dst, ts, eids):
+        """a batch as given -> (on the device?, four flat contiguous int64 / int64 / float64 / int64 arrays - tensors on the
+        device of a device `src`, numpy arrays otherwise -, the number of events)"""
+        on_dev = torch.is_tensor(src) and src.device.type != 'cpu'
+        if on_dev:
+            batch = tuple(torch.as_tensor(x).to(src.device, dt).contiguous().reshape(-1)
+                          for x, dt in zip((src, dst, ts, eids), (torch.int64, torch.int64, torch.float64, torch.int64)))
+        else:
+            np_of = lambda x, dt: np.ascontiguousarray(x.detach().numpy() if torch.is_tensor(x) else x, dtype=dt).reshape(-1)
+            batch = (np_of(src, np.int64), np_of(dst, np.int64), np_of(ts, np.float64), np_of(eids, np.int64))
+        n = int(batch[0].shape[0])
+        if any(int(b.shape[0]) != n for b in batch):
+            raise ValueError(f'{what}: src, dst, ts and eids must have one entry per event')
+        return on_dev, batch, n
+
     def extended(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None, num_node=None) -> 'Graph':
         """A NEW Graph over this graph's events followed by the batch (src, dst, ts, eids) - what `from_arrays` over the
         concatenated stream builds, bit for bit (tg_tcsr_append; graph.py:11-42,226-241 has no counterpart: the reference
@@ -393,26 +424,8 @@ class Graph:
         trusted there).  The child is what `from_arrays(..., max_node_id=num_node - 1)` over the concatenated stream
         builds, bit for bit; `trimmed`, `renumbered` and later `extended` calls keep its num_node.  The default None keeps
         num_node and refuses an id at or beyond it.  ValueError: an int below self.num_node or above 2^31 - 1."""
-        auto = isinstance(num_node, str)
-        if auto and num_node != 'auto':
-            raise ValueError(f"extended: num_node must be None, an int or 'auto', not {num_node!r}")
-        n_out = self.num_node
-        if num_node is not None and not auto:
-            n_out = operator.index(num_node)
-            if n_out < self.num_node:
-                raise ValueError(f'extended: num_node = {n_out} is below the graph\'s {self.num_node} (node ids are never released)')
-            if n_out > 0x7FFFFFFF:
-                raise ValueError('extended: node ids must fit in 31 bits')
-        on_dev = torch.is_tensor(src) and src.device.type != 'cpu'
-        if on_dev:
-            batch = tuple(torch.as_tensor(x).to(src.device, dt).contiguous().reshape(-1)
-                          for x, dt in zip((src, dst, ts, eids), (torch.int64, torch.int64, torch.float64, torch.int64)))
-        else:
-            np_of = lambda x, dt: np.ascontiguousarray(x.detach().numpy() if torch.is_tensor(x) else x, dtype=dt).reshape(-1)
-            batch = (np_of(src, np.int64), np_of(dst, np.int64), np_of(ts, np.float64), np_of(eids, np.int64))
-        n = int(batch[0].shape[0])
-        if any(int(b.shape[0]) != n for b in batch):
-            raise ValueError('extended: src, dst, ts and eids must have one entry per event')
+        auto, n_out = self._num_node_arg('extended', num_node)
+        on_dev, batch, n = self._batch_arrays('extended', src, dst, ts, eids)
         if auto and n and on_dev and not validate:
             raise ValueError("extended: num_node='auto' takes the largest id from the validation's read-back; with "
                              'validate=False pass an int')
@@ -482,6 +495,82 @@ class Graph:
         ones own empty rows).  This graph stays valid and unchanged."""
         e = np.empty(0, dtype=np.int64)
         return self.extended(e, e, np.empty(0, dtype=np.float64), e, num_node=operator.index(num_node))
+
+    # ---- late events ------------------------------------------------------------------
+    def merged(self, src, dst, ts, eids, *, validate: bool = True, eid_rows: Optional[int] = None, num_node=None) -> 'Graph':
+        """A NEW Graph over this graph's entries and the batch (src, dst, ts, eids), which may be in ANY order and hold ANY
+        non-NaN times - before, inside or after this graph's range (tg_tcsr_merge; graph.py:11-42,226-241 has no
+        counterpart: the reference sorts its lists once, over the whole stream).  Every row is the stable merge of the old
+        row with the node's new entries sorted stably by time: at equal times the old entries first, then the new ones in
+        event order (seen from src before seen from dst) - what `from_arrays` over [this graph's events | batch] builds, bit
+        for bit, when this graph is the T-CSR of an event list, and the row-wise definition when it is not (a trimmed,
+        erased or compacted parent).  A batch `extended` accepts gives the arrays `extended` gives.
+        This graph stays valid and unchanged, and the child holds no reference to it: it adopts its arrays as a root of
+        its own, as the children of `trimmed` / `without` do.  Inputs, validate, eid_rows and num_node (None / int / 'auto')
+        are those of `extended`; a device-resident parent is merged on the device, on the current stream with
+        allocator-owned buffers and no synchronisation beyond the validation's one read-back; a host-only parent takes the
+        host twin.  strategy / seed / alpha / device carry over, the child shares `rng` and the device MT19937 state, has
+        a `serial` of its own, and its latest event time is max(this graph's, the batch's).  On the host path with a known
+        event list `_events` is the concatenation, and the time-ordered flag survives only if the concatenation really is
+        ordered (the device builder's contract); on the device path `_events` is None and the flag is cleared.
+        ValueError before anything is launched: a NaN time, ids outside [0, num_node), eids beyond 31 bits or beyond
+        eid_rows, arrays of unequal length, 2^32 entries or more.  NOT refused: disorder, going back in time."""
+        from ..hip_ops import tcsr_merge, tcsr_merge_host
+        auto, n_out = self._num_node_arg('merged', num_node)
+        on_dev, batch, n = self._batch_arrays('merged', src, dst, ts, eids)
+        if auto and n and on_dev and not validate:
+            raise ValueError("merged: num_node='auto' takes the largest id from the validation's read-back; with "
+                             'validate=False pass an int')
+        t_last = self._t_last
+        if n and (validate or not on_dev):
+            if torch.is_tensor(t_last):
+                t_last = self._t_last = float(t_last)
+            s, d, t, e = batch
+            if on_dev:  # a handful of reductions and the one read-back (ids and eids are exact in float64 below 2^53)
+                ints = torch.stack(torch.aminmax(torch.cat([s, d])) + torch.aminmax(e))
+                st = torch.cat([(t != t).any().reshape(1).double(), t.max().reshape(1), ints.double()]).tolist()
+            else:
+                st = [float(np.isnan(t).any()), t.max(), min(s.min(), d.min()), max(s.max(), d.max()), e.min(), e.max()]
+            if st[0]:
+                raise ValueError('merged: a NaN time has no place in a row')
+            if auto:
+                if st[3] > 0x7FFFFFFE:
+                    raise ValueError('merged: node ids must fit in 31 bits')
+                n_out = max(self.num_node, int(st[3]) + 1)
+            if st[2] < 0 or st[3] >= n_out:
+                if num_node is not None:
+                    raise ValueError(f'node ids must lie in [0, num_node) (num_node = {n_out})')
+                raise ValueError('node ids must lie in [0, num_node) (num_node does not grow: the model\'s tables are sized by it)')
+            if st[4] < 0 or st[5] > 0x7FFFFFFF:
+                raise ValueError('edge ids must fit in 31 bits')
+            if eid_rows is not None and st[5] >= eid_rows:
+                raise ValueError(f'edge id {int(st[5])} is no row of the edge table ({eid_rows} rows)')
+            t_last = max(t_last, float(st[1]))
+        elif n:  # trusted device batch: the latest time stays on the device until a validation asks for it
+            t_last = torch.maximum(torch.as_tensor(t_last, dtype=torch.float64, device=batch[2].device), batch[2].max())
+        if self._dev is not None:
+            old_entries = self._dev[1].numel()
+        else:
+            old_entries = len(self._host_tcsr()[1])
+        if old_entries + 2 * n >= 2 ** 32:
+            raise ValueError('merged: the device T-CSR holds fewer than 2^32 entries')
+        child = self._child(n_out)
+        child._t_last = t_last
+        if self._dev is not None:  # device-resident parent: merge on the device
+            dev = self._dev[0].device
+            d_batch = batch if on_dev and batch[0].device == dev else tuple(torch.as_tensor(b).to(dev) for b in batch)
+            child._time_ordered = self._time_ordered and n == 0
+            return child._adopt_device(tcsr_merge(self, d_batch, n_out), self)
+        if on_dev:
+            batch = tuple(np.ascontiguousarray(b.cpu().numpy()) for b in batch)
+        out = tcsr_merge_host(self, batch, n_out)
+        ev = self._root.events
+        if ev is not None:
+            ev = tuple(np.concatenate([a, b]) for a, b in zip(ev, batch))
+            child._time_ordered = bool(self._time_ordered and np.all(ev[2][1:] >= ev[2][:-1]))
+        else:
+            child._time_ordered = self._time_ordered and n == 0
+        return child._adopt_host(out, ev, self)
 
     # ---- sliding-window expiry --------------------------------------------------------
     def trimmed(self, before: Optional[float] = None, keep_last: Optional[int] = None) -> 'Graph':

@@ -734,6 +734,40 @@ def tcsr_compacted_host(graph, name: str, twin):
     return (out[0],) + tuple(a[:kept.value].copy() for a in out[1:])  # (copies: the full-size arrays die)
 
 
+# ---- late events (tg_tcsr_merge and its host twin) ----------------------------------------------------------------------------
+def tcsr_merge(graph, batch, num_node_out: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The arrays of a device-resident `graph` merged with a batch in ANY order and with ANY non-NaN times (tiger_hip.h:
+    tg_tcsr_merge) -> (indptr int64 [num_node_out + 1], ts float64, nbr int32, eid int32), on the current stream of the
+    graph's device with allocator-owned buffers, no synchronisation.  batch = (src, dst, ts, eids): contiguous int64 /
+    int64 / float64 / int64 tensors of one length ON THAT DEVICE, trusted as they are (Graph.merged validates)."""
+    if graph._dev is None:
+        graph._tensors()
+    dev = graph._dev[0].device
+    g, n = graph.tcsr, int(batch[0].numel())
+    n_out = graph.num_node if num_node_out is None else int(num_node_out)
+    want = (torch.int64, torch.int64, torch.float64, torch.int64)
+    if any(b.dtype != dt or b.device != dev or b.numel() != n or not b.is_contiguous() for b, dt in zip(batch, want)):
+        raise ValueError(f'tcsr_merge: the batch is four contiguous tensors (int64, int64, float64, int64) of one length on {dev}')
+    out = tcsr_arrays(n_out, g.num_entry + 2 * n, dev)
+    nbytes = int(lib.tg_tcsr_merge_workspace_bytes(g.num_entry, n, g.num_node, n_out))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tg_tcsr_merge(C_.byref(g), n_out, n, *(ptr(b) for b in batch), *(ptr(t) for t in out), ptr(ws), nbytes,
+                                stream_ptr(dev)), 'tg_tcsr_merge')
+    return out
+
+
+def tcsr_merge_host(graph, batch, num_node_out: Optional[int] = None):
+    """The host twin (tiger_hip.h: tg_tcsr_merge_host) over the graph's host arrays and a batch of contiguous numpy arrays
+    (int64, int64, float64, int64) -> numpy (indptr, ts, nbr, eid).  Ids, eids and NaN times are checked by the twin."""
+    g, h = _graph_struct('tcsr_merge_host', graph, torch.device('cpu'))
+    n = len(batch[0])
+    n_out = graph.num_node if num_node_out is None else int(num_node_out)
+    out = tcsr_arrays(n_out, len(h[1]) + 2 * n)
+    check(lib.tg_tcsr_merge_host(C_.byref(g), n_out, n, *(ptr(b) for b in batch), *(ptr(a) for a in out)), 'tg_tcsr_merge_host')
+    return out
+
+
 # ---- erasing nodes and retracting events (tg_tcsr_erase_plan / _apply and their host twin) ----------------------------------
 def host_bitmap(ids, n_ids: int):
     """The bitmap of `new_bitmap` + `bitmap_mark` over n_ids ids as a numpy int64 array (the host twins' format); ids at or

@@ -1666,6 +1666,81 @@ class TIGE(nn.Module):
             src, dst, ts, eids = new_graph.last_batch
         return self.stream_step(src, dst, dst if neg is None else neg, ts, eids, want_prev=want_prev)
 
+    @torch.no_grad()
+    def observe_late(self, src, dst, ts, eids, *, efeats=None, num_node=None, nfeats=None):
+        """Admit LATE events: a batch in any order whose times may lie before, inside or after what the model has seen (a
+        client that was offline, a slow partition of a message bus, a settlement booked hours after the fact) -> the new
+        graph.  Their edge-feature rows (efeats [n, d_e], for a model with an edge table) are appended to the table and
+        the graph is replaced by `graph.merged(...)` through the setter (the restarter follows, snapshot stamps go stale,
+        a prefetched collate part is dropped as for `forget`): every event stands in the rows of its two endpoints at the
+        place its time gives it.  num_node / nfeats: as in `observe` - new node ids are admitted with the batch, the
+        per-node tables grow (`grow_nodes`).  NOTHING IS STREAMED: both memories and the mailbox are not touched.
+        THE LIMITS:
+          * A late event changes what is READ from the graph from now on: sampled neighbours, the sequence restarter's
+            histories, `exclude_seen`, `walk_candidates`, `trending`, `fill_candidates`.
+          * It cannot be replayed into the recurrent state of its endpoints: that state has already consumed later
+            events, and a GRU cannot be rewound.  Memories and pending mail are what they were.
+          * Batches streamed before the call did not see the event - their embeddings and the state they left are not
+            recomputed.
+          * The caller's duties are those of `forget`: captured device graphs and resident evaluation runs built before
+            the call read the old graph (and, after growth, the old tables) - rebuild them; CatalogueSnapshots held from
+            before are stale.
+        Refused before anything changes: a partitioned model, training mode, a stream capture in progress when tables
+        would grow, efeats of another shape, and what `Graph.merged` refuses (a NaN time, ids outside [0, num_node), an
+        eid that is no row of the edge table after the append, arrays of unequal length).  `observe` keeps refusing a
+        batch that starts before the latest event: the two do not overlap."""
+        self._refuse_partitioned('observe_late')
+        if self.training:
+            raise RuntimeError('observe_late: late events are admitted in eval() mode (the streaming state of a served model)')
+        if num_node is None and nfeats is not None:
+            raise ValueError('observe_late: nfeats are the feature rows of newly admitted node ids (pass num_node)')
+        fg = self.raw_feat_getter
+        n = len(src)
+        if efeats is not None and fg.efeats is not None:
+            efeats = torch.as_tensor(efeats)
+            if efeats.dim() != 2 or efeats.shape[0] != n or efeats.shape[1] != fg.efeats.shape[1]:
+                raise ValueError(f'observe_late: efeats {tuple(efeats.shape)} for {n} events of width {fg.efeats.shape[1]}')
+        grows = efeats is not None and fg.efeats is not None and n > 0
+        if grows and self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('observe_late: tables cannot grow while a stream is being captured into a graph')
+        rows = None if fg.efeats is None else fg.efeats.shape[0] + (n if efeats is not None else 0)
+        # (validates, the eids against the table's rows included, before any launch; nothing has changed if it raises)
+        if num_node is None:
+            new_graph = self.graph.merged(src, dst, ts, eids, eid_rows=rows)
+        else:
+            new_graph = self.graph.merged(src, dst, ts, eids, eid_rows=rows, num_node=num_node)
+            nfeats = self._grow_refusals('observe_late', max(new_graph.num_node, self.n_nodes), nfeats, None)
+        if efeats is not None and fg.efeats is not None and fg.append_edge_rows(efeats):
+            self.invalidate_struct()
+        if new_graph.num_node > self.n_nodes:
+            self._grow(new_graph.num_node, nfeats, None, new_graph)  # (swaps the graph in with the tables)
+        else:
+            self.graph = new_graph
+        return self.graph
+
+    def observe_late_keys(self, idmap, src_keys, dst_keys, ts, eids, *, efeats=None, nfeats=None):
+        """`observe_late` for a stream that names its nodes by external int64 keys: the batch's keys are assigned dense ids
+        by `idmap` in EVENT order, exactly as `observe_keys` assigns them (a key the map does not hold gets the next id, or
+        a recycled one; nfeats may be a callable handed the admitted keys), and the batch is merged with num_node =
+        max(idmap.size, n_nodes) -> the new graph.  Refusals and their order are those of `observe_keys`: what
+        `observe_late` refuses about the batch is refused AFTER the assignment - the model is untouched, the keys stay."""
+        src_keys = self._device_keys('observe_late_keys', 'src_keys', src_keys).reshape(-1)
+        dst_keys = self._device_keys('observe_late_keys', 'dst_keys', dst_keys).reshape(-1)
+        if src_keys.numel() != dst_keys.numel():
+            raise ValueError('observe_late_keys: src_keys and dst_keys must have one entry per event')
+        keys = torch.stack([src_keys, dst_keys], 1).reshape(-1)  # event order
+        self._keyed_refusals('observe_late_keys', idmap, keys)
+        if idmap.n_free == 0:
+            ids = idmap.assign(keys).view(-1, 2).long()
+            num_node = max(idmap.size, self.n_nodes)
+            if callable(nfeats):
+                nfeats = nfeats(idmap.key_of[self.n_nodes:num_node])
+        else:
+            ids, num_node = self._admit_recycled('observe_late_keys', idmap, keys, nfeats)
+            ids, nfeats = ids.view(-1, 2).long(), None
+        return self.observe_late(ids[:, 0].contiguous(), ids[:, 1].contiguous(), torch.as_tensor(ts).to(self.device),
+                                 torch.as_tensor(eids).to(self.device), efeats=efeats, num_node=num_node, nfeats=nfeats)
+
     def _grow_refusals(self, what: str, num_node, nfeats, reserve):
         """everything grow_nodes refuses, before anything has changed -> the feature rows of the new ids (a tensor, or the
         count of zero rows)"""

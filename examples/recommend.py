@@ -63,6 +63,12 @@ just loaded a checkpoint and a graph can do before it has seen the stream.
 is scored as of the batch's start - an approximation of the exact per-pair protocol for the queries later in the batch -
 and the line printed says which protocol ran.
 
+--online --snapshot --refresh [--max_age S] serves the online replay from ONE catalogue snapshot that is kept current
+incrementally: change tracking is switched on (`TIGE.track_changes`), the snapshot is taken once before the replay, every
+batch is ranked on it, and after every `observe` `TIGE.refresh_catalogue(snap, t_batch_end, max_age=S)` re-embeds only the
+rows that read a node the batch changed (or that are older than S) - `n_dirty / C` is printed per batch.  Items are scored
+as of their last refresh, the serving approximation of --snapshot, so no offline replay is made.
+
 --walk C [--fanout 10,10,10] retrieves before it ranks: instead of all destination nodes, every event's candidates are the
 C best-connected ends of walks over the graph from its source at its own time (`TIGE.recommend_walk`: `hip_ops.
 walk_candidates`, levels 1 and 3 of a three-level walk by default, then `recommend` over those ids; with --exclude_seen the
@@ -205,12 +211,13 @@ class _Keyed:
         return self.model.n_nodes - n_old
 
 
-def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None, first=0, stop=None, keyed=None):
+def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=None, first=0, stop=None, keyed=None,
+            snapshot=None):
     """recommend, then `ingest`, batch by batch over the test split -> (ids [n_test, k], dict of the metrics of
     eval_recommendation: position of the true destination in its list, folded the same way).  known: a callable -> the
     (catalogue, col_of) of the batch, for a model whose node ids grow on the way (run_online(grow=True)).  first / stop: the
     events [first, stop) of the split alone (a replay that was saved, or will be).  keyed (a _Keyed): the lists are asked
-    for and returned as keys"""
+    for and returned as keys.  snapshot: a callable -> the catalogue snapshot to rank on instead of embedding the items"""
     dev = model.device
     ids, pos = [], []
     place = torch.arange(k, device=dev)
@@ -225,7 +232,8 @@ def _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=N
             if known is not None:
                 catalogue, col_of = known()
                 q = q.clamp(max=model.n_nodes - 1)   # a source nobody has seen yet is asked for as the last id (and scores as a miss)
-            i, _, _ = model.recommend(q, t, catalogue, k, exclude_seen=exclude_seen, col_of=col_of)
+            i, _, _ = model.recommend(q, t, catalogue if snapshot is None else snapshot(), k, exclude_seen=exclude_seen,
+                                      col_of=col_of)
             hit = (i == d[:, None]) & (i != 0)
             if known is not None:
                 hit &= torch.from_numpy(src).to(dev)[:, None] < model.n_nodes
@@ -244,7 +252,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
                erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False,
-               churn=None, compact_at=None, late=None, late_by=1):
+               churn=None, compact_at=None, late=None, late_by=1, refresh=False, max_age=None):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -289,9 +297,19 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     histories, exclude_seen - from then on and is never streamed into the memories, so the lists differ from the offline
     replay's and none is made.  The replay prints, and its metrics carry, 'late': the number of late events merged; the
     final graph is asserted equal to the graph over the whole stream: indptr and ts exactly, nbr up to the order among
-    entries of one node at one time (a late entry stands behind the on-time ones of its time)."""
+    entries of one node at one time (a late entry stands behind the on-time ones of its time).
+    refresh (the plain online replay only): ONE catalogue snapshot, taken before the replay with change tracking on, serves
+    every batch and is brought up to date after every `observe` by `refresh_catalogue(snap, t_batch_end, max_age=max_age)`;
+    the replay prints `n_dirty / C` per batch and its metrics carry 'refreshed': (n_dirty, n_by_age) per batch.  Items are
+    scored as of their last refresh, so the lists differ from the offline replay's and none is made."""
     from www2023tiger_amd.data.graph import Graph
     forgetting = window is not None or keep_last is not None
+    if refresh:
+        if keyed or grow or forgetting or late is not None or erase_nodes is not None or retract_eids is not None or save_state \
+                or load_state or save_after is not None:
+            raise ValueError('refresh: the plain online replay only (no --keyed, --grow, --window / --keep_last, --late, erase, '
+                             'save / load)')
+        offline = False
     if late is not None:
         if not 0 <= float(late) < 1:
             raise ValueError(f'late = {late} is a fraction of every batch in [0, 1)')
@@ -462,8 +480,20 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                 held.append((b + int(late_by), s[m], d[m], t[m], e[m]))
             merge_due(b)
         ingest = observe_and_forget if forgetting else (observe if late is None else observe_some_late)
+        snap, refreshed = [None], []
+        if refresh:   # the tracker first: the snapshot remembers the tracker's epoch
+            model.track_changes()
+            snap[0] = model.embed_catalogue(catalogue, float(full_data.ts[n_seen - 1]))
+
+            def ingest(s, d, t, e):
+                observe(s, d, t, e)
+                snap[0] = model.refresh_catalogue(snap[0], float(t[-1]), max_age=max_age)
+                refreshed.append(model.last_refreshed)
+                if verbose:
+                    print(f'batch {len(refreshed) - 1}: refreshed {refreshed[-1][0]} / {len(snap[0])} rows '
+                          f'({refreshed[-1][1]} by age alone)')
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=known if grow else None,
-                                 first=first, stop=stop, keyed=keyed or None)
+                                 first=first, stop=stop, keyed=keyed or None, snapshot=(lambda: snap[0]) if refresh else None)
         if late is not None:
             merge_due(float('inf'))
             if verbose:
@@ -501,6 +531,8 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         online = dict(online, erased=erased)
     if late is not None:
         online = dict(online, late=n_late[0])
+    if refresh:
+        online = dict(online, refreshed=refreshed)
     if forgetting:
         online = dict(online, forgot=forgot)
         if release_rows:
@@ -599,6 +631,9 @@ if __name__ == '__main__':
     ap.add_argument('--late', type=float, default=None, metavar='FRACTION', help='--online: hold a seeded fraction of every '
                     'test batch back and hand it to TIGE.observe_late --late_by batches later; prints the late events merged')
     ap.add_argument('--late_by', type=int, default=1, metavar='BATCHES', help='--late: how many batches later (default 1)')
+    ap.add_argument('--refresh', action='store_true', help='--online --snapshot: serve the replay from ONE catalogue snapshot, '
+                    'refreshed incrementally after every observe (TIGE.track_changes, TIGE.refresh_catalogue)')
+    ap.add_argument('--max_age', type=float, default=None, metavar='S', help='--refresh: also re-embed rows older than S time units')
     ap.add_argument('--walk', type=int, default=None, metavar='C', help='retrieve C walk candidates per event from the graph '
                     '(TIGE.recommend_walk) instead of ranking all destination nodes; prints recall@C')
     ap.add_argument('--fanout', default='10,10,10', help='--walk: entries followed per node at each level, e.g. 10,10,10')
@@ -613,6 +648,8 @@ if __name__ == '__main__':
         print(f"cold: HitRate@{a.k} {m['hit_rate']:.4f}  NDCG@{a.k} {m['ndcg']:.4f}  MRR@{a.k} {m['mrr_at_k']:.4f}  "
               f"({m['n_events']} events, {sum(restarted)} restarts over {len(restarted)} batches)")
         sys.exit(0)
+    if a.refresh and not (a.online and a.snapshot):
+        ap.error('--refresh keeps the snapshot of an online replay current: it needs --online --snapshot')
     if a.online:
         for name, m in zip(('online ', 'offline'), run_online(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen,
                                                               seed=a.seed, bs=a.bs, restarter_type=a.restarter_type,
@@ -623,7 +660,8 @@ if __name__ == '__main__':
                                                               else np.load(a.retract_eids), save_state=a.save_state,
                                                               save_after=a.save_after, load_state=a.load_state,
                                                               keyed=a.keyed, churn=a.churn, compact_at=a.compact_at,
-                                                              late=a.late, late_by=a.late_by)):
+                                                              late=a.late, late_by=a.late_by, refresh=a.refresh,
+                                                              max_age=a.max_age)):
             if m is None:
                 continue
             if a.keyed and 'ids' in m:

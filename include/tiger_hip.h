@@ -1523,6 +1523,61 @@ int tg_involved_list_host(const tg_tcsr* g, int64_t Q, const int64_t* nids_host,
                           int32_t* count_host, float* tmin_host);
 
 /* ------------------------------------------------------------------------- */
+/* Incremental catalogue refresh (tg_snapshot_refresh.hip; no reference       */
+/* counterpart - DESIGN 7.22): which rows of a catalogue snapshot read a node  */
+/* that changed, and the merge of re-embedded rows into a new snapshot         */
+/* ------------------------------------------------------------------------- */
+/* tg_catalogue_dirty.  Row j of a catalogue (ids[j], embedded at t_row[j]; t_row == NULL: every row at t_all) is dirty iff
+ *   (1) a node of involved(ids[j], t_row[j]) - the set of tg_involved_list above for that one query: same strategy, K,
+ *       n_layers, strict float64 cut, float32 hop-2 times and padding id 0 - has its bit set in `touched` (a bitmap over
+ *       g->num_node ids), or
+ *   (2) t_new - t_row[j] > max_age (strict float64; max_age NaN: rule off).
+ * Outputs: rank int32 [C] - a dirty row's position among the dirty rows in ascending row order, -1 for a clean row;
+ * cols int32 [C] - cols[0 .. n_dirty) = the dirty rows, ascending (the rest is not written); count int32 [2] = n_dirty,
+ * and the rows that are dirty by rule (2) alone.  Nothing else is written; no model state is read.
+ * Flag pass: one wavefront per row walks the enumeration of tg_involved_list (one shared template, tg_involved_visit.h)
+ * with a visitor that tests bits and leaves the row at the first hit; one byte per row.  Compaction: two launches over
+ * tiles of 2 048 rows (tile totals; each workgroup then sums the totals in front of it).  No atomics, no workgroup waits
+ * for another: the result does not depend on the launch geometry.  Three plain launches on `stream`.
+ * ws: tg_catalogue_dirty_workspace_bytes(C) bytes (0 for C outside [0, 2^31)), 16-byte aligned: one byte per row + 8
+ * bytes per tile - no term in C K.  TG_EUNSUPPORTED for strategy 2.  TG_EINVAL: another strategy outside {0, 1}, K
+ * outside [1, TG_INVOLVED_MAX_K], n_layers outside {1, 2}, C outside [0, 2^31), a NaN t_new or t_all, a negative
+ * max_age, a null pointer, a misaligned workspace.  TG_EWORKSPACE: a missing or short workspace.  All before anything is
+ * launched.  C == 0: count = {0, 0} and nothing else.  ids[j] must lie in [0, num_node): the device entry treats one
+ * outside as a node without entries and without a bit; the host twin returns TG_EINVAL. */
+size_t tg_catalogue_dirty_workspace_bytes(int64_t C);
+int tg_catalogue_dirty(const tg_tcsr* g, int64_t C, const int64_t* ids, const double* t_row, double t_all, int32_t K,
+                       int32_t n_layers, int32_t strategy, const uint64_t* touched, double t_new, double max_age,
+                       int32_t* rank, int32_t* cols, int32_t* count, void* ws, size_t ws_bytes, void* stream);
+/* The same on the host (g and every array HOST pointers; plain C++); identical outputs. */
+int tg_catalogue_dirty_host(const tg_tcsr* g, int64_t C, const int64_t* ids_host, const double* t_row_host, double t_all,
+                            int32_t K, int32_t n_layers, int32_t strategy, const uint64_t* touched_host, double t_new,
+                            double max_age, int32_t* rank_host, int32_t* cols_host, int32_t* count_host);
+/* tg_catalogue_merge: the row tables of the refreshed snapshot in ONE launch, every byte read once and written once:
+ *   x_out[j] = rank[j] >= 0 ? x_new[rank[j]] : x_old[j]   for x = h float32 [C, d], P float32 [C, d] (P_old, P_new, P_out
+ *   all NULL: no P) and nb int64 [C, K] (all NULL: no nb);  t_out[j] = rank[j] >= 0 ? t_new : (t_old ? t_old[j] : t_old_all).
+ * x_new holds n_new rows; a rank at or beyond n_new keeps the old row (the host twin returns TG_EINVAL).  The float rows
+ * move as 16-byte words: d % 4 == 0 and 16-byte aligned tables.  Rows past C are never stored.  Outputs must not overlap
+ * inputs.  TG_EINVAL before the launch: C outside [0, 2^31), n_new outside [0, C], d < 4 or d % 4 != 0, K < 0, a null
+ * rank / h / t_out pointer, a P or nb triple that is partly NULL, K == 0 with an nb triple, a misaligned float table.
+ * C == 0: nothing is launched. */
+int tg_catalogue_merge(int64_t C, int64_t n_new, int32_t d, int32_t K, const int32_t* rank, const float* h_old,
+                       const float* h_new, float* h_out, const float* P_old, const float* P_new, float* P_out,
+                       const int64_t* nb_old, const int64_t* nb_new, int64_t* nb_out, const double* t_old, double t_old_all,
+                       double t_new, double* t_out, void* stream);
+int tg_catalogue_merge_host(int64_t C, int64_t n_new, int32_t d, int32_t K, const int32_t* rank, const float* h_old,
+                            const float* h_new, float* h_out, const float* P_old, const float* P_new, float* P_out,
+                            const int64_t* nb_old, const int64_t* nb_new, int64_t* nb_out, const double* t_old,
+                            double t_old_all, double t_new, double* t_out);
+/* tg_bitmap_mark_degree_diff: bits |= {v : len_a(v) != len_b(v)}, len_x(v) = x->indptr[v + 1] - x->indptr[v] for v <
+ * x->num_node and 0 beyond - every node whose T-CSR row length differs between two graphs (only indptr is read).  bits: a
+ * bitmap of at least tg_bitmap_words(max(a->num_node, b->num_node)) words.  One launch; every word has one owner (a
+ * wavefront ballots its 64 ids, one lane stores): plain stores, no atomics.  TG_EINVAL: a null pointer, a node count
+ * outside [1, 2^31), bit_words too small. */
+int tg_bitmap_mark_degree_diff(const tg_tcsr* a, const tg_tcsr* b, uint64_t* bits, int64_t bit_words, void* stream);
+int tg_bitmap_mark_degree_diff_host(const tg_tcsr* a, const tg_tcsr* b, uint64_t* bits_host, int64_t bit_words);
+
+/* ------------------------------------------------------------------------- */
 /* Walk candidates (no reference counterpart): per-query candidate generation */
 /* over the T-CSR - a source's own recent neighbours and the ends of its       */
 /* src -> nbr -> nbr -> nbr walks, counted, filtered, ordered and truncated    */

@@ -367,6 +367,17 @@ SIGNATURES = {
     'tg_involved_list_workspace_bytes': (sz, [i64, i64, i32, i32]),
     'tg_involved_list': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, sz, vp]),
     'tg_involved_list_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp]),
+    'tg_catalogue_dirty_workspace_bytes': (sz, [i64]),
+    'tg_catalogue_dirty': (C.c_int, [P(TgTcsr), i64, vp, vp, C.c_double, i32, i32, i32, vp, C.c_double, C.c_double, vp, vp, vp,
+                                     vp, sz, vp]),
+    'tg_catalogue_dirty_host': (C.c_int, [P(TgTcsr), i64, vp, vp, C.c_double, i32, i32, i32, vp, C.c_double, C.c_double, vp, vp,
+                                          vp]),
+    'tg_catalogue_merge': (C.c_int, [i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
+                                     vp, vp]),
+    'tg_catalogue_merge_host': (C.c_int, [i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double,
+                                          C.c_double, vp]),
+    'tg_bitmap_mark_degree_diff': (C.c_int, [P(TgTcsr), P(TgTcsr), vp, i64, vp]),
+    'tg_bitmap_mark_degree_diff_host': (C.c_int, [P(TgTcsr), P(TgTcsr), vp, i64]),
     'tg_walk_candidates_lds_bytes': (sz, [i32, vp, i32]),
     'tg_walk_candidates': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     'tg_walk_candidates_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),

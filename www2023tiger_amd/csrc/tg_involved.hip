@@ -6,7 +6,8 @@
 // involved = {nids[q]}  +  the K sampler slots of every (nids[q], ts[q])  (padding id 0 included, as the sampler marks it)
 //            +  (two layers) the K slots of every hop-1 slot at the slot's float32 time (padding slots: node 0 at time 0).
 //
-// Launch 1 (k_involved_edges / k_involved_nodes), one wavefront per query: the cut is prefix_end_group (strict float64),
+// Launch 1 (k_involved_edges / k_involved_nodes), one wavefront per query; the enumeration itself lives in
+// tg_involved_visit.h (shared with tg_snapshot_refresh.hip): the cut is prefix_end_group (strict float64),
 // lane j holds hop-1 slot j in registers, the wavefront flags its query and its slots (byte flags, plain stores: every
 // writer stores the same value) and then walks its own slots and flags their tails.  Nothing is written per slot.  All
 // padding slots of a query are the same hop-2 query, searched once.  The batch's earliest time travels as the
@@ -20,7 +21,7 @@
 #include <cmath>
 #include <vector>
 
-#include "tg_sample.h"
+#include "tg_involved_visit.h"
 
 namespace tg {
 
@@ -51,85 +52,38 @@ __device__ __forceinline__ void involved_tmin(const InvolvedArgs& a, float tmin)
   }
 }
 
-// recent_edges (graph.py:117-127).  The second hop is searched by G lanes per slot, 64 / G slots at a time (K <= G).
+// the marking visitor of tg_involved_visit.h: a byte per node, never stops
+struct InvolvedMarker {
+  const InvolvedArgs& a;
+  __device__ __forceinline__ void visit(int64_t v) const { involved_mark(a, v); }
+  __device__ __forceinline__ constexpr bool stop() const { return false; }
+};
+
+// recent_edges: involved_visit_edges<G>, one wavefront per query (K <= G)
 template <int G>
 __global__ void __launch_bounds__(256) k_involved_edges(InvolvedArgs a) {
-  constexpr int SPW = TG_WAVE / G;
-  const tg_tcsr& g = a.g;
-  const int lane = lane_id(), sub = lane % G, grp = lane / G;
-  const int K = a.K;
+  const int lane = lane_id();
+  InvolvedMarker vis{a};
   float tmin = INFINITY;
   for (int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < a.Q; q += (int64_t)gridDim.x * 4) {
-    const int64_t nid = a.nids[q];
     const double t = a.ts[q];
     tmin = fminf(tmin, (float)t);
-    int64_t start;
-    const int64_t end = prefix_end_group<64>(g, nid, t, &start, lane);
-    // lane j: slot j of the query (left padded: node 0 at time 0); the slot time is the sampler's float32
-    int64_t nb = 0;
-    double tt = 0.0;
-    const int64_t p = end - K + lane;
-    if (lane < K && p >= start) {
-      nb = g.nbr[p];
-      tt = (double)(float)g.ts[p];
-    }
-    if (lane < K) involved_mark(a, nb);
-    if (lane == 0) involved_mark(a, nid);
-    if (!a.two) continue;  // (wave-uniform)
-    const int64_t n1 = min((int64_t)K, end - start);
-    for (int j = n1 < K ? (int)(K - n1 - 1) : 0; j < K; j += SPW) {  // the last padding slot stands for all of them
-      const int s = j + grp;
-      int64_t nb2 = __shfl(nb, s < K ? s : K - 1, TG_WAVE);
-      const double t2 = __shfl(tt, s < K ? s : K - 1, TG_WAVE);
-      if (s >= K) nb2 = -1;  // a group without a slot: no entries
-      int64_t st2;
-      const int64_t e2 = prefix_end_group<G>(g, nb2, t2, &st2, sub);
-      for (int i = sub; i < K; i += G) {
-        const int64_t p2 = e2 - K + i;
-        if (s < K) involved_mark(a, p2 >= st2 ? (int64_t)g.nbr[p2] : (int64_t)0);
-      }
-    }
+    involved_visit_edges<G>(a.g, a.nids[q], t, a.K, a.two != 0, lane, vis);
   }
   involved_tmin(a, tmin);
 }
 
-// recent_nodes (graph.py:129-143): the scan of k_sample_recent_nodes (tg_sample.h), hop-1 slots parked in LDS
+// recent_nodes: involved_visit_nodes, hop-1 slots parked in LDS
 __global__ void __launch_bounds__(256) k_involved_nodes(InvolvedArgs a) {
   __shared__ int s_new[4][TG_WAVE];
   __shared__ float s_t[4][TG_WAVE];
-  const tg_tcsr& g = a.g;
   const int lane = lane_id(), wv = threadIdx.x >> 6;
-  const int K = a.K;
+  InvolvedMarker vis{a};
   float tmin = INFINITY;
   for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < a.Q; q += (int64_t)gridDim.x * 4) {
-    const int64_t nid = a.nids[q];
     const double t = a.ts[q];
     tmin = fminf(tmin, (float)t);
-    int64_t start;
-    const int64_t end = prefix_end_group<64>(g, nid, t, &start, lane);
-    float* st = s_t[wv];
-    const int c = recent_nodes_scan(g, start, end, K, s_new[wv], lane,
-                                    [&](int slot, int64_t p, int) { st[slot] = (float)g.ts[p]; });
-    __builtin_amdgcn_wave_barrier();
-    int nb = 0;  // lane j < c: kept entry j; lanes c .. K-1: padding slots
-    float tf = 0.f;
-    if (lane < c) {
-      nb = s_new[wv][lane];
-      tf = st[lane];
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < K) involved_mark(a, nb);
-    if (lane == 0) involved_mark(a, nid);
-    if (!a.two) continue;  // (wave-uniform)
-    const int n2 = c < K ? c + 1 : K;  // one padding slot stands for all of them
-    for (int j = 0; j < n2; ++j) {
-      const int64_t nb2 = __shfl(nb, j, TG_WAVE);
-      const double t2 = (double)__shfl(tf, j, TG_WAVE);
-      int64_t st2;
-      const int64_t e2 = prefix_end_group<64>(g, nb2, t2, &st2, lane);
-      const int c2 = recent_nodes_scan(g, st2, e2, K, s_new[wv], lane, [&](int, int64_t, int v) { involved_mark(a, v); });
-      if (c2 < K && lane == 0) involved_mark(a, 0);
-    }
+    involved_visit_nodes(a.g, a.nids[q], t, a.K, a.two != 0, lane, s_new[wv], s_t[wv], vis);
   }
   involved_tmin(a, tmin);
 }
@@ -263,23 +217,6 @@ static int involved_args(const tg_tcsr* g, int64_t Q, const int64_t* nids, const
   return TG_OK;
 }
 
-// graph.py:117-143 on the host arrays: the entries of the K slots of (nid, t), in any order -> how many
-static int host_tail(const tg_tcsr* g, int64_t nid, double t, int K, int strategy, std::vector<int64_t>& sel) {
-  sel.clear();
-  const int64_t lo = g->indptr[nid];
-  const int64_t hi = std::lower_bound(g->ts + lo, g->ts + g->indptr[nid + 1], t) - g->ts;  // ts < t
-  if (strategy == 0) {
-    for (int64_t p = std::max(lo, hi - K); p < hi; ++p) sel.push_back(p);
-  } else {  // the last occurrence of every distinct neighbour, the K most recent of those
-    for (int64_t p = hi - 1; p >= lo && (int)sel.size() < K; --p) {
-      bool seen = false;
-      for (int64_t s : sel) seen = seen || g->nbr[s] == g->nbr[p];
-      if (!seen) sel.push_back(p);
-    }
-  }
-  return (int)sel.size();
-}
-
 }  // namespace tg
 
 using namespace tg;
@@ -349,19 +286,10 @@ extern "C" int tg_involved_list_host(const tg_tcsr* g, int64_t Q, const int64_t*
   double t_first = ts_host[0];
   for (int64_t q = 0; q < Q; ++q) {
     t_first = std::min(t_first, ts_host[q]);
-    flags[nids_host[q]] = 1;
-    const int n1 = host_tail(g, nids_host[q], ts_host[q], K, strategy, hop1);
-    for (int64_t p : hop1) flags[g->nbr[p]] = 1;
-    if (n1 < K) flags[0] = 1;  // left padding: the sampler marks id 0
-    if (n_layers != 2) continue;
-    // data_loader.py:131: every slot is sampled again at its own float32 time, padding slots as node 0 at time 0
-    for (int j = n1 < K ? -1 : 0; j < n1; ++j) {
-      const int64_t v = j < 0 ? 0 : g->nbr[hop1[j]];
-      const double t = j < 0 ? 0.0 : (double)(float)g->ts[hop1[j]];
-      const int n2 = host_tail(g, v, t, K, strategy, hop2);
-      for (int64_t p : hop2) flags[g->nbr[p]] = 1;
-      if (n2 < K) flags[0] = 1;
-    }
+    host_involved_visit(g, nids_host[q], ts_host[q], K, n_layers, strategy, hop1, hop2, [&](int64_t v) {
+      flags[v] = 1;
+      return false;
+    });
   }
   int64_t n = 0;
   for (int64_t v = 0; v < g->num_node; ++v) {

@@ -374,6 +374,135 @@ def involved_list(graph, nids: Tensor, ts: Tensor, n_neighbors: int, n_layers: i
     return out
 
 
+# ---- incremental catalogue refresh (tg_snapshot_refresh.hip and its host twins) --------------------------------------------
+def _graph_tcsr(what: str, graph, dev):
+    """the tg_tcsr of `graph` for tensors on `dev`: host arrays for the cpu, graph.tcsr on the graph's own device"""
+    if dev.type == 'cpu':
+        h = graph._host_tcsr()
+        return _lib.TgTcsr(graph.num_node, len(h[1]), *(ptr(a) for a in h)), h
+    gd = graph.device
+    if gd is None or gd.type != dev.type or (gd.index is not None and dev.index is not None and gd.index != dev.index):
+        raise ValueError(f'{what}: the graph lives on {gd}, the tensors on {dev}')
+    return graph.tcsr, None
+
+
+def catalogue_dirty(graph, ids: Tensor, t_row, n_neighbors: int, n_layers: int, touched: Tensor, t_new: float, *,
+                    max_age: Optional[float] = None, strategy: Optional[str] = None, check_ids: bool = True) -> dict:
+    """Which rows of a catalogue read a changed node (tiger_hip.h: tg_catalogue_dirty)?  Row j - the query (ids[j],
+    t_row[j]); t_row a float64 [C] tensor, or ONE float for all rows - is dirty iff a node of its involved set (that of
+    `involved_list` for the one query) has its bit in `touched` (a `new_bitmap` over graph.num_node ids), or max_age is
+    given and t_new - t_row[j] > max_age.  -> dict(rank int32 [C]: position among the dirty rows or -1, cols int32 [C]:
+    the dirty rows ascending in cols[:count[0]], count int32 [2]: n_dirty and the rows dirty by age alone); nothing is
+    read back - but for the ids' range check (two values; check_ids=False for ids the caller has checked already, as
+    those of a CatalogueSnapshot).  Device tensors take the device entry, host tensors the host twin.  ValueError for an
+    id outside [0, num_node), C >= 2^31, a NaN t_new, a negative or NaN max_age."""
+    dev = ids.device
+    ids = _i64(ids).reshape(-1)
+    Cn, K, L = ids.numel(), int(n_neighbors), int(n_layers)
+    strategy = graph.strategy if strategy is None else strategy
+    if strategy not in _STRATEGY_CODE:
+        raise NotImplementedError(strategy)
+    if strategy == 'uniform':
+        raise NotImplementedError("catalogue_dirty: strategy='uniform' would make the set depend on the graph's random stream")
+    n_nodes = graph.num_node
+    t_all = 0.0
+    if torch.is_tensor(t_row):
+        t_row = t_row.to(dev).double().contiguous().reshape(-1)
+        if t_row.numel() != Cn:
+            raise ValueError(f'catalogue_dirty: {Cn} rows, t_row {tuple(t_row.shape)}')
+    else:
+        t_all, t_row = float(t_row), None
+    t_new = float(t_new)
+    age = float('nan') if max_age is None else float(max_age)
+    if Cn >= 2 ** 31 or t_new != t_new or t_all != t_all or (max_age is not None and not age >= 0.0):
+        raise ValueError(f'catalogue_dirty: C = {Cn} (< 2^31), t_new = {t_new}, t_row = {t_all}, max_age = {max_age} (>= 0)')
+    if (touched.dtype != torch.int64 or touched.numel() != bitmap_words(n_nodes) or touched.device != dev
+            or not touched.is_contiguous()):
+        raise ValueError(f'catalogue_dirty: touched {touched.dtype} {tuple(touched.shape)} on {touched.device} for {n_nodes} '
+                         f'nodes on {dev}')
+    if not 1 <= K <= _lib.TG_INVOLVED_MAX_K or L not in (1, 2):
+        raise ValueError(f'catalogue_dirty: 1 <= n_neighbors <= {_lib.TG_INVOLVED_MAX_K}, n_layers 1 or 2')
+    if Cn and (check_ids or dev.type == 'cpu') and (int(ids.min()) < 0 or int(ids.max()) >= n_nodes):
+        raise ValueError('catalogue_dirty: a node id outside [0, num_node)')
+    out = dict(rank=torch.empty(max(Cn, 1), dtype=torch.int32, device=dev)[:Cn],
+               cols=torch.empty(max(Cn, 1), dtype=torch.int32, device=dev)[:Cn],
+               count=torch.zeros(2, dtype=torch.int32, device=dev))
+    tc, keep = _graph_tcsr('catalogue_dirty', graph, dev)
+    args = (Cn, ptr(ids), ptr(t_row), t_all, K, L, _STRATEGY_CODE[strategy], ptr(touched), t_new, age, ptr(out['rank']),
+            ptr(out['cols']), ptr(out['count']))
+    if dev.type == 'cpu':
+        check(lib.tg_catalogue_dirty_host(C_.byref(tc), *args), 'tg_catalogue_dirty_host')
+    else:
+        ws = torch.empty(int(lib.tg_catalogue_dirty_workspace_bytes(Cn)), dtype=torch.uint8, device=dev)
+        check(lib.tg_catalogue_dirty(C_.byref(tc), *args, ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_catalogue_dirty')
+    return out
+
+
+def catalogue_merge(rank: Tensor, n_new: int, h_old: Tensor, h_new: Tensor, t_old, t_new: float, *,
+                    P_old: Optional[Tensor] = None, P_new: Optional[Tensor] = None, nb_old: Optional[Tensor] = None,
+                    nb_new: Optional[Tensor] = None):
+    """The row tables of a refreshed snapshot in one launch (tiger_hip.h: tg_catalogue_merge): out[j] = new[rank[j]] where
+    rank[j] >= 0, else old[j] -> (h float32 [C, d], P float32 [C, d] or None, nb int64 [C, K] or None, t_row float64 [C]).
+    rank int32 [C] (catalogue_dirty); *_new hold n_new rows; t_old: a float64 [C] tensor or ONE float for all old rows; new
+    rows get t_new.  P and nb take part when both their tables are given.  ValueError for shapes that do not fit."""
+    dev = rank.device
+    Cn, n_new = rank.numel(), int(n_new)
+    d = int(h_old.shape[1])
+
+    def table(name, old, new, dtype, width):
+        if (old is None) != (new is None):
+            raise ValueError(f'catalogue_merge: {name}_old and {name}_new come together')
+        if old is None:
+            return None, None, None
+        for what, x, rows in (('old', old, Cn), ('new', new, n_new)):
+            if x.dtype != dtype or x.dim() != 2 or x.shape[0] < rows or x.shape[1] != width or x.device != dev:
+                raise ValueError(f'catalogue_merge: {name}_{what} {x.dtype} {tuple(x.shape)} on {x.device}; wanted {dtype} '
+                                 f'[>= {rows}, {width}] on {dev}')
+        return old.contiguous(), new.contiguous(), torch.empty(Cn, width, dtype=dtype, device=dev)
+
+    if rank.dtype != torch.int32 or rank.dim() != 1 or not 0 <= n_new <= Cn or d < 4 or d % 4:
+        raise ValueError(f'catalogue_merge: rank {rank.dtype} {tuple(rank.shape)}, n_new {n_new}, d {d} (a multiple of 4)')
+    rank = rank.contiguous()
+    h_old, h_new, h_out = table('h', h_old, h_new, torch.float32, d)
+    P_old, P_new, P_out = table('P', P_old, P_new, torch.float32, d)
+    K = int(nb_old.shape[1]) if nb_old is not None else 0
+    nb_old, nb_new, nb_out = table('nb', nb_old, nb_new, torch.int64, K)
+    t_all = 0.0
+    if torch.is_tensor(t_old):
+        t_old = t_old.to(dev).double().contiguous().reshape(-1)
+        if t_old.numel() != Cn:
+            raise ValueError(f'catalogue_merge: {Cn} rows, t_old {tuple(t_old.shape)}')
+    else:
+        t_all, t_old = float(t_old), None
+    t_out = torch.empty(Cn, dtype=torch.float64, device=dev)
+    args = (Cn, n_new, d, K, ptr(rank), ptr(h_old), ptr(h_new), ptr(h_out), ptr(P_old), ptr(P_new), ptr(P_out), ptr(nb_old),
+            ptr(nb_new), ptr(nb_out), ptr(t_old), t_all, float(t_new), ptr(t_out))
+    if dev.type == 'cpu':
+        check(lib.tg_catalogue_merge_host(*args), 'tg_catalogue_merge_host')
+    else:
+        check(lib.tg_catalogue_merge(*args, stream_ptr(dev)), 'tg_catalogue_merge')
+    return h_out, P_out, nb_out, t_out
+
+
+def bitmap_mark_degree_diff(graph_a, graph_b, bits: Tensor):
+    """bits |= the ids whose T-CSR row length differs between the two graphs, an id present in only one of them counting
+    with length 0 there (tiger_hip.h: tg_bitmap_mark_degree_diff).  bits: a `new_bitmap` over max(num_node) ids, IN
+    PLACE; a host tensor takes the host twin over the graphs' host arrays."""
+    dev = bits.device
+    W = bitmap_words(max(graph_a.num_node, graph_b.num_node))
+    if bits.dtype != torch.int64 or bits.dim() != 1 or bits.numel() < W or not bits.is_contiguous():
+        raise ValueError(f'bitmap_mark_degree_diff: bits {bits.dtype} {tuple(bits.shape)}; wanted an int64 bitmap of at least '
+                         f'{W} words')
+    ta, keep_a = _graph_tcsr('bitmap_mark_degree_diff', graph_a, dev)
+    tb, keep_b = _graph_tcsr('bitmap_mark_degree_diff', graph_b, dev)
+    if dev.type == 'cpu':
+        check(lib.tg_bitmap_mark_degree_diff_host(C_.byref(ta), C_.byref(tb), ptr(bits), bits.numel()),
+              'tg_bitmap_mark_degree_diff_host')
+    else:
+        check(lib.tg_bitmap_mark_degree_diff(C_.byref(ta), C_.byref(tb), ptr(bits), bits.numel(), stream_ptr(dev)),
+              'tg_bitmap_mark_degree_diff')
+
+
 # ---- walk candidates (tg_walk_candidates and its host twin) ----------------------------------------------------------------
 def _walk_plan(what: str, C: int, fanout, take) -> Tuple[Tensor, int]:
     """the refusals of tg_walk_candidates that need no tensor, each with the cap it names -> (fanout int32 host, take bits)"""

@@ -27,7 +27,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import hip_ops
-from .._lib import TG_FORM_FC2_DEFERRED, TG_TOPK_MAX_K, TgLazyRestart, TgLinear, TgModel, TgStepIo, check, lib, ptr
+from .._lib import TG_FORM_FC2_DEFERRED, TG_INVOLVED_MAX_K, TG_TOPK_MAX_K, TgLazyRestart, TgLinear, TgModel, TgStepIo, check, lib, ptr
 from ..hip_ops import stream_ptr
 from .basic_modules import MergeLayer
 from .memory import Memory, MessageStoreNoGradLastOnly
@@ -59,7 +59,10 @@ class CatalogueSnapshot:
     parameters have changed since.  col_of int32 [n_nodes], the row of every node id in the snapshot and -1 for a node
     that is not in it (`hip_ops.catalogue_index(ids, n_nodes)`), is built on first use - recommend_subset gathers
     through it - and raises ValueError for a snapshot that lists an id twice.  A snapshot is read-only: nothing in it is
-    updated by later calls."""
+    updated by later calls.  A snapshot is either uniform in time (t_row is None: every row at t) or carries t_row float64
+    [C], the time each row was embedded at (TIGE.refresh_catalogue: rows no change reached keep their bits and their
+    time; t is then the time of the latest refresh).  change_epoch: the epoch of the model's ChangeTracker when the rows
+    were computed (None without tracking) - a snapshot is refreshable while it equals the tracker's."""
 
     def __init__(self, model, ids: Tensor, h: Tensor, nb: Optional[Tensor], t: float, graph, stamp):
         self._model = weakref.ref(model)
@@ -71,6 +74,8 @@ class CatalogueSnapshot:
         self._P = None
         self._P_stamp = None
         self._col_of = None
+        self.t_row = None
+        self.change_epoch = None
 
     @property
     def model(self):
@@ -90,8 +95,62 @@ class CatalogueSnapshot:
         return int(self.ids.numel())
 
 
+class ChangeTracker:
+    """What changed under the rows of a catalogue snapshot (TIGE.track_changes, TIGE.refresh_catalogue).
+    bits: a `hip_ops.new_bitmap` over the model's node ids - every node whose per-node state row (memories, mailbox,
+    node-feature row) or T-CSR row changed since `clear()`; whole: everything may have changed (`reason` says why);
+    epoch: bumped by `clear()` - a snapshot whose change_epoch equals it has seen every change the bits hold.  The model's
+    own writers mark what they write; writes through raw tensors by third parties are the caller's to `mark`."""
+
+    def __init__(self, n_nodes: int, device):
+        self.n_nodes = int(n_nodes)
+        self.bits = hip_ops.new_bitmap(self.n_nodes, device)
+        self.whole, self.reason, self.epoch = False, None, 0
+
+    def fit(self, n_nodes: int):
+        """the model admitted node ids (grow_nodes): the bitmap follows"""
+        if n_nodes > self.n_nodes:
+            self.bits = hip_ops.bitmap_grown(self.bits, n_nodes)
+            self.n_nodes = int(n_nodes)
+
+    def mark(self, ids):
+        ids = torch.as_tensor(ids).to(self.bits.device).long().reshape(-1)
+        if ids.numel() and not self.whole:
+            hip_ops.bitmap_mark(ids, self.bits, self.n_nodes)
+
+    def mark_graph(self, old, new):
+        """every node whose T-CSR row length differs between the two graphs (tg_bitmap_mark_degree_diff): exact for
+        children that only add or only remove entries (extended, merged, trimmed, without); nothing for `renumbered`,
+        which shares indptr.  A graph without device arrays: mark_all."""
+        if old is new or self.whole:
+            return
+        if old is None or new is None or getattr(old, '_dev', None) is None or getattr(new, '_dev', None) is None:
+            return self.mark_all('a graph without device arrays was swapped in or out')
+        self.fit(max(old.num_node, new.num_node))
+        if old._dev[0] is not new._dev[0]:
+            hip_ops.bitmap_mark_degree_diff(old, new, self.bits)
+
+    def mark_all(self, reason: str):
+        if not self.whole:
+            self.whole, self.reason = True, reason
+
+    def clear(self):
+        self.bits.zero_()
+        self.whole, self.reason = False, None
+        self.epoch += 1
+
+    def renumbered(self, n_nodes: int):
+        """the node ids were renumbered (compact_nodes): a fresh bitmap over the new ids, a new epoch, everything changed"""
+        self.n_nodes = int(n_nodes)
+        self.bits = hip_ops.new_bitmap(self.n_nodes, self.bits.device)
+        self.epoch += 1
+        self.whole, self.reason = True, 'compact_nodes / compact_keys renumbered the node ids'
+
+
 class TIGE(nn.Module):
     _born_rows = None
+    _tracker = None          # ChangeTracker (track_changes), None: nothing is recorded
+    last_refreshed = None    # (n_dirty, n_by_age) of the latest refresh_catalogue
 
     @staticmethod
     def born_with_rows(n_rows: int):
@@ -199,6 +258,7 @@ class TIGE(nn.Module):
         if train and (r.rng_fn is None or float(r.merger.dropout.p) != p):
             return self.restart(nids, t_dev.expand(n))
         self._touch()
+        self._mark(nids)
         m, rs = self.model_struct(), r._struct()
         nbytes = int(lib.tg_restart_seq_list_workspace_bytes(C.byref(m), C.byref(rs), n))
         ws = getattr(self, '_restart_list_ws', None)
@@ -270,6 +330,7 @@ class TIGE(nn.Module):
     def restart_list_apply(self, nids: Tensor, h_left: Tensor, h_right: Tensor, prev_ts: Tensor):
         """The state update of `restart_list` (tiger.py:603,608-609) from rows `restart_list_forward` left."""
         self._touch()
+        self._mark(nids)
         m = self.model_struct()
         check(lib.tg_restart_apply(C.byref(m), int(nids.numel()), ptr(nids), ptr(h_left), ptr(h_right), ptr(prev_ts),
                                    stream_ptr(self.device)), 'tg_restart_apply')
@@ -281,6 +342,7 @@ class TIGE(nn.Module):
         for every batch whose count fits and does the host-side bookkeeping itself (eval_utils._RestartPipeline)."""
         r = self.restarter_fn
         cap = int(nids_cap.numel())
+        self._mark_all('restart_list_captured: the count of restarted nodes lives on the device')
         m, rs = self.model_struct(), r._struct()
         nbytes = int(lib.tg_restart_seq_list_workspace_bytes(C.byref(m), C.byref(rs), cap))
         ws = getattr(self, '_restart_cap_ws', None)
@@ -299,7 +361,58 @@ class TIGE(nn.Module):
 
     @graph.setter
     def graph(self, new_obj):
+        old = self.temporal_embedding_fn.graph
         self.temporal_embedding_fn.graph = new_obj
+        if self._tracker is not None:
+            self._tracker.mark_graph(old, new_obj)
+
+    # ---- change tracking ----------------------------------------------------
+    def track_changes(self, enable: bool = True) -> Optional[ChangeTracker]:
+        """Start (or, enable=False, stop) recording which nodes' state rows and T-CSR rows change -> the ChangeTracker
+        (None when switched off).  Opt-in: nothing is recorded, and nothing costs anything, while it is off.  With a
+        tracker installed the model's own writers mark what they write (a streaming step its src and dst, the graph
+        setter the rows whose length changed, restarts / erase / set_node_rows / update_*_memory their ids; whatever
+        rewrites everything - load_state_dict, reset, load_memory_state, flush_msg, load_online, compact_nodes, train(),
+        a step with the in-step restart loop or over a resident stream - sets `whole`).  The evaluation and training
+        steps of `contrast_learning` / `contrast_and_mutual_learning` mark as a streaming step does.  REPLAYS OF A CAPTURED
+        DEVICE GRAPH ARE INVISIBLE to the tracker: the host runs no code when a graph is replayed, so a step captured
+        before tracking was switched on marks nothing, and one captured with tracking on sets `whole` once, at capture
+        time.  Whoever replays captured steps between two refreshes calls `tracker.mark_all(...)` (or `mark(ids)`)
+        itself, as for writes through raw tensors.  Calling track_changes again while a tracker is installed returns
+        that tracker."""
+        if not enable:
+            self._tracker = None
+            return None
+        if self._tracker is None:
+            self._tracker = ChangeTracker(self.n_nodes, self.device)
+        return self._tracker
+
+    def _mark(self, ids):
+        if self._tracker is not None:
+            self._tracker.mark(ids)
+
+    def _mark_all(self, reason: str):
+        if self._tracker is not None:
+            self._tracker.mark_all(reason)
+
+    def _mark_step(self, buf, io):
+        """what one step over the batch in `buf` writes (io: its tg_step_io), for launch_step and for the training /
+        evaluation step of TrainBuffers.launch.  STEP 4-6 write the rows of the batch's positive nodes only (tg_memory.hip:
+        one wavefront per unique positive node); the in-step restart loop re-initialises rows no host list names, a
+        resident stream's batch is named by an offset on the device, and a step that is being captured into a device
+        graph runs again at every replay, which the host does not see: those mark everything."""
+        tr = self._tracker
+        if tr is None:
+            return
+        if io.lazy and getattr(buf, '_lazy_collate', None) is None:
+            tr.mark_all('a step with the in-step lazy-restart loop')
+        elif buf.offset is not None:
+            tr.mark_all('a step over a resident stream: its batch offset lives on the device')
+        elif self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            tr.mark_all('a step captured into a device graph: its replays are invisible to the host')
+        else:
+            tr.mark(buf.src)
+            tr.mark(buf.dst)
 
     @property
     def device(self):
@@ -564,6 +677,7 @@ class TIGE(nn.Module):
         graphs) does not bump: it writes through raw pointers.  Whoever trains passes through train() first."""
         if mode:
             self._param_epoch = getattr(self, '_param_epoch', 0) + 1
+            self._mark_all('train(): parameters are about to change')
         return super().train(mode)
 
     def _attn_stamp(self):
@@ -788,6 +902,8 @@ class TIGE(nn.Module):
         bs, d = len(src_ids), self.memory_dim
         src_ids, dst_ids, neg_dst_ids, eids = (x.to(dev).long().contiguous() for x in
                                                (src_ids, dst_ids, neg_dst_ids, eids))
+        self._mark(src_ids)  # STEP 4-6 below write the rows of the positive nodes
+        self._mark(dst_ids)
         ts = ts.to(dev).float().contiguous()
         pos = torch.cat([src_ids, dst_ids])
         batch_ids = torch.cat([pos, neg_dst_ids])
@@ -1016,7 +1132,133 @@ class TIGE(nn.Module):
             t64 = torch.full((cand.numel(),), t, dtype=torch.float64, device=dev)
             h, nb = self._embed_queries(cand, t64, graph, strategy, err)
             hip_ops.raise_if_err(err)
-        return CatalogueSnapshot(self, cand, h, nb, t, graph, self._snapshot_stamp())
+        snap = CatalogueSnapshot(self, cand, h, nb, t, graph, self._snapshot_stamp())
+        if self._tracker is not None:  # (nothing is cleared: bits from before the snapshot only over-mark)
+            snap.change_epoch = self._tracker.epoch
+        return snap
+
+    def refresh_catalogue(self, snap: CatalogueSnapshot, t: float, *, max_age: Optional[float] = None, graph=None,
+                          clear: bool = True, verify: bool = False) -> CatalogueSnapshot:
+        """Refresh a catalogue snapshot incrementally: re-embed, at time t, only the rows that read something that changed
+        since they were computed -> a NEW CatalogueSnapshot over the same ids; `snap` stays valid and unchanged.  Needs
+        `track_changes()` switched on before `snap` was made.  The child carries t_row float64 [C] and obeys ONE
+        invariant: for every row j, h[j], nb[j] and (when present) P[j] are, bit for bit, what embed_catalogue(ids[j:j+1],
+        t_row[j]) followed by tg_rank_cand_half gives on the model's CURRENT state, graph and parameters.  Row j is dirty
+        iff (1) a node of involved(ids[j], t_row[j]) - the set of tg_involved_list on the current graph - has its bit in
+        the tracker, or (2) max_age is given and t - t_row[j] > max_age (strict float64), or (3) the tracker's `whole`
+        flag is set or the attention / updater parameters changed since `snap` (then every row).  Dirty rows are embedded
+        at t (`_embed_queries`: a row's bits are a function of (node, time, state)) and get t_row[j] = t; clean rows keep
+        their bits and their time.  The child's t is t, its stamps are the current ones (recommend accepts it without
+        stale_ok) and `last_refreshed` = (n_dirty, rows dirty by age alone); when every row is dirty by rule (3) the
+        dirty pass is skipped and the second number is 0 whatever the rows' ages and `max_age`.  One value is read back:
+        the count.
+        Nothing is written to the model's state.  clear=True clears the tracker afterwards and gives the child the new
+        epoch (the parent can then not be refreshed again); clear=False keeps bits and epoch, for a caller with several
+        snapshots.  verify=True re-embeds, for every distinct time of the child, the rows of that time and raises
+        RuntimeError naming the first row whose bits differ - a debugging aid for a missed change, not the fast path.
+        Refused before anything runs, with snapshot and tracker unchanged: no tracker; a snapshot from another tracker
+        epoch; a snapshot of another model, device or numbering; t NaN or below snap.t; max_age negative or NaN; whatever
+        embed_catalogue refuses (strategy 'uniform', a partitioned model, training mode, the 'vec' cases)."""
+        from .training import score_struct
+        tr = self._tracker
+        if tr is None:
+            raise RuntimeError('refresh_catalogue: nothing recorded what changed - call track_changes() before embed_catalogue')
+        if not isinstance(snap, CatalogueSnapshot):
+            raise TypeError(f'refresh_catalogue: {type(snap).__name__} is no CatalogueSnapshot')
+        graph, strategy = self._pair_refusals('refresh_catalogue', graph, 1, None)
+        self._shared_refusals('refresh_catalogue')
+        if self.memory_dim % 4 or self.n_neighbors > TG_INVOLVED_MAX_K:
+            raise NotImplementedError(f'refresh_catalogue: memory_dim {self.memory_dim} must be a multiple of 4 (the merge moves '
+                                      f'16-byte words) and n_neighbors {self.n_neighbors} at most {TG_INVOLVED_MAX_K}')
+        self._check_snapshot(snap, graph, True)
+        if snap.change_epoch != tr.epoch:
+            raise RuntimeError(f'refresh_catalogue: the snapshot belongs to change epoch {snap.change_epoch}, the tracker is at '
+                               f'{tr.epoch} (cleared by another refresh, or the snapshot predates track_changes): embed it again')
+        t = float(t)
+        if t != t or t < snap.t:
+            raise ValueError(f'refresh_catalogue: t = {t}; a refresh moves a snapshot of time {snap.t} forward')
+        if max_age is not None and not float(max_age) >= 0.0:
+            raise ValueError(f'refresh_catalogue: max_age = {max_age} (a non-negative number of time units)')
+        dev, Cn = self.device, len(snap)
+        K = self.n_neighbors
+        t_old = snap.t if snap.t_row is None else snap.t_row
+        whole = tr.whole or tuple(snap.stamp[2]) != tuple(self._attn_stamp())
+        with torch.no_grad():
+            self._embed_prepare()
+            if whole or Cn == 0:
+                n_dirty, n_age = Cn, 0
+                rank = torch.arange(Cn, dtype=torch.int32, device=dev)
+                ids_new = snap.ids
+            else:
+                out = hip_ops.catalogue_dirty(graph, snap.ids, t_old, K, self.n_layers, tr.bits, t, max_age=max_age,
+                                              strategy=strategy, check_ids=False)  # (embed_catalogue checked them)
+                n_dirty, n_age = (int(x) for x in out['count'].tolist())  # the one read-back
+                rank = out['rank']
+                ids_new = snap.ids[out['cols'][:n_dirty].long()]
+            err = hip_ops.new_err(dev)
+            h_new = torch.empty(0, self.memory_dim, dtype=torch.float32, device=dev)
+            nb_new = None if snap.nb is None else torch.empty(0, K, dtype=torch.int64, device=dev)
+            if n_dirty:
+                t64 = torch.full((n_dirty,), t, dtype=torch.float64, device=dev)
+                h_new, nb_new = self._embed_queries(ids_new.contiguous(), t64, graph, strategy, err)
+                hip_ops.raise_if_err(err)
+            P_old = P_new = None
+            score_stamp = self._score_stamp()
+            if snap._P is not None and snap._P_stamp == score_stamp:
+                P_old, P_new = snap._P, torch.empty_like(h_new)
+                if n_dirty:
+                    sp = score_struct(self)
+                    check(lib.tg_rank_cand_half(n_dirty, self.memory_dim, K, C.byref(sp), ptr(h_new), ptr(P_new),
+                                                stream_ptr(dev)), 'tg_rank_cand_half')
+            if Cn:
+                h, P, nb, t_row = hip_ops.catalogue_merge(rank, n_dirty, snap.h, h_new, t_old, t, P_old=P_old, P_new=P_new,
+                                                          nb_old=snap.nb, nb_new=nb_new)
+            else:
+                h, P, nb, t_row = snap.h.clone(), None, snap.nb, torch.empty(0, dtype=torch.float64, device=dev)
+        child = CatalogueSnapshot(self, snap.ids, h, nb, t, graph, self._snapshot_stamp())
+        child.t_row = t_row
+        child.change_epoch = tr.epoch
+        if P is not None:
+            child._P, child._P_stamp = P, score_stamp
+        if snap._col_of is not None and child.n_nodes == snap.n_nodes:
+            child._col_of = snap._col_of
+        if verify:
+            self._verify_snapshot(child, graph, strategy)
+        self.last_refreshed = (n_dirty, n_age)
+        if clear:
+            tr.clear()
+            child.change_epoch = tr.epoch
+        return child
+
+    def _verify_snapshot(self, snap: CatalogueSnapshot, graph, strategy: str):
+        """refresh_catalogue(verify=True): every group of rows that share a t_row, embedded again at that time"""
+        from .training import score_struct
+        dev = self.device
+        with torch.no_grad():
+            for tau in torch.unique(snap.t_row).tolist():
+                rows = torch.nonzero(snap.t_row == tau).reshape(-1)
+                err = hip_ops.new_err(dev)
+                t64 = torch.full((rows.numel(),), tau, dtype=torch.float64, device=dev)
+                h, nb = self._embed_queries(snap.ids[rows].contiguous(), t64, graph, strategy, err)
+                hip_ops.raise_if_err(err)
+                pairs = [('h', h, snap.h[rows])]
+                if nb is not None:
+                    pairs.append(('nb', nb, snap.nb[rows]))
+                if snap._P is not None:
+                    P = torch.empty_like(h)
+                    sp = score_struct(self)
+                    check(lib.tg_rank_cand_half(rows.numel(), self.memory_dim, self.n_neighbors, C.byref(sp), ptr(h), ptr(P),
+                                                stream_ptr(dev)), 'tg_rank_cand_half')
+                    pairs.append(('P', P, snap._P[rows]))
+                for name, fresh, held in pairs:
+                    a = fresh.view(torch.int32) if fresh.dtype == torch.float32 else fresh
+                    b = held.contiguous().view(torch.int32) if held.dtype == torch.float32 else held
+                    bad = (a != b).reshape(rows.numel(), -1).any(1)
+                    if bool(bad.any()):
+                        j = int(rows[torch.nonzero(bad)[0, 0]])
+                        raise RuntimeError(f'refresh_catalogue(verify=True): row {j} (node {int(snap.ids[j])}, embedded at '
+                                           f'{tau}) differs from a fresh embedding in {name} - a change the tracker did '
+                                           'not see (a write through a raw tensor? `tracker.mark(ids)` is the caller\'s)')
 
     def embed_catalogue(self, cand: Tensor, t: float, *, graph=None, uptodate: Optional[Tensor] = None) -> CatalogueSnapshot:
         """Embed a shared catalogue once, at ONE time t, on the model's CURRENT state -> CatalogueSnapshot (ids, h, nb, t;
@@ -1579,6 +1821,8 @@ class TIGE(nn.Module):
                 buf._pf_state.value = 2  # made, but for another state / offset / graph: the step discards it
             before = buf._pf_state.value
         self._step_serial = getattr(self, '_step_serial', 0) + 1
+        if self._tracker is not None and not (buf.embed_only or buf.io.collate_only):
+            self._mark_step(buf, buf.io)
         check(lib.tg_stream_step(C.byref(m), C.byref(g), C.byref(buf.io), ptr(buf.ws), buf.ws.numel(),
                                  stream_ptr(self.device)), 'tg_stream_step')
         if pf:
@@ -1786,6 +2030,8 @@ class TIGE(nn.Module):
         self.n_nodes = num_node
         if getattr(self, 'restarter_fn', None) is not None:
             self.restarter_fn.n_nodes = num_node
+        if self._tracker is not None:
+            self._tracker.fit(num_node)  # (the admitted ids are born with zero rows: a snapshot cannot have read them)
         self.graph = graph  # (the setter: the restarter follows)
         self._touch()
         self.invalidate_struct()
@@ -1884,6 +2130,8 @@ class TIGE(nn.Module):
         self.n_nodes = n_new
         if getattr(self, 'restarter_fn', None) is not None:
             self.restarter_fn.n_nodes = n_new
+        if self._tracker is not None:  # another numbering: a bitmap over the old ids means nothing any more
+            self._tracker.renumbered(n_new)  # (a new epoch: no snapshot from before is refreshable)
         self.graph = child  # (the setter: the restarter follows; snapshot stamps go stale)
         self._touch()
         self.invalidate_struct()
@@ -2064,6 +2312,7 @@ class TIGE(nn.Module):
         updates, centre / query rows) are rebuilt before their next use.  Its refusals."""
         self.raw_feat_getter.set_node_rows(ids, rows, check=check)
         self._touch()
+        self._mark(ids)
 
     def erase_keys(self, idmap, keys, *, eids=None, release_edge_rows: bool = False, keep_from=None):
         """`erase` behind external keys, and the keys LEAVE the map (a closed account) -> (graph,
@@ -2204,6 +2453,7 @@ class TIGE(nn.Module):
             S.node_msg_vals.index_fill_(0, ids, 0)
             S.node_msg_ts.index_fill_(0, ids, 0)
             S.clear(ids)
+            self._mark(ids)
         self._touch()
         return self.graph
 
@@ -2381,6 +2631,7 @@ class TIGE(nn.Module):
         else:
             self.graph = graph
         fg.install_rows(tables.get('nfeats'), tables.get('efeats'))
+        self._mark_all('load_online replaced state, graph and tables')
         self.load_state_dict(sd)
         for k in self._MAILBOX:
             getattr(S, k).copy_(mb[k])
@@ -2400,11 +2651,13 @@ class TIGE(nn.Module):
     @torch.no_grad()
     def update_right_memory(self, node_ids: Tensor, new_vals: Tensor, ts: Tensor):
         self.right_memory.set(node_ids, new_vals, ts)
+        self._mark(node_ids)
 
     @torch.no_grad()
     def update_left_memory(self, node_ids: Tensor, new_vals: Tensor, ts: Tensor):
         node_ids, index = select_latest_nids(node_ids, ts, self.n_nodes)
         self.left_memory.set(node_ids, new_vals[index], ts[index])
+        self._mark(node_ids)
 
     @torch.no_grad()
     def flush_msg(self):
@@ -2412,6 +2665,7 @@ class TIGE(nn.Module):
         self._refuse_partitioned('flush_msg')
         self._poll_train_errors()
         self._touch()
+        self._mark_all('flush_msg consumed every pending message')
         dev = self.device
         m = self.model_struct()
         err = hip_ops.new_err(dev)
@@ -2430,12 +2684,14 @@ class TIGE(nn.Module):
         recomputed and the eager-update table is rebuilt before its next use"""
         out = super().load_state_dict(*args, **kwargs)
         self._touch()
+        self._mark_all('load_state_dict replaced parameters and memories')
         if self._fused is not None:
             self.fuse_attention()
         return out
 
     def reset(self):
         self._touch()
+        self._mark_all('reset cleared every memory and the mailbox')
         self.left_memory.clear()
         self.right_memory.clear()
         self.msg_store.clear()
@@ -2449,6 +2705,7 @@ class TIGE(nn.Module):
                 raise ValueError(f'load_memory_state: the saved state holds {new.n} rows per table, the model {cur.n} '
                                  '(saved before grow_nodes admitted node ids? grow it with its own grow(n) first)')
         self._touch()
+        self._mark_all('load_memory_state replaced every memory and the mailbox')
         self.left_memory, self.right_memory, self.msg_store = data
         self.msg_memory = self.left_memory if self.msg_src == 'left' else self.right_memory
         self.upd_memory = self.left_memory if self.upd_src == 'left' else self.right_memory
@@ -2514,6 +2771,7 @@ class TIGER(TIGE):
         self._touch()
         dev = self.device
         nids = nids.to(dev).long().contiguous()
+        self._mark(nids)
         h_left, h_right, prev_ts = self.restarter_fn(nids, ts.to(dev))
         if mix > 0:
             # the library's gather, not torch indexing: tables beyond 2^31 elements (10 M nodes x 256)
@@ -2561,5 +2819,8 @@ class TIGER(TIGE):
 
     @graph.setter
     def graph(self, new_obj):
+        old = self.temporal_embedding_fn.graph
         self.temporal_embedding_fn.graph = new_obj
         self.restarter_fn.graph = new_obj
+        if self._tracker is not None:
+            self._tracker.mark_graph(old, new_obj)

@@ -275,6 +275,7 @@ class TrainBuffers:
         self._grads_taken = False
         if zero_grads and not self.eval_only:
             self.gflat.zero_()
+        model._mark_step(self.sb, self.io.step)  # (change tracking: the write-back is the streaming step's)
         m = model.model_struct()
         self.io.step.rows_hint = model.rows_bound()
         graph = model.graph if graph is None else graph

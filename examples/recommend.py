@@ -37,6 +37,11 @@ batches first.  --load_state PATH starts from such a file instead of train + val
 `init_model` builds: the graph is checked by `tg_tcsr_verify` before anything reads it) and replays the rest of the split.
 A replay that is saved after N batches and one that loads the file write, between them, the lists of the uninterrupted
 replay, exactly.
+--journal DIR [--journal_every N] writes INCREMENTAL state files instead (`TIGE.journal().save`): a base before the first
+batch, then a file after every N batches that holds only the rows that changed - a delta; a base again whenever something
+rewrote everything, as --release_rows does - and index.json with each file's kind and position.  --load_state DIR/BASE.pt
+--apply_deltas DIR loads that base, applies the deltas behind it (`TIGE.apply_online_delta`) and replays the rest of the
+split: its lists are the journaling replay's from there on, exactly.
 --keyed runs the online replay as a service meets its users: every node id of the data set is replaced by an external
 64-bit key (a fixed odd-multiplier scramble of the id), the model sits behind a device id map (`IdMap.from_keys` over the ids
 it was built on), every batch asks `TIGE.recommend_keys` and is ingested with `TIGE.observe_keys`, and the keys admitted are
@@ -88,6 +93,7 @@ candidates.
 Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
 import argparse
+import json
 import os
 import sys
 
@@ -252,7 +258,8 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
                erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False,
-               churn=None, compact_at=None, late=None, late_by=1, refresh=False, max_age=None):
+               churn=None, compact_at=None, late=None, late_by=1, refresh=False, max_age=None, journal=None, journal_every=1,
+               apply_deltas=None):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -301,9 +308,23 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     refresh (the plain online replay only): ONE catalogue snapshot, taken before the replay with change tracking on, serves
     every batch and is brought up to date after every `observe` by `refresh_catalogue(snap, t_batch_end, max_age=max_age)`;
     the replay prints `n_dirty / C` per batch and its metrics carry 'refreshed': (n_dirty, n_by_age) per batch.  Items are
-    scored as of their last refresh, so the lists differ from the offline replay's and none is made."""
+    scored as of their last refresh, so the lists differ from the offline replay's and none is made.
+    journal (a directory; not with keyed): the replay writes incremental state files there (`model.journal().save`): a base
+    before the first batch, then a file after every journal_every batches - a delta that holds only the rows that changed,
+    or a base again when something rewrote everything (release_rows does) - as 000000.pt, 000001.pt, ... beside
+    index.json: per file its kind and the position in the split.  No offline replay is made; the metrics carry 'ids' and
+    'journal': the kinds written.
+    apply_deltas (such a directory; with load_state = one of its BASE files): `load_online(base)`, then
+    `apply_online_delta` for every delta that follows it in the index, and the replay continues at the last file's
+    position - its lists are those of the replay that wrote the files, from there on."""
     from www2023tiger_amd.data.graph import Graph
     forgetting = window is not None or keep_last is not None
+    if journal is not None and keyed:
+        raise ValueError('journal: the id map of a keyed replay is not part of the state files')
+    if apply_deltas is not None and load_state is None:
+        raise ValueError('apply_deltas: name the base file of the directory with load_state')
+    if journal is not None or apply_deltas is not None:
+        offline = False
     if refresh:
         if keyed or grow or forgetting or late is not None or erase_nodes is not None or retract_eids is not None or save_state \
                 or load_state or save_after is not None:
@@ -384,7 +405,23 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
             model.graph = seen()
         else:   # (checks everything, the graph with tg_tcsr_verify, before anything changes; grows the tables if need be)
             blob = torch.load(load_state, map_location='cpu', weights_only=True)
-            model.load_online(blob['state'])
+            if apply_deltas is not None:   # a base of a journal directory and the deltas behind it, in the index's order
+                with open(os.path.join(apply_deltas, 'index.json')) as f:
+                    index = json.load(f)
+                at = [i for i, x in enumerate(index) if x['file'] == os.path.basename(load_state) and x['kind'] == 'base']
+                if not at:
+                    raise ValueError(f'{load_state} is no base file of {apply_deltas}/index.json')
+                model.load_online(blob)
+                blob = dict(next_event=index[at[0]]['next_event'], shifted=index[at[0]]['shifted'])
+                for x in index[at[0] + 1:]:
+                    if x['kind'] != 'delta':
+                        break
+                    model.apply_online_delta(os.path.join(apply_deltas, x['file']))
+                    blob = dict(next_event=x['next_event'], shifted=x['shifted'])
+                    if verbose:
+                        print(f"applied {x['file']}: {model.n_nodes} node ids, {int(model.graph.tcsr.num_entry)} entries")
+            else:
+                model.load_online(blob['state'])
             first, shifted[0] = int(blob['next_event']), int(blob['shifted'])
             if keyed and 'idmap' not in blob:
                 raise ValueError(f'{load_state} was saved by a replay without --keyed: it holds no id map')
@@ -492,6 +529,27 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                 if verbose:
                     print(f'batch {len(refreshed) - 1}: refreshed {refreshed[-1][0]} / {len(snap[0])} rows '
                           f'({refreshed[-1][1]} by age alone)')
+        written = []
+        if journal is not None:
+            os.makedirs(journal, exist_ok=True)
+            J, inner, at = model.journal(), ingest, [first, 0]
+
+            def save_file():
+                name = f'{len(written):06d}.pt'
+                kind = J.save(os.path.join(journal, name))
+                written.append(dict(file=name, kind=kind, next_event=at[0], shifted=shifted[0]))
+                with open(os.path.join(journal, 'index.json'), 'w') as f:
+                    json.dump(written, f)
+                if verbose:
+                    print(f'journal: {name} ({kind}) at event {at[0]}: {os.path.getsize(os.path.join(journal, name))} bytes')
+
+            def ingest(s, d, t, e):
+                inner(s, d, t, e)
+                at[0] += len(s)
+                at[1] += 1
+                if at[1] % int(journal_every) == 0:
+                    save_file()
+            save_file()
         ids_on, online = _replay(model, test, catalogue, col_of, k, exclude_seen, bs, ingest, known=known if grow else None,
                                  first=first, stop=stop, keyed=keyed or None, snapshot=(lambda: snap[0]) if refresh else None)
         if late is not None:
@@ -517,8 +575,10 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         # (keyed: the padding id 0 of a short list is INT64_MIN among keys)
         want = np.where(ids_off == 0, INT64_MIN, scramble(ids_off)) if keyed else ids_off
         assert np.array_equal(ids_on, want) and online == offline, (online, offline)
-    if partial or save_state is not None or keyed:
+    if partial or save_state is not None or keyed or journal is not None:
         online = dict(online, ids=ids_on)
+    if journal is not None:
+        online = dict(online, journal=[x['kind'] for x in written])
     if grow or keyed:
         online = dict(online, admitted=admitted)
     if keyed:
@@ -619,6 +679,11 @@ if __name__ == '__main__':
     ap.add_argument('--save_after', type=int, default=None, metavar='N', help='--save_state: stop the replay after N batches')
     ap.add_argument('--load_state', default=None, metavar='PATH', help='--online: start from a file of --save_state instead '
                     'of train + validation (TIGE.load_online) and replay the rest of the split')
+    ap.add_argument('--journal', default=None, metavar='DIR', help='--online: write incremental state files to DIR '
+                    '(TIGE.journal().save: a base, then deltas that hold only the rows that changed) and index.json')
+    ap.add_argument('--journal_every', type=int, default=1, metavar='N', help='--journal: a file after every N batches (default 1)')
+    ap.add_argument('--apply_deltas', default=None, metavar='DIR', help='--online --load_state DIR/BASE.pt: load that base of a '
+                    '--journal directory, apply the deltas behind it (TIGE.apply_online_delta) and replay the rest of the split')
     ap.add_argument('--keyed', action='store_true', help='--online: every node id becomes an external 64-bit key; the model '
                     'sits behind a device id map (observe_keys / recommend_keys) and ids.npy holds keys')
     ap.add_argument('--compact_at', type=float, default=None, metavar='F', help='--online --keyed --churn FILE: behind an erase, '
@@ -661,7 +726,8 @@ if __name__ == '__main__':
                                                               save_after=a.save_after, load_state=a.load_state,
                                                               keyed=a.keyed, churn=a.churn, compact_at=a.compact_at,
                                                               late=a.late, late_by=a.late_by, refresh=a.refresh,
-                                                              max_age=a.max_age)):
+                                                              max_age=a.max_age, journal=a.journal,
+                                                              journal_every=a.journal_every, apply_deltas=a.apply_deltas)):
             if m is None:
                 continue
             if a.keyed and 'ids' in m:

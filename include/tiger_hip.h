@@ -1577,6 +1577,78 @@ int tg_catalogue_merge_host(int64_t C, int64_t n_new, int32_t d, int32_t K, cons
 int tg_bitmap_mark_degree_diff(const tg_tcsr* a, const tg_tcsr* b, uint64_t* bits, int64_t bit_words, void* stream);
 int tg_bitmap_mark_degree_diff_host(const tg_tcsr* a, const tg_tcsr* b, uint64_t* bits_host, int64_t bit_words);
 
+/* Incremental online state files (tg_journal.hip; TIGE.journal / TIGE.apply_online_delta).  The reference
+ * (tiger.py, memory.py:127-129, graph.py:11-42) rebuilds graph, mailbox and tables from the data set and never saves a
+ * served model: none of the entries below has a counterpart there.
+ *
+ * tg_tcsr_rows_pack_plan (graph.py:11-42: no counterpart): rows [D] int32, ascending and distinct, 0 <= D <= num_node.
+ * Writes off [D + 1] int64: off[j] = the entries of the listed rows in front of row j, off[D] = the packed length - the
+ * ONE value the caller reads back, so that the packed arrays are allocated exactly.  A row id outside [0, num_node) counts
+ * as an empty row.  Tiles of 2048 listed rows: one launch for a single tile, two otherwise (D == 0: a memset of off[0]);
+ * no kernel waits for another workgroup.  ws: tg_tcsr_rows_pack_workspace_bytes(D) bytes, 16-byte aligned; a short one
+ * returns TG_EWORKSPACE before any launch.
+ * tg_tcsr_rows_pack_apply (no counterpart): one launch over the PACKED entries (tiles of 2048: a hub row is spread over as
+ * many workgroups as it has tiles): ts_out / nbr_out / eid_out [n_pack] = the entries of the listed rows, row after row;
+ * n_pack = off[D].  No atomics.  TG_EINVAL: what tcsr_args refuses for g, D outside [0, num_node], n_pack outside
+ * [0, num_entry], a missing array.
+ *
+ * tg_tcsr_rows_splice_plan (no counterpart): the old graph g, N_new in [g->num_node, 2^31), rows [D] / off [D + 1] and
+ * n_pack as a pack produced them - UNTRUSTED.  The length of new row v is off[j + 1] - off[j] if v == rows[j], else the old
+ * length (0 for v >= g->num_node).  Writes indptr_out [N_new + 1] and out3 (DEVICE, int64 [3]) = {num_entry_new, error class,
+ * smallest offender}: the one read-back.  Error classes (0: clean), reported in this order, each with its SMALLEST offender
+ * whatever the launch geometry:
+ *   TG_SPLICE_ROWS  rows[j] outside [0, N_new) or rows[j] <= rows[j - 1]; offender = j
+ *   TG_SPLICE_OFF   off[0] != 0 (offender 0), off[j + 1] < off[j] (offender j + 1), off[D] != n_pack (offender D)
+ *   TG_SPLICE_PTR   a row v of g with indptr[v] < 0, indptr[v + 1] < indptr[v] or indptr[v + 1] > num_entry; offender = v
+ * On an error the other outputs are not to be used.  Every loaded row id, offset and row bound is range-checked before
+ * it is used as an index.  A memset of 32 bytes and four launches (one thread per listed row; 256 new ids per workgroup,
+ * the id is looked for in `rows` by a binary search); no kernel waits for another workgroup.  ws:
+ * tg_tcsr_rows_splice_workspace_bytes(N_new) bytes (0 for N_new outside [1, 2^31)), 16-byte aligned, handed on to the
+ * apply.  TG_EINVAL: what tcsr_args refuses for g, N_new < g->num_node, D outside [0, N_new], a missing array, n_pack < 0 or
+ * g->num_entry + n_pack >= 2^32 (no partial sum of the scan wraps).
+ * tg_tcsr_rows_splice_apply (no counterpart): one launch over the NEW entries (tiles of 2048); every entry is read from g
+ * or from the pack and has one writer: no atomics.  The parent's arrays are only read; the child references none of them.
+ * The arrays are those of a T-CSR only as far as the pack was one: they still go through tg_tcsr_verify.
+ *
+ * tg_node_rows_scatter (memory.py:127-129: no counterpart): the inverse of tg_node_rows_compact, ONE launch for up to
+ * TG_NODE_ROWS_MAX tables: for table t and j < n_rows_src <= n_ids, dst[ids[j]] = src[j] (row_bytes bytes).  Here
+ * n_rows_src = the rows of src that are read and n_rows_out = the rows of dst, which every id is checked against before the
+ * store (an id outside stores nothing).  ids distinct.  row_bytes: a multiple of 16 (16-byte loads and stores; src and dst
+ * 16-byte aligned) or 8, 4 or 1.  src and dst must not overlap.  TG_EINVAL before the launch: n_tab outside [0, 8],
+ * another row width, row_bytes > 2^20, n_rows_src > n_ids, a missing or misaligned pointer, overlap.
+ *
+ * tg_bitmap_scatter (no counterpart): bit ids[j] of `bits` (a bitmap over n_ids ids) = (bytes[j] != 0) for j < n; every
+ * other bit keeps its value.  ids distinct (neighbours share words: one 64-bit atomicOr / atomicAnd per id, the result does
+ * not depend on the order); an id outside [0, n_ids) stores nothing.
+ * The _host twins: HOST pointers (those of `g` and the descriptors included), plain C++, the same results bit for bit;
+ * tg_tcsr_rows_pack_host is plan + apply (the output arrays hold at least the packed length), tg_tcsr_rows_splice_host is
+ * plan + apply (the output arrays hold at least g->num_entry + n_pack entries; on an error indptr_out is zeroed). */
+#define TG_SPLICE_ROWS 1
+#define TG_SPLICE_OFF 2
+#define TG_SPLICE_PTR 3
+size_t tg_tcsr_rows_pack_workspace_bytes(int64_t D);
+int tg_tcsr_rows_pack_plan(const tg_tcsr* g, const int32_t* rows, int64_t D, int64_t* off, void* ws, size_t ws_bytes,
+                           void* stream);
+int tg_tcsr_rows_pack_apply(const tg_tcsr* g, const int32_t* rows, int64_t D, const int64_t* off, int64_t n_pack,
+                            double* ts_out, int32_t* nbr_out, int32_t* eid_out, void* stream);
+size_t tg_tcsr_rows_splice_workspace_bytes(int64_t N_new);
+int tg_tcsr_rows_splice_plan(const tg_tcsr* g, int64_t N_new, const int32_t* rows, int64_t D, const int64_t* off,
+                             int64_t n_pack, int64_t* indptr_out, int64_t* out3, void* ws, size_t ws_bytes, void* stream);
+int tg_tcsr_rows_splice_apply(const tg_tcsr* g, int64_t N_new, const int64_t* indptr_out, int64_t num_entry_out,
+                              int64_t n_pack, const double* ts_pack, const int32_t* nbr_pack, const int32_t* eid_pack,
+                              double* ts_out, int32_t* nbr_out, int32_t* eid_out, const void* ws, size_t ws_bytes,
+                              void* stream);
+int tg_node_rows_scatter(const tg_node_rows* tabs, int32_t n_tab, const int32_t* ids, int64_t n_ids, void* stream);
+int tg_bitmap_scatter(const uint8_t* bytes, const int32_t* ids, int64_t n, uint64_t* bits, int64_t n_ids, void* stream);
+int tg_tcsr_rows_pack_host(const tg_tcsr* g, const int32_t* rows_host, int64_t D, int64_t* off_host, double* ts_out_host,
+                           int32_t* nbr_out_host, int32_t* eid_out_host);
+int tg_tcsr_rows_splice_host(const tg_tcsr* g, int64_t N_new, const int32_t* rows_host, int64_t D, const int64_t* off_host,
+                             int64_t n_pack, const double* ts_pack_host, const int32_t* nbr_pack_host,
+                             const int32_t* eid_pack_host, int64_t* indptr_out_host, double* ts_out_host, int32_t* nbr_out_host,
+                             int32_t* eid_out_host, int64_t* out3_host);
+int tg_node_rows_scatter_host(const tg_node_rows* tabs, int32_t n_tab, const int32_t* ids_host, int64_t n_ids);
+int tg_bitmap_scatter_host(const uint8_t* bytes_host, const int32_t* ids_host, int64_t n, uint64_t* bits_host, int64_t n_ids);
+
 /* ------------------------------------------------------------------------- */
 /* Walk candidates (no reference counterpart): per-query candidate generation */
 /* over the T-CSR - a source's own recent neighbours and the ends of its       */

@@ -60,6 +60,7 @@ class TgNodeRows(C.Structure):
 
 TG_NODE_COMPACT_ID0, TG_NODE_COMPACT_SPARE, TG_NODE_COMPACT_ROW, TG_NODE_COMPACT_NBR = 1, 2, 3, 4
 TG_NODE_ROWS_MAX = 8
+TG_SPLICE_ROWS, TG_SPLICE_OFF, TG_SPLICE_PTR = 1, 2, 3  # tg_tcsr_rows_splice_plan: error classes
 
 
 class TgAdvIndex(C.Structure):
@@ -378,6 +379,18 @@ SIGNATURES = {
                                           C.c_double, vp]),
     'tg_bitmap_mark_degree_diff': (C.c_int, [P(TgTcsr), P(TgTcsr), vp, i64, vp]),
     'tg_bitmap_mark_degree_diff_host': (C.c_int, [P(TgTcsr), P(TgTcsr), vp, i64]),
+    'tg_tcsr_rows_pack_workspace_bytes': (sz, [i64]),
+    'tg_tcsr_rows_pack_plan': (C.c_int, [P(TgTcsr), vp, i64, vp, vp, sz, vp]),
+    'tg_tcsr_rows_pack_apply': (C.c_int, [P(TgTcsr), vp, i64, vp, i64, vp, vp, vp, vp]),
+    'tg_tcsr_rows_splice_workspace_bytes': (sz, [i64]),
+    'tg_tcsr_rows_splice_plan': (C.c_int, [P(TgTcsr), i64, vp, i64, vp, i64, vp, vp, vp, sz, vp]),
+    'tg_tcsr_rows_splice_apply': (C.c_int, [P(TgTcsr), i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_node_rows_scatter': (C.c_int, [P(TgNodeRows), i32, vp, i64, vp]),
+    'tg_bitmap_scatter': (C.c_int, [vp, vp, i64, vp, i64, vp]),
+    'tg_tcsr_rows_pack_host': (C.c_int, [P(TgTcsr), vp, i64, vp, vp, vp, vp]),
+    'tg_tcsr_rows_splice_host': (C.c_int, [P(TgTcsr), i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'tg_node_rows_scatter_host': (C.c_int, [P(TgNodeRows), i32, vp, i64]),
+    'tg_bitmap_scatter_host': (C.c_int, [vp, vp, i64, vp, i64]),
     'tg_walk_candidates_lds_bytes': (sz, [i32, vp, i32]),
     'tg_walk_candidates': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     'tg_walk_candidates_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -1424,3 +1424,178 @@ def bitmap_compact(bits: Tensor, old_of: Tensor, n_in: int, n_out: int, out: Opt
         with torch.cuda.device(dev):
             check(lib.tg_bitmap_compact(ptr(bits), n_in, ptr(old_of), n_out, ptr(out), stream_ptr(dev)), 'tg_bitmap_compact')
     return out
+
+
+# ---- incremental online state files: pack / splice T-CSR rows, scatter rows and bits (tg_journal.hip and its host twins) ---
+SPLICE_CLASSES = ('ROWS', 'OFF', 'PTR')
+_SPLICE_WHAT = ('rows[{i}] is no id below the new node count or does not ascend',
+                'off[{i}] is no offset into the pack (off[0] == 0, non-decreasing, off[D] == the packed length)',
+                'row {i} of the old graph has no valid bounds')
+
+
+def SPLICE_TEXT(cls: int, first=None) -> str:
+    """The message of a non-zero tcsr_rows_splice class."""
+    if not 1 <= cls <= len(SPLICE_CLASSES):
+        return 'a clean splice' if cls == 0 else f'error class {cls}'
+    return f'{SPLICE_CLASSES[cls - 1]}: ' + _SPLICE_WHAT[cls - 1].format(i='?' if first is None else first)
+
+
+def _journal_tcsr(what: str, arrays_or_graph):
+    """a Graph (its device arrays) or four tensors (indptr int64 [N + 1], ts float64, nbr int32, eid int32 [P]) on one
+    device - CPU tensors take the host twins -> (struct, the tensors that keep it alive, device)"""
+    if hasattr(arrays_or_graph, 'tcsr'):
+        g = arrays_or_graph.tcsr
+        return g, arrays_or_graph._dev, arrays_or_graph._dev[0].device
+    keep = tuple(arrays_or_graph)
+    n, P = _verify_arrays(what, keep, False)
+    dev = keep[0].device
+    if any(a.device != dev for a in keep):
+        raise ValueError(f'{what}: the four arrays of a T-CSR live on one device')
+    return _lib.TgTcsr(n, P, *(ptr(a) for a in keep)), keep, dev
+
+
+def _journal_list(what: str, name: str, t, dtype, dev, numel=None) -> Tensor:
+    if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 1 and t.is_contiguous() and t.device == dev
+            and (numel is None or t.numel() == numel)):
+        got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f'{what}: {name} must be a contiguous 1-d {dtype} tensor'
+                         + (f' of {numel} entries' if numel is not None else '') + f' on {dev} (got {got})')
+    return t
+
+
+def tcsr_rows_pack(arrays_or_graph, rows: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The rows `rows` (int32, ascending, distinct) of a T-CSR, one after the other (tiger_hip.h: tg_tcsr_rows_pack_plan /
+    _apply; CPU tensors: the host twin) -> (off int64 [D + 1], ts float64, nbr int32, eid int32 [off[D]]).  On the arrays'
+    device and the current stream; ONE int64 is read back (the packed length), the outputs are allocated exactly."""
+    what = 'tcsr_rows_pack'
+    g, keep, dev = _journal_tcsr(what, arrays_or_graph)
+    rows = _journal_list(what, 'rows', rows, torch.int32, dev)
+    D = int(rows.numel())
+    if D > g.num_node:
+        raise ValueError(f'{what}: {D} rows of a graph of {g.num_node} nodes')
+    off = torch.empty(D + 1, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        r = rows.long()
+        ok = (r >= 0) & (r < g.num_node)
+        ip = keep[0]
+        cap = int((ip[r[ok] + 1] - ip[r[ok]]).clamp_(min=0).sum()) if D else 0
+        out = _entry_arrays(min(cap, g.num_entry), dev)
+        check(lib.tg_tcsr_rows_pack_host(C_.byref(g), ptr(rows), D, ptr(off), *(ptr(t) for t in out)), 'tg_tcsr_rows_pack_host')
+        n = int(off[-1])
+        return (off,) + tuple(t[:n].clone() if t.numel() != n else t for t in out)
+    with torch.cuda.device(dev):
+        nbytes = int(lib.tg_tcsr_rows_pack_workspace_bytes(D))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.tg_tcsr_rows_pack_plan(C_.byref(g), ptr(rows), D, ptr(off), ptr(ws), nbytes, stream_ptr(dev)),
+              'tg_tcsr_rows_pack_plan')
+        n = int(off[-1])  # the one read-back
+        out = _entry_arrays(n, dev)
+        check(lib.tg_tcsr_rows_pack_apply(C_.byref(g), ptr(rows), D, ptr(off), n, *(ptr(t) for t in out), stream_ptr(dev)),
+              'tg_tcsr_rows_pack_apply')
+    return (off,) + out
+
+
+def tcsr_rows_splice(arrays_or_graph, n_new: int, rows: Tensor, off: Tensor, pack, strict: bool = True):
+    """A NEW T-CSR over n_new >= num_node ids: row rows[j] is row j of the pack (off, and pack = (ts, nbr, eid) as
+    `tcsr_rows_pack` returns them), every other row the old one, empty for ids at and beyond the old num_node (tiger_hip.h:
+    tg_tcsr_rows_splice_plan / _apply; CPU tensors: the host twin) -> (code, first, arrays): code 0 and arrays = (indptr,
+    ts, nbr, eid), or a class of SPLICE_CLASSES (1-based) with its smallest offender and arrays None.  rows / off / pack are
+    untrusted as far as their CONTENTS go (dtypes, shapes and devices are checked here: ValueError); strict: a non-zero
+    code raises ValueError.  ONE read-back of three words.  The result still has to pass `tcsr_verify`."""
+    what = 'tcsr_rows_splice'
+    g, keep, dev = _journal_tcsr(what, arrays_or_graph)
+    n_new = int(n_new)
+    if n_new < g.num_node or n_new > 0x7FFFFFFF:
+        raise ValueError(f'{what}: n_new = {n_new} is outside [{g.num_node}, 2^31)')
+    rows = _journal_list(what, 'rows', rows, torch.int32, dev)
+    D = int(rows.numel())
+    if D > n_new:
+        raise ValueError(f'{what}: {D} rows for {n_new} node ids')
+    off = _journal_list(what, 'off', off, torch.int64, dev, D + 1)
+    if len(pack) != 3:
+        raise ValueError(f'{what}: the pack is (ts, nbr, eid)')
+    n_pack = int(pack[0].numel()) if torch.is_tensor(pack[0]) else -1
+    pack = tuple(_journal_list(what, name, t, dt, dev, n_pack)
+                 for name, t, dt in zip(('ts', 'nbr', 'eid'), pack, (torch.float64, torch.int32, torch.int32)))
+    if g.num_entry + n_pack > 0xFFFFFFFF:
+        raise ValueError(f'{what}: {g.num_entry} + {n_pack} entries are more than a T-CSR holds')
+    indptr = torch.empty(n_new + 1, dtype=torch.int64, device=dev)
+    if dev.type == 'cpu':
+        out3 = torch.empty(3, dtype=torch.int64)
+        out = _entry_arrays(g.num_entry + n_pack, dev)
+        check(lib.tg_tcsr_rows_splice_host(C_.byref(g), n_new, ptr(rows), D, ptr(off), n_pack, *(ptr(t) for t in pack),
+                                           ptr(indptr), *(ptr(t) for t in out), ptr(out3)), 'tg_tcsr_rows_splice_host')
+        n, code, first = (int(x) for x in out3)
+        if not code:
+            out = tuple(t[:n].clone() for t in out)
+    else:
+        with torch.cuda.device(dev):
+            out3 = torch.empty(3, dtype=torch.int64, device=dev)
+            nbytes = int(lib.tg_tcsr_rows_splice_workspace_bytes(n_new))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            check(lib.tg_tcsr_rows_splice_plan(C_.byref(g), n_new, ptr(rows), D, ptr(off), n_pack, ptr(indptr), ptr(out3),
+                                               ptr(ws), nbytes, stream_ptr(dev)), 'tg_tcsr_rows_splice_plan')
+            n, code, first = out3.tolist()  # the one read-back
+            if not code:
+                out = _entry_arrays(n, dev)
+                check(lib.tg_tcsr_rows_splice_apply(C_.byref(g), n_new, ptr(indptr), n, n_pack, *(ptr(t) for t in pack),
+                                                    *(ptr(t) for t in out), ptr(ws), nbytes, stream_ptr(dev)),
+                      'tg_tcsr_rows_splice_apply')
+    if code:
+        if strict:
+            raise ValueError(f'{what}: ' + SPLICE_TEXT(code, first))
+        return code, first, None
+    return 0, -1, (indptr,) + tuple(out)
+
+
+def node_rows_scatter(tables, ids: Tensor):
+    """ONE launch that scatters up to 8 packed per-node tables back by `ids` (tiger_hip.h: tg_node_rows_scatter, the inverse
+    of `node_rows_compact`; CPU tensors: its host twin).  tables: (src, dst) pairs of contiguous tensors of one dtype and
+    trailing shape on ids' device; for j < src.shape[0] <= ids.numel(): dst[ids[j]] = src[j], bit for bit; an id that is
+    no row of dst stores nothing.  ids: int32, distinct.  A row is the bytes of src[j]: a multiple of 16, or 8, 4 or 1.  dst
+    may be the leading rows of a larger backing store; src and dst must not overlap.  ValueError: more than 8 tables,
+    tensors of other shapes / dtypes / devices, another row width."""
+    what = 'node_rows_scatter'
+    tables = list(tables)
+    if not (torch.is_tensor(ids) and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()):
+        raise ValueError(f'{what}: ids must be a contiguous 1-d int32 tensor')
+    dev = ids.device
+    if len(tables) > _lib.TG_NODE_ROWS_MAX:
+        raise ValueError(f'{what}: {len(tables)} tables in one call (at most {_lib.TG_NODE_ROWS_MAX})')
+    descs = (_lib.TgNodeRows * max(len(tables), 1))()
+    for i, (src, dst) in enumerate(tables):
+        if not (torch.is_tensor(src) and torch.is_tensor(dst) and src.dim() >= 1 and src.is_contiguous() and dst.is_contiguous()
+                and src.dtype == dst.dtype and src.shape[1:] == dst.shape[1:] and src.device == dev and dst.device == dev):
+            raise ValueError(f'{what}: table {i} must be a (src, dst) pair of contiguous tensors of one dtype and row shape on {dev}')
+        row_bytes = src.element_size()
+        for s in src.shape[1:]:
+            row_bytes *= int(s)
+        if src.shape[0] > ids.numel() or dst.shape[0] < 1:
+            raise ValueError(f'{what}: table {i} brings {src.shape[0]} rows, ids has {ids.numel()}')
+        if row_bytes not in (1, 4, 8) and (row_bytes < 16 or row_bytes % 16):
+            raise ValueError(f'{what}: table {i} has rows of {row_bytes} bytes (a multiple of 16, or 8, 4 or 1)')
+        descs[i] = _lib.TgNodeRows(ptr(src), ptr(dst), row_bytes, dst.shape[0], src.shape[0])
+    if dev.type == 'cpu':
+        check(lib.tg_node_rows_scatter_host(descs, len(tables), ptr(ids), ids.numel()), 'tg_node_rows_scatter_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_node_rows_scatter(descs, len(tables), ptr(ids), ids.numel(), stream_ptr(dev)), 'tg_node_rows_scatter')
+
+
+def bitmap_scatter(flags: Tensor, ids: Tensor, bits: Tensor, n_ids: int):
+    """bit ids[j] of `bits` (a `new_bitmap` over n_ids ids, IN PLACE) = (flags[j] != 0); every other bit keeps its value
+    (tiger_hip.h: tg_bitmap_scatter; CPU tensors: its host twin).  flags uint8 [n], ids int32 [n], distinct; an id outside
+    [0, n_ids) stores nothing."""
+    what = 'bitmap_scatter'
+    dev = bits.device
+    n_ids = int(n_ids)
+    ids = _journal_list(what, 'ids', ids, torch.int32, dev)
+    flags = _journal_list(what, 'flags', flags, torch.uint8, dev, ids.numel())
+    if bits.dtype != torch.int64 or bits.dim() != 1 or not bits.is_contiguous() or n_ids < 1 or bits.numel() < bitmap_words(n_ids):
+        raise ValueError(f'{what}: bits must be a contiguous int64 bitmap of at least {bitmap_words(max(n_ids, 1))} words '
+                         f'({n_ids} ids)')
+    if dev.type == 'cpu':
+        check(lib.tg_bitmap_scatter_host(ptr(flags), ptr(ids), ids.numel(), ptr(bits), n_ids), 'tg_bitmap_scatter_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_bitmap_scatter(ptr(flags), ptr(ids), ids.numel(), ptr(bits), n_ids, stream_ptr(dev)), 'tg_bitmap_scatter')

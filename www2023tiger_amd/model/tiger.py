@@ -147,9 +147,200 @@ class ChangeTracker:
         self.whole, self.reason = True, 'compact_nodes / compact_keys renumbered the node ids'
 
 
+class OnlineJournal:
+    """What changed since the last saved online state file, and the writer of the next one (TIGE.journal,
+    TIGE.apply_online_delta).  A sink of the model's writers beside the ChangeTracker and independent of it:
+    both may be installed, clearing one loses nothing for the other.  Two bitmaps over the node ids - state_bits: the
+    per-node state row (both memories, mailbox, node-feature row) changed; graph_bits: the T-CSR row changed - so a restart
+    does not drag T-CSR rows into a file.  whole: the next file must be a base (`reason` says why): everything that sets a
+    tracker's `whole`, and a graph whose eids were renumbered (`release_edge_rows` shares indptr with its parent: no
+    degree changes).  As of the last save: chain (the id of the base the files follow), seq (0: the base), and the counts a
+    delta states as its "before": edge-table rows, n_nodes, the graph's nodes and entries.
+    REPLAYS OF A CAPTURED DEVICE GRAPH ARE INVISIBLE, exactly as for the tracker: whoever replays captured steps between
+    two saves calls `mark(ids)` / `mark_all(...)` itself, as for writes through raw tensors.
+    NOT in a delta: parameters (deltas are for eval() mode), optimiser state, `uptodate` bitmaps, snapshots, held eids.
+    A dirty T-CSR row is saved WHOLE: a hub row costs its full length per delta unless `forget(keep_last=M)` bounds it.
+    Keeping the files in order and durable is the caller's job."""
+    DELTA_FORMAT, DELTA_VERSION = 'tiger-online-delta', 1
+
+    def __init__(self, model):
+        self._model = weakref.ref(model)
+        self.n_nodes = int(model.n_nodes)
+        dev = model.device
+        self.state_bits = hip_ops.new_bitmap(self.n_nodes, dev)
+        self.graph_bits = hip_ops.new_bitmap(self.n_nodes, dev)
+        self.whole, self.reason = True, 'no base has been saved on this chain yet'
+        self.chain, self.seq, self.saved = None, -1, None
+
+    @property
+    def model(self):
+        return self._model()
+
+    # ---- the sink the model's writers feed (the interface of ChangeTracker) ------------------------------------------
+    def fit(self, n_nodes: int):
+        if n_nodes > self.n_nodes:
+            self.state_bits = hip_ops.bitmap_grown(self.state_bits, n_nodes)
+            self.graph_bits = hip_ops.bitmap_grown(self.graph_bits, n_nodes)
+            self.n_nodes = int(n_nodes)
+
+    def admitted(self, n0: int, n1: int):
+        """a growth that gave the ids [n0, n1) feature rows: their state rows are no longer those of a grown table"""
+        self.fit(n1)
+        if n1 > n0:
+            self.mark(torch.arange(n0, n1, device=self.state_bits.device))
+
+    def mark(self, ids):
+        ids = torch.as_tensor(ids).to(self.state_bits.device).long().reshape(-1)
+        if ids.numel() and not self.whole:
+            hip_ops.bitmap_mark(ids, self.state_bits, self.n_nodes)
+
+    def mark_graph(self, old, new):
+        if old is new or self.whole:
+            return
+        if old is None or new is None or getattr(old, '_dev', None) is None or getattr(new, '_dev', None) is None:
+            return self.mark_all('a graph without device arrays was swapped in or out')
+        self.fit(max(old.num_node, new.num_node))
+        if old._dev[0] is not new._dev[0]:
+            hip_ops.bitmap_mark_degree_diff(old, new, self.graph_bits)
+        elif any(a is not b for a, b in zip(old._dev, new._dev)):
+            self.mark_all('the graph was renumbered: every edge id (or neighbour) changed under unchanged row bounds')
+
+    def mark_all(self, reason: str):
+        if not self.whole:
+            self.whole, self.reason = True, reason
+
+    def renumbered(self, n_nodes: int):
+        self.n_nodes = int(n_nodes)
+        self.state_bits = hip_ops.new_bitmap(self.n_nodes, self.state_bits.device)
+        self.graph_bits = hip_ops.new_bitmap(self.n_nodes, self.state_bits.device)
+        self.whole, self.reason = True, 'compact_nodes / compact_keys renumbered the node ids'
+
+    # ---- files ------------------------------------------------------------------------------------------------------
+    def _position(self, chain: int, seq: int):
+        """the model IS the state of file `seq` of `chain`: nothing is dirty"""
+        m = self.model
+        self.fit(m.n_nodes)
+        self.state_bits.zero_()
+        self.graph_bits.zero_()
+        self.whole, self.reason = False, None
+        self.chain, self.seq = int(chain), int(seq)
+        fg, g = m.raw_feat_getter, m.graph
+        entries = int(g.tcsr.num_entry) if m.device.type == 'cuda' else len(g._host_tcsr()[1])  # (a host model: bases only)
+        self.saved = dict(efeat_rows=0 if fg.efeats is None else int(fg.efeats.shape[0]), n_nodes=int(m.n_nodes),
+                          graph_nodes=int(g.num_node), num_entry=entries)
+
+    @staticmethod
+    def per_node_tables(m):
+        """name -> the per-node tensors a delta carries rows of (the two REAL memories, not the alias modules), in the order
+        they are gathered; the mailbox's has-message bit travels as one byte per id beside them"""
+        L, R, S, fg = m.left_memory, m.right_memory, m.msg_store, m.raw_feat_getter
+        out = {f'{side}.{name}': getattr(mem, name) for side, mem in (('left', L), ('right', R)) for name in mem.COMPACT_TABLES}
+        out.update(node_msg_vals=S.node_msg_vals, node_msg_ts=S.node_msg_ts)
+        if fg.nfeats is not None:
+            out['nfeats'] = fg.nfeats
+        return out
+
+    def _refusals(self, what: str):
+        m = self.model
+        if m is None:
+            raise RuntimeError(f'{what}: the model of this journal is gone')
+        if m._journal is not self:
+            raise RuntimeError(f'{what}: this journal is no longer the model\'s (load_online installed another)')
+        m._refuse_partitioned(what)
+        if m.training:
+            raise RuntimeError(f'{what}: online state files are written in eval() mode (the streaming state of a served model)')
+        if not m.raw_feat_getter.pin_mem:
+            raise NotImplementedError(f'{what}: the feature tables live in pinned host memory (register_buffer=False)')
+        if m.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: a state file cannot be written while a stream is being captured into a graph')
+        return m
+
+    @torch.no_grad()
+    def save(self, f) -> str:
+        """Write the next file of the chain to `f` (a path or a file object) -> 'base' or 'delta'.  The first save, and any
+        save after `whole` was set, is a BASE: `online_state()` plus `chain` (a new id) and `seq` = 0 - a file `load_online`
+        reads as any other.  Every other save is a DELTA (format 'tiger-online-delta', one `torch.save` dict, loadable with
+        weights_only=True): the rows of the ids of state_bits from every per-node tensor, the edge-table rows appended
+        since the last save, the T-CSR rows of graph_bits packed (tg_tcsr_rows_pack), the graph's small state whole, and
+        the counts before and after.  Device work of a delta: two bitmap listings, two row gathers (8 + 1 tables), one bit
+        gather, the pack's plan and copy; two read-backs (both list counts together; the packed length) besides the copies
+        of the payload.  Afterwards both bitmaps are clear and seq has advanced; if the save raises, the journal is
+        unchanged.  Refused: what `save_online` / `load_online` refuse (training mode, a partitioned model, tables in pinned
+        host memory, a stream capture in progress)."""
+        m = self._refusals('OnlineJournal.save')
+        m._poll_train_errors()
+        if self.whole or self.chain is None:
+            chain = int.from_bytes(os.urandom(8), 'little') >> 1
+            st = m.online_state()
+            st.update(chain=chain, seq=0)
+            torch.save(st, f)
+            self._position(chain, 0)
+            return 'base'
+        if m.device.type != 'cuda':
+            raise RuntimeError(f'OnlineJournal.save: the model lives on {m.device}; deltas are cut on the GPU')
+        st = self._delta(m)
+        torch.save(st, f)
+        self._position(self.chain, self.seq + 1)
+        return 'delta'
+
+    def _listed(self, m):
+        """the set bits of both bitmaps as ascending int32 lists: two listings, ONE read-back of both counts"""
+        n = int(m.n_nodes)
+        self.fit(n)
+        a, b = hip_ops.unique_compact(self.state_bits, n, n), hip_ops.unique_compact(self.graph_bits, n, n)
+        ca, cb = torch.stack([a['count'][0], b['count'][0]]).tolist()
+        return a['ids'][:ca].int(), b['ids'][:cb].int()
+
+    def _delta(self, m) -> dict:
+        fg, S, g, dev = m.raw_feat_getter, m.msg_store, m.graph, m.device
+        g.tcsr  # (a graph that was never sampled from has no device arrays yet)
+        ids, rows = self._listed(m)
+        D = int(ids.numel())
+        cpu = lambda t: t.detach().to('cpu', copy=True)
+        packed = {}
+        tables = self.per_node_tables(m)
+        if D:
+            for name, t in tables.items():
+                row_bytes = t.element_size() * int(np.prod(t.shape[1:], dtype=np.int64))
+                if row_bytes not in (1, 4, 8) and row_bytes % 16:
+                    raise NotImplementedError(f'OnlineJournal.save: rows of {row_bytes} bytes ({name}) are not gathered '
+                                              '(a multiple of 16, or 8, 4 or 1)')
+            pairs = [(t, torch.empty((D,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)) for t in tables.values()]
+            for i in range(0, len(pairs), hip_ops._lib.TG_NODE_ROWS_MAX):  # (as few launches as the table limit allows)
+                hip_ops.node_rows_compact(pairs[i:i + hip_ops._lib.TG_NODE_ROWS_MAX], ids)
+            words = hip_ops.bitmap_compact(S.has_msg_bits, ids, int(m.n_nodes), D)
+            j = torch.arange(D, device=dev)
+            has = ((words[j >> 6] >> (j & 63)) & 1).to(torch.uint8)
+            packed = {name: cpu(dst) for name, (_, dst) in zip(tables, pairs)}
+        else:
+            packed = {name: torch.empty((0,) + tuple(t.shape[1:]), dtype=t.dtype) for name, t in tables.items()}
+            has = torch.empty(0, dtype=torch.uint8)
+        off, ts, nbr, eid = hip_ops.tcsr_rows_pack(g, rows)
+        before = self.saved
+        rows_now = 0 if fg.efeats is None else int(fg.efeats.shape[0])
+        if rows_now < before['efeat_rows'] or m.n_nodes < before['n_nodes'] or g.num_node < before['graph_nodes']:
+            raise RuntimeError('OnlineJournal.save: a table or the graph shrank and nothing told the journal (mark_all)')
+        kind, key, pos, has_gauss, gauss = g.rng.get_state()
+        return dict(
+            format=self.DELTA_FORMAT, version=self.DELTA_VERSION, chain=int(self.chain), seq=int(self.seq) + 1,
+            fingerprint=m._online_fingerprint(),
+            n_nodes_before=before['n_nodes'], n_nodes_after=int(m.n_nodes),
+            graph_nodes_before=before['graph_nodes'], graph_nodes_after=int(g.num_node),
+            num_entry_before=before['num_entry'], num_entry_after=int(g.tcsr.num_entry),
+            efeat_rows_before=before['efeat_rows'], efeat_rows_after=rows_now,
+            ids=cpu(ids), rows_of=packed, has_msg=cpu(has),
+            efeats_tail=None if fg.efeats is None else cpu(fg.efeats[before['efeat_rows']:rows_now]),
+            rows=cpu(rows), off=cpu(off), ts=cpu(ts), nbr=cpu(nbr), eid=cpu(eid),
+            graph_state=dict(t_last=float(g._t_last), time_ordered=bool(g._time_ordered), rng_kind=str(kind),
+                             rng_key=torch.from_numpy(key.astype(np.int64)), rng_pos=int(pos), rng_has_gauss=int(has_gauss),
+                             rng_cached_gaussian=float(gauss),
+                             mt_state=None if g._mt is None else g._mt.detach().to('cpu', copy=True)))
+
+
 class TIGE(nn.Module):
     _born_rows = None
     _tracker = None          # ChangeTracker (track_changes), None: nothing is recorded
+    _journal = None          # OnlineJournal (journal), None: nothing is recorded
     last_refreshed = None    # (n_dirty, n_by_age) of the latest refresh_catalogue
 
     @staticmethod
@@ -363,10 +554,23 @@ class TIGE(nn.Module):
     def graph(self, new_obj):
         old = self.temporal_embedding_fn.graph
         self.temporal_embedding_fn.graph = new_obj
-        if self._tracker is not None:
-            self._tracker.mark_graph(old, new_obj)
+        for sink in self._sinks():
+            sink.mark_graph(old, new_obj)
 
     # ---- change tracking ----------------------------------------------------
+    def _sinks(self):
+        """whoever records what the model's writers change: the snapshot tracker (track_changes), the journal (journal)"""
+        return tuple(s for s in (self._tracker, self._journal) if s is not None)
+
+    def journal(self) -> OnlineJournal:
+        """-> the model's OnlineJournal (installed on first use): from now on the model's own writers record
+        which nodes' state rows and which T-CSR rows change, and `journal().save(f)` writes a base file first and then
+        deltas that hold only those rows (`load_online(base)` + `apply_online_delta(delta)`, in order, rebuild the model
+        bit for bit).  Independent of `track_changes()`: both may be installed at once and neither clears the other.
+        `load_online` of a base that carries chain / seq installs a journal positioned there."""
+        if self._journal is None:
+            self._journal = OnlineJournal(self)
+        return self._journal
     def track_changes(self, enable: bool = True) -> Optional[ChangeTracker]:
         """Start (or, enable=False, stop) recording which nodes' state rows and T-CSR rows change -> the ChangeTracker
         (None when switched off).  Opt-in: nothing is recorded, and nothing costs anything, while it is off.  With a
@@ -388,12 +592,12 @@ class TIGE(nn.Module):
         return self._tracker
 
     def _mark(self, ids):
-        if self._tracker is not None:
-            self._tracker.mark(ids)
+        for sink in self._sinks():
+            sink.mark(ids)
 
     def _mark_all(self, reason: str):
-        if self._tracker is not None:
-            self._tracker.mark_all(reason)
+        for sink in self._sinks():
+            sink.mark_all(reason)
 
     def _mark_step(self, buf, io):
         """what one step over the batch in `buf` writes (io: its tg_step_io), for launch_step and for the training /
@@ -401,18 +605,16 @@ class TIGE(nn.Module):
         one wavefront per unique positive node); the in-step restart loop re-initialises rows no host list names, a
         resident stream's batch is named by an offset on the device, and a step that is being captured into a device
         graph runs again at every replay, which the host does not see: those mark everything."""
-        tr = self._tracker
-        if tr is None:
-            return
-        if io.lazy and getattr(buf, '_lazy_collate', None) is None:
-            tr.mark_all('a step with the in-step lazy-restart loop')
-        elif buf.offset is not None:
-            tr.mark_all('a step over a resident stream: its batch offset lives on the device')
-        elif self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
-            tr.mark_all('a step captured into a device graph: its replays are invisible to the host')
-        else:
-            tr.mark(buf.src)
-            tr.mark(buf.dst)
+        for tr in self._sinks():
+            if io.lazy and getattr(buf, '_lazy_collate', None) is None:
+                tr.mark_all('a step with the in-step lazy-restart loop')
+            elif buf.offset is not None:
+                tr.mark_all('a step over a resident stream: its batch offset lives on the device')
+            elif self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                tr.mark_all('a step captured into a device graph: its replays are invisible to the host')
+            else:
+                tr.mark(buf.src)
+                tr.mark(buf.dst)
 
     @property
     def device(self):
@@ -1821,7 +2023,7 @@ class TIGE(nn.Module):
                 buf._pf_state.value = 2  # made, but for another state / offset / graph: the step discards it
             before = buf._pf_state.value
         self._step_serial = getattr(self, '_step_serial', 0) + 1
-        if self._tracker is not None and not (buf.embed_only or buf.io.collate_only):
+        if (self._tracker is not None or self._journal is not None) and not (buf.embed_only or buf.io.collate_only):
             self._mark_step(buf, buf.io)
         check(lib.tg_stream_step(C.byref(m), C.byref(g), C.byref(buf.io), ptr(buf.ws), buf.ws.numel(),
                                  stream_ptr(self.device)), 'tg_stream_step')
@@ -2024,7 +2226,7 @@ class TIGE(nn.Module):
 
     def _grow(self, num_node: int, nfeats, reserve, graph) -> bool:
         """grow_nodes after its refusals: tables, counts, graph, caches"""
-        eager = self._pending is not None
+        eager, n0 = self._pending is not None, int(self.n_nodes)
         moved = [self.left_memory.grow(num_node, reserve), self.right_memory.grow(num_node, reserve),
                  self.msg_store.grow(num_node, reserve), self.raw_feat_getter.append_node_rows(nfeats, reserve)]
         self.n_nodes = num_node
@@ -2032,6 +2234,8 @@ class TIGE(nn.Module):
             self.restarter_fn.n_nodes = num_node
         if self._tracker is not None:
             self._tracker.fit(num_node)  # (the admitted ids are born with zero rows: a snapshot cannot have read them)
+        if self._journal is not None:  # (rows a delta's own growth does not rebuild: the feature rows the ids came with)
+            self._journal.admitted(n0 if torch.is_tensor(nfeats) else num_node, num_node)
         self.graph = graph  # (the setter: the restarter follows)
         self._touch()
         self.invalidate_struct()
@@ -2130,8 +2334,8 @@ class TIGE(nn.Module):
         self.n_nodes = n_new
         if getattr(self, 'restarter_fn', None) is not None:
             self.restarter_fn.n_nodes = n_new
-        if self._tracker is not None:  # another numbering: a bitmap over the old ids means nothing any more
-            self._tracker.renumbered(n_new)  # (a new epoch: no snapshot from before is refreshable)
+        for sink in self._sinks():  # another numbering: a bitmap over the old ids means nothing any more
+            sink.renumbered(n_new)  # (the tracker: a new epoch, no snapshot from before is refreshable)
         self.graph = child  # (the setter: the restarter follows; snapshot stamps go stale)
         self._touch()
         self.invalidate_struct()
@@ -2489,6 +2693,8 @@ class TIGE(nn.Module):
             return None
         child = graph.renumbered(res.remap, res.eid_out)
         self.graph = child
+        if self._journal is not None:  # (a trim or an erase in the same call hides the shared indptr from the setter)
+            self._journal.mark_all('release_edge_rows packed the edge table and renumbered every edge id')
         fg.adopt_edge_rows(res)
         self.invalidate_struct()
         self.last_release = res
@@ -2569,6 +2775,12 @@ class TIGE(nn.Module):
         missing = [k for k in ('fingerprint', 'n_nodes', 'state_dict', 'mailbox', 'nfeats', 'efeats', 'graph') if k not in st]
         if missing:
             raise ValueError(f'{what}: the saved state lacks {missing}')
+        chain = st.get('chain')  # (a base of an OnlineJournal carries chain and seq; files without them load as before)
+        if chain is not None or st.get('seq') is not None:
+            for k in ('chain', 'seq'):
+                v = st.get(k)
+                if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                    raise ValueError(f'{what}: {k} = {v!r} (a base of a journal carries both as non-negative ints)')
         mine = self._online_fingerprint()
         if st['fingerprint'] != mine:
             theirs = st['fingerprint'] if isinstance(st['fingerprint'], dict) else {}
@@ -2645,7 +2857,206 @@ class TIGE(nn.Module):
         self._pending = self._pending_stamp = None
         if eager:
             self.eager_updates()
+        if chain is not None:  # a base of a journal: the model is file 0 of that chain, nothing is dirty
+            self._journal = OnlineJournal(self)
+            self._journal._position(chain, st['seq'])
         return graph
+
+    def _drop_derived(self):
+        """what was derived from the old state, graph or tables, as after a growth (the tail of load_online)"""
+        self._touch()
+        self.invalidate_struct()
+        eager = self._pending is not None
+        self._step_ws = {k: v for k, v in self._step_ws.items() if k == 'rng'}
+        self._gtab = self._ctab = self._gtab_stamp = None
+        self._pending = self._pending_stamp = None
+        if eager:
+            self.eager_updates()
+
+    @torch.no_grad()
+    def apply_online_delta(self, f_or_state, *, verify: bool = True):
+        """Become the model that wrote the next delta of the journal's chain (`OnlineJournal.save`) -> the new graph.
+        f_or_state: a path, a file object or the loaded dict.  Applied once per file, in order, on a model that loaded the
+        chain's base with `load_online` (or wrote the files itself): a fresh model that loads the base and applies the
+        deltas is, bit for bit, the model that saved them - every tensor of `online_state()`, the graph arrays included,
+        and everything it computes afterwards.
+        A DELTA IS UNTRUSTED INPUT.  Checked before anything is written, each with a ValueError that names the field:
+        format, version, fingerprint, that chain and seq are the expected successor, the "before" counts against the
+        model, n_nodes_after >= n_nodes, dtypes and shapes of every tensor, ids and rows strictly ascending inside their
+        counts, off[0] == 0 / non-decreasing / off[D] == the packed length.  The new graph is then BUILT beside the old one
+        (tg_tcsr_rows_splice: the parent is only read; its one read-back repeats the checks on rows / off and those of the
+        old row bounds), must hold num_entry_after entries, and goes through `tg_tcsr_verify` against the NEW edge-table row
+        count and its latest time against t_max, before any sampler or table sees it (verify=False skips those two, as in
+        `load_online`).  Only then: the tables grow to n_nodes_after (the `grow_nodes` machinery; its refusals apply and are
+        made first), the edge-table tail is appended, the state rows are scattered (tg_node_rows_scatter: 8 + 1 tables in
+        two launches; tg_bitmap_scatter), the graph goes in through the setter and derived tables and stamps are dropped
+        as `load_online` drops them.  The journal then stands at the delta's seq with nothing dirty; a ChangeTracker sees
+        the applied ids and rows as changes.  IF THE CALL RAISES, EVERY BUFFER, TABLE AND THE GRAPH ARE WHAT THEY WERE.
+        Refused as `load_online`: a partitioned model, training mode, tables in pinned host memory, a stream capture in
+        progress; and a model without a journal, or one whose journal is dirty (the model has moved on since the last
+        file: it is no longer the delta's predecessor)."""
+        what = 'apply_online_delta'
+        self._refuse_partitioned(what)
+        if self.training:
+            raise RuntimeError(f'{what}: a delta is applied in eval() mode (the streaming state of a served model)')
+        fg, S, J = self.raw_feat_getter, self.msg_store, self._journal
+        if not fg.pin_mem:
+            raise NotImplementedError(f'{what}: the feature tables live in pinned host memory (register_buffer=False)')
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'{what}: the model lives on {self.device}; deltas are applied on the GPU')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: tables cannot be written while a stream is being captured into a graph')
+        st = f_or_state if isinstance(f_or_state, dict) else torch.load(f_or_state, map_location='cpu', weights_only=True)
+        if not isinstance(st, dict) or st.get('format') != OnlineJournal.DELTA_FORMAT:
+            raise ValueError(f'{what}: format - not a saved online delta')
+        if st.get('version') != OnlineJournal.DELTA_VERSION:
+            raise ValueError(f"{what}: version {st.get('version')!r} of the format is unknown (this library reads "
+                             f'{OnlineJournal.DELTA_VERSION})')
+        counts = ('n_nodes', 'graph_nodes', 'num_entry', 'efeat_rows')
+        keys = ('chain', 'seq', 'fingerprint', 'ids', 'rows_of', 'has_msg', 'efeats_tail', 'rows', 'off', 'ts', 'nbr', 'eid',
+                'graph_state') + tuple(f'{c}_{w}' for c in counts for w in ('before', 'after'))
+        missing = [k for k in keys if k not in st]
+        if missing:
+            raise ValueError(f'{what}: the delta lacks {missing}')
+        mine = self._online_fingerprint()
+        if st['fingerprint'] != mine:
+            theirs = st['fingerprint'] if isinstance(st['fingerprint'], dict) else {}
+            diff = {k: (theirs.get(k), v) for k, v in mine.items() if theirs.get(k) != v}
+            raise ValueError(f'{what}: fingerprint - the delta is of another model - (saved, this one): {diff}')
+        isint = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        for k in ('chain', 'seq') + tuple(f'{c}_{w}' for c in counts for w in ('before', 'after')):
+            if not isint(st[k]) or st[k] < 0:
+                raise ValueError(f'{what}: {k} = {st[k]!r}')
+        if J is None or J.chain is None:
+            raise ValueError(f'{what}: chain - this model follows no chain (load the base with load_online first)')
+        if st['chain'] != J.chain:
+            raise ValueError(f"{what}: chain {st['chain']} is not the chain this model follows ({J.chain})")
+        if st['seq'] != J.seq + 1:
+            raise ValueError(f"{what}: seq {st['seq']} is not the successor of the file this model stands at ({J.seq})")
+        if J.whole or J.saved is None:
+            raise ValueError(f'{what}: seq - the model has left the chain since file {J.seq} ({J.reason}); load a base')
+        g_old = self.graph
+        g_old.tcsr  # (a graph that was never sampled from has no device arrays yet)
+        rows_now = 0 if fg.efeats is None else int(fg.efeats.shape[0])
+        have = dict(n_nodes=int(self.n_nodes), graph_nodes=int(g_old.num_node), num_entry=int(g_old.tcsr.num_entry),
+                    efeat_rows=rows_now)
+        for c in counts:
+            if st[f'{c}_before'] != have[c]:
+                raise ValueError(f"{what}: {c}_before = {st[f'{c}_before']}, but the model has {have[c]}")
+        n0, n1 = have['n_nodes'], st['n_nodes_after']
+        gn1, P1, er1 = st['graph_nodes_after'], st['num_entry_after'], st['efeat_rows_after']
+        if n1 < n0 or n1 > 0x7FFFFFFF:
+            raise ValueError(f'{what}: n_nodes_after = {n1} is below the model\'s {n0} (node ids are never released)')
+        if gn1 < have['graph_nodes'] or gn1 > n1:
+            raise ValueError(f"{what}: graph_nodes_after = {gn1} is outside [{have['graph_nodes']}, {n1}]")
+        if er1 < rows_now or P1 > 0xFFFFFFFF:
+            raise ValueError(f'{what}: efeat_rows_after = {er1} / num_entry_after = {P1} do not fit')
+        # -- dtypes and shapes
+
+        def tensor(name, v, dtype, shape):
+            if not torch.is_tensor(v) or v.dtype != dtype or tuple(v.shape) != tuple(shape):
+                got = f'{v.dtype} {tuple(v.shape)}' if torch.is_tensor(v) else type(v).__name__
+                raise ValueError(f'{what}: {name} is {got}, wanted {dtype} {tuple(shape)}')
+            return v.contiguous()
+
+        def ascending(name, v, hi):
+            if v.numel() and (int(v[0]) < 0 or int(v[-1]) >= hi or bool((v[1:] <= v[:-1]).any())):
+                raise ValueError(f'{what}: {name} must ascend strictly inside [0, {hi})')
+
+        ids = st['ids']
+        D = int(ids.numel()) if torch.is_tensor(ids) and ids.dim() == 1 else -1
+        ids = tensor('ids', ids, torch.int32, (max(D, 0),))
+        ascending('ids', ids, n1)
+        tables = OnlineJournal.per_node_tables(self)
+        packed = st['rows_of']
+        if not isinstance(packed, dict) or set(packed) != set(tables):
+            raise ValueError(f'{what}: rows_of must hold the rows of {sorted(tables)}')
+        packed = {k: tensor(f'rows_of[{k!r}]', packed[k], t.dtype, (D,) + tuple(t.shape[1:])) for k, t in tables.items()}
+        has = tensor('has_msg', st['has_msg'], torch.uint8, (D,))
+        tail = st['efeats_tail']
+        if (tail is None) != (fg.efeats is None):
+            raise ValueError(f'{what}: efeats_tail - the delta has {"a" if tail is not None else "no"} edge table, this model '
+                             f'{"has one" if fg.efeats is not None else "none"}')
+        if tail is not None:
+            tail = tensor('efeats_tail', tail, fg.efeats.dtype, (er1 - rows_now, fg.efeats.shape[1]))
+        elif er1 != rows_now:
+            raise ValueError(f'{what}: efeat_rows_after = {er1} for a model without an edge table')
+        rows = st['rows']
+        Dg = int(rows.numel()) if torch.is_tensor(rows) and rows.dim() == 1 else -1
+        rows = tensor('rows', rows, torch.int32, (max(Dg, 0),))
+        ascending('rows', rows, gn1)
+        off = tensor('off', st['off'], torch.int64, (Dg + 1,))
+        n_pack = int(st['ts'].numel()) if torch.is_tensor(st['ts']) and st['ts'].dim() == 1 else -1
+        pack = tuple(tensor(k, st[k], dt, (max(n_pack, 0),))
+                     for k, dt in (('ts', torch.float64), ('nbr', torch.int32), ('eid', torch.int32)))
+        if int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) or int(off[-1]) != n_pack:
+            raise ValueError(f'{what}: off must start at 0, never decrease and end at the packed length {n_pack}')
+        if have['num_entry'] + n_pack > 0xFFFFFFFF:
+            raise ValueError(f'{what}: ts - {n_pack} packed entries beside {have["num_entry"]} are more than a T-CSR holds')
+        gs = st['graph_state']
+        gkeys = ('t_last', 'time_ordered', 'rng_kind', 'rng_key', 'rng_pos', 'rng_has_gauss', 'rng_cached_gaussian', 'mt_state')
+        if not isinstance(gs, dict) or any(k not in gs for k in gkeys):
+            raise ValueError(f'{what}: graph_state must hold {gkeys}')
+        key, mt = gs['rng_key'], gs['mt_state']
+        if (not isinstance(gs['t_last'], float) or not isinstance(gs['time_ordered'], bool) or gs['rng_kind'] != 'MT19937'
+                or not torch.is_tensor(key) or key.dtype != torch.int64 or tuple(key.shape) != (624,) or int(key.min()) < 0
+                or int(key.max()) > 0xFFFFFFFF or not isint(gs['rng_pos']) or not 0 <= gs['rng_pos'] <= 624
+                or not isint(gs['rng_has_gauss']) or not isinstance(gs['rng_cached_gaussian'], float)):
+            raise ValueError(f'{what}: graph_state holds no latest time, time-ordered flag and MT19937 state')
+        if mt is not None and (not torch.is_tensor(mt) or mt.dtype != torch.int32 or tuple(mt.shape) != (625,)
+                               or not 0 <= int(mt[624]) <= 624):
+            raise ValueError(f'{what}: graph_state[\'mt_state\'] is no int32 [625] device MT19937 state')
+        if n1 > n0:
+            self._grow_refusals(what, n1, None, None)
+        # -- the new graph, built beside the old one: nothing of it reaches a sampler or a table before it has passed
+        dev = self.device
+        up = lambda t: t.to(dev)
+        code, first, arrays = hip_ops.tcsr_rows_splice(g_old, gn1, up(rows), up(off), tuple(up(t) for t in pack), strict=False)
+        if code:
+            field = ('rows', 'off', 'the model\'s own graph')[code - 1]
+            raise ValueError(f'{what}: {field} - ' + hip_ops.SPLICE_TEXT(code, first))
+        if int(arrays[1].numel()) != P1:
+            raise ValueError(f'{what}: num_entry_after = {P1}, but the spliced graph holds {arrays[1].numel()} entries')
+        if verify:
+            vcode, vfirst, t_max = hip_ops.tcsr_verify(arrays, er1 if fg.efeats is not None else None)
+            if vcode:
+                raise ValueError(f'{what}: the spliced graph is ' + hip_ops.TCSR_VERIFY_TEXT(vcode, vfirst))
+            if not gs['t_last'] >= t_max:
+                raise ValueError(f"{what}: graph_state['t_last'] = {gs['t_last']} is below the largest time of the entries "
+                                 f'({t_max})')
+        child = g_old._child(num_node=gn1)
+        child.rng = np.random.RandomState()
+        child.rng.set_state((str(gs['rng_kind']), key.numpy().astype(np.uint32), int(gs['rng_pos']), int(gs['rng_has_gauss']),
+                             float(gs['rng_cached_gaussian'])))
+        child._time_ordered, child._t_last, child._mt_saved = bool(gs['time_ordered']), float(gs['t_last']), None
+        child._adopt_device(arrays)
+        child._mt = None if mt is None else mt.to(dev).contiguous()
+        ids_d, has_d = up(ids), up(has)
+        packed = {k: up(v) for k, v in packed.items()}
+        tail = None if tail is None else up(tail)
+        # -- everything fits and everything is built: from here on nothing is refused
+        if n1 > n0:
+            self._grow(n1, n1 - n0, None, g_old)
+            tables = OnlineJournal.per_node_tables(self)  # (the grown views)
+        if tail is not None and tail.shape[0] and fg.append_edge_rows(tail):
+            self.invalidate_struct()
+        if D:
+            pairs = [(packed[k], t) for k, t in tables.items()]
+            for i in range(0, len(pairs), hip_ops._lib.TG_NODE_ROWS_MAX):
+                hip_ops.node_rows_scatter(pairs[i:i + hip_ops._lib.TG_NODE_ROWS_MAX], ids_d)
+            hip_ops.bitmap_scatter(has_d, ids_d, S.has_msg_bits, n1)
+            for mod in (self.left_memory, self.right_memory, S):
+                mod._version_ += 1
+            fg._version_ = getattr(fg, '_version_', 0) + 1
+            fg._nz_cache = None
+            if self._tracker is not None:
+                self._tracker.mark(ids_d)
+        self.graph = child  # (the setter: the restarter follows; a tracker marks the rows whose length changed)
+        if self._tracker is not None and Dg:
+            self._tracker.mark(up(rows))  # (a row rewritten at its old length too)
+        self._drop_derived()
+        J._position(st['chain'], st['seq'])
+        return child
 
     # ---- remaining reference methods -----------------------------------------------------
     @torch.no_grad()
@@ -2822,5 +3233,5 @@ class TIGER(TIGE):
         old = self.temporal_embedding_fn.graph
         self.temporal_embedding_fn.graph = new_obj
         self.restarter_fn.graph = new_obj
-        if self._tracker is not None:
-            self._tracker.mark_graph(old, new_obj)
+        for sink in self._sinks():
+            sink.mark_graph(old, new_obj)

@@ -775,6 +775,39 @@ int tg_gru_blend_fwd(int64_t n, const float* x, int32_t xw, const float* t, cons
                      const float* w_ih, const float* whh2, const float* b_ih, const float* bhh2, const float* w2,
                      const float* b2, float* out, void* stream);
 
+/* Diagnostic: ONE fused GRU cell straight through the updater's dispatcher, with every operand / epilogue feature of the
+ * cell spelled out (tests/test_hip_gru_forms.py).  For each live row m < min(cap, *n_dev) (n_dev NULL: cap), with
+ * xr = x[x_idx ? x_idx[m] : m] (xw floats, row stride x_ld), hr = h[h_idx ? h_idx[m] : m] (d floats, row stride h_ld)
+ * and o = out_rows ? out_rows[m] : m:
+ *   r = sigmoid(W_ir xr + b_ir + W_hr hr + b_hr), z likewise, h_n = W_hn hr + b_hn, n = tanh(W_in xr + b_in + r h_n)
+ *   out[o * ldo + j] = v = (1 - z) n + z hr                       (w_ih [3d, xw], w_hh [3d, d], b_ih / b_hh [3d]: r, z, n)
+ *   gates (nullable) [cap, 4, d]: row m receives r, z, n, h_n
+ *   out2 (nullable) [*, d]: row (out2_by_row ? o : m) receives v + (add2 ? add2[o * d + j] : 0)
+ * Message k-tiles (32 columns) [x_skip_at, x_skip_at + x_skip_n) are taken as zero and never read (x_skip_n = 0: none).
+ * Blend form (w_blend [d, d] and b_blend [d] non-NULL): the blend operand is w_blend hr + b_blend instead of hr, while the
+ * three gate products use the handed w_hh / b_hh on hr as they are (tg_gru_fc2_fold makes them the fold).
+ * rows_hint (0: none) is the caller's bound on the live rows and picks kernels only.  Nothing else is written.
+ * *form_out (nullable) receives a static string naming the kernel family and instance that ran: "direct16<3>",
+ * "direct16<6>", "direct16<3,blend>", "direct16<6,blend>", "direct", "gru<1,4>", "gru<2,4>", "gru<3,4>", "gru<3,4,tail16>",
+ * "gru<4,2>", "gru<4,1>" (NULL when nothing was launched).
+ * TG_EINVAL before anything touches the GPU: NULL p / x / h / w_ih / w_hh / b_ih / b_hh / out; cap or rows_hint negative;
+ * d or xw not a positive multiple of 4; x_w != xw, h_w != d; x_ld < xw, h_ld < d, either not a multiple of 4; ldo < d; a
+ * skipped run that is negative, reaches past the message's whole k-tiles ((x_skip_at + x_skip_n) * 32 > xw) or leaves no
+ * message column; out2_by_row or add2 without out2.  TG_EUNSUPPORTED (the dispatcher's own refusals, also before any
+ * launch): the blend form with gates, without b_blend, or where the 16 x 16 updater kernel does not apply. */
+typedef struct tg_gru_probe {
+  int64_t cap; const int32_t* n_dev;
+  int32_t d, xw;
+  const float* x; int64_t x_ld; int32_t x_w; const int64_t* x_idx;
+  const float* h; int64_t h_ld; int32_t h_w; const int64_t* h_idx;
+  const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh;
+  float* out; int64_t ldo; const int32_t* out_rows; float* gates;
+  float* out2; const float* add2; int32_t out2_by_row;
+  int64_t rows_hint; int32_t x_skip_at, x_skip_n;
+  const float* w_blend; const float* b_blend;
+} tg_gru_probe;
+int tg_debug_gru(const tg_gru_probe* p, const char** form_out, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* STEP 1-2: consume pending messages (tiger.py:208-221,292-356)              */
 /* ------------------------------------------------------------------------- */

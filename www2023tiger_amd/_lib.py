@@ -193,6 +193,20 @@ class TgGemmProbe(C.Structure):
     ]
 
 
+class TgGruProbe(C.Structure):
+    """tiger_hip.h: tg_gru_probe - one fused GRU cell through the updater's dispatcher (tg_debug_gru)"""
+    _fields_ = [
+        ('cap', i64), ('n_dev', vp), ('d', i32), ('xw', i32),
+        ('x', vp), ('x_ld', i64), ('x_w', i32), ('x_idx', vp),
+        ('h', vp), ('h_ld', i64), ('h_w', i32), ('h_idx', vp),
+        ('w_ih', vp), ('w_hh', vp), ('b_ih', vp), ('b_hh', vp),
+        ('out', vp), ('ldo', i64), ('out_rows', vp), ('gates', vp),
+        ('out2', vp), ('add2', vp), ('out2_by_row', i32),
+        ('rows_hint', i64), ('x_skip_at', i32), ('x_skip_n', i32),
+        ('w_blend', vp), ('b_blend', vp),
+    ]
+
+
 P = C.POINTER
 # name -> (restype, argtypes); every symbol include/tiger_hip.h declares
 SIGNATURES = {
@@ -278,6 +292,7 @@ SIGNATURES = {
     'tg_linear_fwd': (C.c_int, [i64, vp, i32, P(TgLinear), i32, i32, vp, vp]),
     'tg_debug_gemm': (C.c_int, [P(TgGemmProbe), P(C.c_char_p), vp]),
     'tg_debug_gemm2': (C.c_int, [P(TgGemmProbe), P(TgGemmProbe), vp, P(i32), vp, i64, i32, vp]),
+    'tg_debug_gru': (C.c_int, [P(TgGruProbe), P(C.c_char_p), vp]),
     'tg_gru_blend_fwd': (C.c_int, [i64, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'tg_linear_bwd_workspace_bytes': (sz, [i32, i32]),
     'tg_linear_bwd': (C.c_int, [i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),

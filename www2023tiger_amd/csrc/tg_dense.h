@@ -108,8 +108,9 @@ struct GruArgs {
   const int32_t* out_rows;  // nullable
   float* gates;             // nullable [cap, 4, d]: r, z, n, h_n (+bias) per live row, for the backward pass
   // nullable: a second copy of the new rows, dense by launch row m ([cap, d]), plus row add2[node(m), :] when add2 is given,
-  // node(m) = the row's output / memory-gather index (the eager updater, where both are the node id, hands the
-  // attention-centre form of its rows, h + node features, to the query-row product)
+  // node(m) = the row's OUTPUT row (out_rows[m], or m), in every kernel body (the eager updater, whose output row and
+  // memory-gather index are both the node id, hands the attention-centre form of its rows, h + node features, to the
+  // query-row product)
   float* out2;
   const float* add2;
   int out2_by_row;          // out2 is a per-node table (tg_model.c_table): row m goes to its output row, not to row m

@@ -8,6 +8,11 @@
 
 namespace tg {
 
+// diagnostic (tg_debug_gru): family and instance of the last cell this thread launched - a string literal picked in
+// the branch that launches (as TG_FORM in tg_gemm.hip; nothing is formatted on the launch path)
+static thread_local const char* t_gru_form = nullptr;
+#define TG_GRU_FORM(lit_) (t_gru_form = (lit_))
+
 // ---------------------------------------------------------------------------------
 // GRU cell, gates fused into the GEMM epilogue.  A block owns 128 rows x 32 hidden
 // columns and accumulates four planes per column: r and z over K = [x | h], i_n over x
@@ -602,8 +607,8 @@ __global__ void __launch_bounds__(256) k_gru_direct(GruArgs g) {
     const int64_t mm = min(m0 + 8 * ks + q + 4 * fk, M - 1);
     const int64_t node = g.h.idx ? g.h.idx[mm] : mm;
     hold[q] = g.h.p[node * g.h.ld + jc];
-    addv[q] = (g.out2 && g.add2) ? g.add2[node * d + jc] : 0.f;
     orow[q] = g.out_rows ? (int64_t)g.out_rows[mm] : mm;
+    addv[q] = (g.out2 && g.add2) ? g.add2[orow[q] * d + jc] : 0.f;  // by the OUTPUT row, as every other body (GruArgs.add2)
   }
   const float br = g.b_ih[jc] + g.b_hh[jc];
   const float bz = g.b_ih[d + jc] + g.b_hh[d + jc];
@@ -827,9 +832,8 @@ __device__ __forceinline__ void gru_direct16_body(const GruArgs& g, int64_t M, i
   for (int rt = 0; rt < RT; ++rt) {
     const int64_t mm = min(m0 + 16 * rt + 4 * lk + ks, M - 1);
     orow[rt] = g.out_rows ? (int64_t)g.out_rows[mm] : mm;
-    const int64_t node = BL ? orow[rt] : (g.h.idx ? g.h.idx[mm] : mm);
-    hold[rt] = BL ? 0.f : g.h.p[node * g.h.ld + jc];
-    addv[rt] = (g.out2 && g.add2) ? g.add2[node * d + jc] : 0.f;
+    hold[rt] = BL ? 0.f : g.h.p[(g.h.idx ? g.h.idx[mm] : mm) * g.h.ld + jc];
+    addv[rt] = (g.out2 && g.add2) ? g.add2[orow[rt] * d + jc] : 0.f;  // by the OUTPUT row, as every other body (GruArgs.add2)
   }
   const float bb = BL ? g.b_blend[jc] : 0.f;
   const float br = g.b_ih[jc] + g.b_hh[jc];
@@ -1129,6 +1133,8 @@ int gru_launch(const GruArgs& g, hipStream_t st) {
       else if (g.w_blend) TG_KLAUNCH((k_gru_direct16<GRU16_RT_MAX, true>), grid16, dim3(256), 0, st, a);
       else if (rt3) TG_KLAUNCH(k_gru_direct16<3>, grid16, dim3(256), 0, st, a);
       else TG_KLAUNCH(k_gru_direct16<GRU16_RT_MAX>, grid16, dim3(256), 0, st, a);
+      static_assert(GRU16_RT_MAX == 6, "the form names below spell the instance out");
+      TG_GRU_FORM(g.w_blend ? (rt3 ? "direct16<3,blend>" : "direct16<6,blend>") : (rt3 ? "direct16<3>" : "direct16<6>"));
       return check_launch("gru(16 x 16)");
     }
   }
@@ -1138,11 +1144,13 @@ int gru_launch(const GruArgs& g, hipStream_t st) {
     const dim3 grid32((unsigned)(8 * cdiv(cdiv(g.cap, 32), 8) * NT));
     if (direct_knob) TG_KLAUNCH(k_gru_direct, grid32, dim3(256), 0, st, a);
     else TG_KLAUNCH((k_gru<1, 4>), grid32, dim3(256), 0, st, a);
+    TG_GRU_FORM(direct_knob ? "direct" : "gru<1,4>");
     return check_launch("gru(32)");
   }
   if (force_nw == 2 || (force_nw == 0 && tiny)) {
     a.tail_blocks = 0;
     TG_KLAUNCH((k_gru<2, 4>), dim3((unsigned)(8 * cdiv(cdiv(g.cap, 64), 8) * NT)), dim3(512), 0, st, a);
+    TG_GRU_FORM("gru<2,4>");
     return check_launch("gru(64)");
   }
   if (force_nw == 3 || (force_nw == 0 && small)) {
@@ -1153,6 +1161,7 @@ int gru_launch(const GruArgs& g, hipStream_t st) {
     // per XCD: its row tiles x column tiles, then at most NT + ceil(tails / 8) + 1 tail slots (see the kernel's map)
     const int64_t per_xcd = cdiv(cdiv(g.cap, 96), 8) * ntm + (use_tail ? ntm + cdiv(a.tail_blocks, 8) + 1 : 0);
     TG_KLAUNCH((k_gru<3, 4>), dim3((unsigned)(8 * per_xcd)), dim3(768), 0, st, a);
+    TG_GRU_FORM(use_tail ? "gru<3,4,tail16>" : "gru<3,4>");
     return check_launch("gru(96)");
   }
   // 128-row blocks.  More blocks than CUs: four wavefronts per block and TWO blocks per CU (k_gru<4, 1>: 58 KB of LDS - the
@@ -1165,11 +1174,43 @@ int gru_launch(const GruArgs& g, hipStream_t st) {
   const int64_t live = g.rows_hint > 0 ? cdiv(std::min<int64_t>(g.rows_hint, g.cap), 128) * NT : grid;
   // (the caller's row bound carries a margin - 1.5 x the rows seen: between one and 1.25 blocks per CU by that bound the launch
   // usually fits one round, where the eight wavefronts are ahead: 5 000 x 688 -> 172 61.6 against 64.2 us)
-  if (ks_knob == 2 || (ks_knob == 0 && live <= (g.rows_hint > 0 ? 320 : 256)))
+  if (ks_knob == 2 || (ks_knob == 0 && live <= (g.rows_hint > 0 ? 320 : 256))) {
     TG_KLAUNCH((k_gru<4, 2>), dim3((unsigned)grid), dim3(512), 0, st, a);
-  else
+    TG_GRU_FORM("gru<4,2>");
+  } else {
     TG_KLAUNCH((k_gru<4, 1>), dim3((unsigned)grid), dim3(256), 0, st, a);
+    TG_GRU_FORM("gru<4,1>");
+  }
   return check_launch("gru");
 }
 
 }  // namespace tg
+
+// diagnostic: one cell straight through gru_launch with every GruArgs field a caller can set, and which kernel it picked.
+// Every argument check runs before anything touches the GPU.
+extern "C" int tg_debug_gru(const tg_gru_probe* p, const char** form_out, void* stream) {
+  using namespace tg;
+  if (form_out) *form_out = nullptr;
+  if (!p || !p->x || !p->h || !p->w_ih || !p->w_hh || !p->b_ih || !p->b_hh || !p->out) return TG_EINVAL;
+  if (p->cap < 0 || p->rows_hint < 0) return TG_EINVAL;
+  if (p->d <= 0 || (p->d % 4) || p->xw <= 0 || (p->xw % 4)) return TG_EINVAL;
+  if (p->x_w != p->xw || p->h_w != p->d) return TG_EINVAL;
+  if (p->x_ld < p->xw || (p->x_ld % 4) || p->h_ld < p->d || (p->h_ld % 4) || p->ldo < p->d) return TG_EINVAL;
+  // the skipped run lies inside the whole k-tiles of the message and leaves a message column to multiply
+  if (p->x_skip_at < 0 || p->x_skip_n < 0) return TG_EINVAL;
+  if (p->x_skip_n > 0 && ((int64_t)(p->x_skip_at + p->x_skip_n) * BK > p->xw || (int64_t)p->x_skip_n * BK >= p->xw)) return TG_EINVAL;
+  if ((p->out2_by_row || p->add2) && !p->out2) return TG_EINVAL;
+  GruArgs g{};
+  g.cap = p->cap; g.n_dev = p->n_dev; g.d = p->d; g.xw = p->xw;
+  g.x = ASeg{p->x, p->x_ld, p->x_w, p->x_idx};
+  g.h = ASeg{p->h, p->h_ld, p->h_w, p->h_idx};
+  g.w_ih = p->w_ih; g.w_hh = p->w_hh; g.b_ih = p->b_ih; g.b_hh = p->b_hh;
+  g.out = p->out; g.ldo = p->ldo; g.out_rows = p->out_rows; g.gates = p->gates;
+  g.out2 = p->out2; g.add2 = p->add2; g.out2_by_row = p->out2_by_row ? 1 : 0;
+  g.rows_hint = p->rows_hint; g.x_skip_at = p->x_skip_at; g.x_skip_n = p->x_skip_n;
+  g.w_blend = p->w_blend; g.b_blend = p->b_blend;
+  t_gru_form = nullptr;
+  const int rc = gru_launch(g, as_stream(stream));
+  if (form_out) *form_out = t_gru_form;
+  return rc;
+}

@@ -56,6 +56,11 @@ every per-node table to them; rows before -> after are printed.
 and handed to `TIGE.observe_late` that many batches later (default 1) - merged into the device graph at the place its
 time gives it, never streamed into the memories.  The number of late events merged is printed, there is no offline line
 beside it, and at the end the graph is asserted equal to the graph over the whole stream (`run_online`).
+--event_keys [--redeliver P] names every event by an external 64-bit key (the scramble of its edge id) and feeds the replay
+as an at-least-once bus would: the model tracks event keys (`TIGE.track_events` over the events of train + validation),
+the edge table holds the rows of the events seen so far and nothing else, and every batch arrives through
+`TIGE.observe_events` together with a seeded fraction P (default 0.25) of itself and of the previous batch a second time.
+Kept / dropped are printed per batch; the lists are the plain --online replay's, exactly, and `run_online` asserts it.
 
 --cold answers without replaying anything: the checkpoint's parameters, memories at reset, an empty up-to-date bitmap.
 Every batch asks `recommend(..., uptodate=bitmap)`, which first restarts - through the model's restarter - exactly the nodes
@@ -259,7 +264,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                device='cuda:0', window=None, keep_last=None, release_rows=False, verbose=True, offline=True, grow=False,
                erase_nodes=None, retract_eids=None, save_state=None, save_after=None, load_state=None, keyed=False,
                churn=None, compact_at=None, late=None, late_by=1, refresh=False, max_age=None, journal=None, journal_every=1,
-               apply_deltas=None):
+               apply_deltas=None, event_keys=False, redeliver=0.25):
     """-> (metrics of the online replay, metrics of the offline replay); they are equal, exactly.  Online: the graph
     covers train + validation only and grows by `observe`.  Offline: the graph over the whole stream, `stream_step`.
     window / keep_last: `forget(before=t_batch_end - window, keep_last=keep_last)` after every `observe`; the online
@@ -316,7 +321,12 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
     'journal': the kinds written.
     apply_deltas (such a directory; with load_state = one of its BASE files): `load_online(base)`, then
     `apply_online_delta` for every delta that follows it in the index, and the replay continues at the last file's
-    position - its lists are those of the replay that wrote the files, from there on."""
+    position - its lists are those of the replay that wrote the files, from there on.
+    event_keys (the plain online replay only; data with an edge table): the model tracks event keys (`track_events`), its
+    edge table is cut back to the rows of train + validation, and every batch is delivered through `observe_events` with
+    a seeded fraction `redeliver` of itself and of the previous batch a second time; the online metrics carry 'ids', 'kept'
+    and 'dropped' per batch.  The lists are the plain online replay's, exactly; the two replays are held equal under the
+    conditions above."""
     from www2023tiger_amd.data.graph import Graph
     forgetting = window is not None or keep_last is not None
     if journal is not None and keyed:
@@ -340,6 +350,13 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                 or save_after is not None:
             raise ValueError('late: the plain online replay only (no --keyed, --grow, --window / --keep_last, erase, save / load)')
         offline = False
+    if event_keys:
+        if keyed or grow or forgetting or late is not None or refresh or erase_nodes is not None or retract_eids is not None \
+                or save_state or load_state or save_after is not None or journal is not None:
+            raise ValueError('event_keys: the plain online replay only (no --keyed, --grow, --window / --keep_last, --late, '
+                             '--refresh, erase, save / load, --journal)')
+        if not 0 <= float(redeliver) <= 1:
+            raise ValueError(f'redeliver = {redeliver} is a fraction of every batch in [0, 1]')
     if churn is not None and not keyed:
         raise ValueError('churn names the nodes that leave by their keys: it needs --keyed')
     if compact_at is not None and churn is None:
@@ -517,6 +534,30 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
                 held.append((b + int(late_by), s[m], d[m], t[m], e[m]))
             merge_due(b)
         ingest = observe_and_forget if forgetting else (observe if late is None else observe_some_late)
+        kept, dropped = [], []
+        if event_keys:   # the table holds the rows of the events seen so far; the rest arrives with its events
+            fg = model.raw_feat_getter
+            if fg.efeats is None:
+                raise ValueError('event_keys: the data have no edge table; event keys name its rows')
+            table = fg.efeats
+            fg.efeats = table[:n_seen + 1].clone()
+            model.invalidate_struct()
+            model.track_events(torch.from_numpy(scramble(np.arange(1, n_seen + 1))))
+            rs_bus, last = np.random.RandomState(seed), [None]
+
+            def ingest(s, d, t, e):
+                def again(b):   # a seeded share of the events of b, all four arrays by ONE draw
+                    m = rs_bus.uniform(size=len(b[0])) < float(redeliver)
+                    return tuple(a[m] for a in b)
+                parts = ([again(last[0])] if last[0] is not None else []) + [(s, d, t, e), again((s, d, t, e))]
+                s2, d2, t2, e2 = (np.concatenate([p[i] for p in parts]) for i in range(4))
+                _, adm = model.observe_events(s2, d2, t2, torch.from_numpy(scramble(e2)), efeats=table[torch.from_numpy(e2).to(device)])
+                assert adm.n_kept == len(s) and np.array_equal(adm.eids[adm.keep].cpu().numpy(), e)   # (no row was released)
+                kept.append(adm.n_kept)
+                dropped.append(len(s2) - adm.n_kept)
+                last[0] = (s, d, t, e)
+                if verbose:
+                    print(f'batch {len(kept) - 1}: {kept[-1]} events kept, {dropped[-1]} redelivered copies dropped')
         snap, refreshed = [None], []
         if refresh:   # the tracker first: the snapshot remembers the tracker's epoch
             model.track_changes()
@@ -575,7 +616,7 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         # (keyed: the padding id 0 of a short list is INT64_MIN among keys)
         want = np.where(ids_off == 0, INT64_MIN, scramble(ids_off)) if keyed else ids_off
         assert np.array_equal(ids_on, want) and online == offline, (online, offline)
-    if partial or save_state is not None or keyed or journal is not None:
+    if partial or save_state is not None or keyed or journal is not None or event_keys:
         online = dict(online, ids=ids_on)
     if journal is not None:
         online = dict(online, journal=[x['kind'] for x in written])
@@ -593,6 +634,8 @@ def run_online(data, root, ckpt_path, *, k=10, exclude_seen=False, seed=0, bs=20
         online = dict(online, late=n_late[0])
     if refresh:
         online = dict(online, refreshed=refreshed)
+    if event_keys:
+        online = dict(online, kept=kept, dropped=dropped)
     if forgetting:
         online = dict(online, forgot=forgot)
         if release_rows:
@@ -696,6 +739,10 @@ if __name__ == '__main__':
     ap.add_argument('--late', type=float, default=None, metavar='FRACTION', help='--online: hold a seeded fraction of every '
                     'test batch back and hand it to TIGE.observe_late --late_by batches later; prints the late events merged')
     ap.add_argument('--late_by', type=int, default=1, metavar='BATCHES', help='--late: how many batches later (default 1)')
+    ap.add_argument('--event_keys', action='store_true', help='--online: name events by external 64-bit keys and deliver every '
+                    'batch at least once (TIGE.track_events / observe_events); kept / dropped are printed per batch')
+    ap.add_argument('--redeliver', type=float, default=0.25, metavar='P', help='--event_keys: the fraction of every batch that '
+                    'arrives a second time, with the batch itself and with the next one (default 0.25)')
     ap.add_argument('--refresh', action='store_true', help='--online --snapshot: serve the replay from ONE catalogue snapshot, '
                     'refreshed incrementally after every observe (TIGE.track_changes, TIGE.refresh_catalogue)')
     ap.add_argument('--max_age', type=float, default=None, metavar='S', help='--refresh: also re-embed rows older than S time units')
@@ -727,7 +774,8 @@ if __name__ == '__main__':
                                                               keyed=a.keyed, churn=a.churn, compact_at=a.compact_at,
                                                               late=a.late, late_by=a.late_by, refresh=a.refresh,
                                                               max_age=a.max_age, journal=a.journal,
-                                                              journal_every=a.journal_every, apply_deltas=a.apply_deltas)):
+                                                              journal_every=a.journal_every, apply_deltas=a.apply_deltas,
+                                                              event_keys=a.event_keys, redeliver=a.redeliver)):
             if m is None:
                 continue
             if a.keyed and 'ids' in m:

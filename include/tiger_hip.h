@@ -358,6 +358,43 @@ int tg_idmap_assign_recycle_host(const tg_idmap* map, int64_t size, int64_t occu
 int tg_idmap_rebuild_free_host(const tg_idmap* map, int64_t size, int64_t live, const uint64_t* free_bits_host,
                                int64_t free_words, int64_t* out2_host);
 
+/* Event keys (tg_events.hip; idempotent ingestion and retraction behind external event ids.  The reference names an event
+ * by its row in the data set and has no counterpart of this).  The table is a tg_idmap whose dense ids are the ROWS of the
+ * edge-feature table: `rows` = the table's rows, the padding row 0 (key INT64_MIN) included; a row the model was built
+ * with and that has no key holds INT64_MIN in key_of under a set bit of a `keyless` bitmap (uint64 words over the rows) -
+ * the "free" row tg_idmap_rebuild_free skips.  The map is written by tg_idmap_assign (commit: the kept keys of a screened
+ * batch, distinct and unknown, get rows, rows + 1, ... in order) and by tg_idmap_rebuild / _rebuild_free alone.
+ * tg_events_screen: READ-ONLY on the map.  eid_out[i] (int32) = the row keys[i] has, or would get: the stored row of a key
+ * the map holds; rows + r for any other key, r = the rank of the key's FIRST occurrence among the first occurrences of all
+ * such keys - so a duplicate inside the batch gets the row of its first copy.  keep_out (int64 [n], the first m entries
+ * written) = the positions of those first occurrences, ascending: the events to observe.  out2 (DEVICE, int64 [2]) = {m,
+ * error bits}: the one read-back.  In-batch duplicates meet in a scratch table of this call (a power of two >= 2 n slots,
+ * the home slot and probing of tg_idmap; in LDS for n <= 256 - one workgroup, one launch -, in the workspace above - five
+ * dependent launches, the first clears it); the smallest position wins a slot.  No atomics touch the map, no kernel waits
+ * for another workgroup, every probe loop ends after its table's capacity (TG_IDMAP_ERR_PROBE), and a value loaded from
+ * either table is range-checked before it is used (TG_IDMAP_ERR_TABLE).  INT64_MIN in keys[] is no key:
+ * TG_EVENTS_ERR_KEY, its eid_out is -1, it is never kept.  eid_out of a position that raised an error is -1.
+ * ws: tg_events_screen_workspace_bytes(n) bytes, 16-byte aligned (0 for a bad n), contents irrelevant before and after.
+ * TG_EINVAL before any launch: a missing array, a capacity that is no power of two in [16, 2^32], rows < 1,
+ * rows > key_rows, n < 0, rows + n > 2^31 - 1.  TG_EWORKSPACE: a short workspace.
+ * tg_events_repack: after a release of edge rows (tg_edge_rows_*: remap int32 [rows_before], monotone, -1 = released):
+ * key_of_new[remap[r]] = key_of_old[r] and bit remap[r] of keyless_new = bit r of keyless_old, for remap[r] in
+ * [0, rows_new).  The words [0, ceil(rows_new / 64)) of keyless_new are written in full; key_of_new [>= rows_new],
+ * keyless_old [>= ceil(rows_before / 64) words].  One launch, no atomics, nothing read back; the caller rebuilds the
+ * table from key_of_new (tg_idmap_rebuild / _rebuild_free).  TG_EINVAL: a missing array, rows_before < 1 or > 2^31 - 1,
+ * rows_new outside [1, rows_before].
+ * The _host twins: HOST pointers, plain C++, the same results bit for bit. */
+#define TG_EVENTS_ERR_KEY 32 /* INT64_MIN stands in keys[]: it is the key of the padding row alone */
+size_t tg_events_screen_workspace_bytes(int64_t n);
+int tg_events_screen(const tg_idmap* map, int64_t rows, const int64_t* keys, int64_t n, int32_t* eid_out, int64_t* keep_out,
+                     int64_t* out2, void* ws, size_t ws_bytes, void* stream);
+int tg_events_repack(const int64_t* key_of_old, const uint64_t* keyless_old, const int32_t* remap, int64_t rows_before,
+                     int64_t* key_of_new, uint64_t* keyless_new, int64_t rows_new, void* stream);
+int tg_events_screen_host(const tg_idmap* map, int64_t rows, const int64_t* keys_host, int64_t n, int32_t* eid_out_host,
+                          int64_t* keep_out_host, int64_t* out2_host);
+int tg_events_repack_host(const int64_t* key_of_old_host, const uint64_t* keyless_old_host, const int32_t* remap_host,
+                          int64_t rows_before, int64_t* key_of_new_host, uint64_t* keyless_new_host, int64_t rows_new);
+
 /* Releasing edge-feature rows (tg_edge_rows.hip; online serving after a trim).  The reference never drops a row of its
  * tables (feature_getter.py:41-47, graph.py:11-42: built once over the whole stream).  A row r of the table
  * T [n_rows, d_e] (float32, d_e % 4 == 0) is LIVE iff r == 0 (the padding row), some entry of g has

@@ -51,6 +51,7 @@ class TgIdmap(C.Structure):
 
 TG_IDMAP_EMPTY = -(1 << 63)
 TG_IDMAP_ERR_PROBE, TG_IDMAP_ERR_DUP, TG_IDMAP_ERR_EMPTY_KEY, TG_IDMAP_ERR_TABLE, TG_IDMAP_ERR_FREE = 1, 2, 4, 8, 16
+TG_EVENTS_ERR_KEY = 32  # tg_events_screen: INT64_MIN in the batch
 
 
 class TgNodeRows(C.Structure):
@@ -253,6 +254,11 @@ SIGNATURES = {
     'tg_idmap_remove_host': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, i64, vp, vp, vp]),
     'tg_idmap_assign_recycle_host': (C.c_int, [P(TgIdmap), i64, i64, vp, i64, i64, vp, i64, vp, vp, vp]),
     'tg_idmap_rebuild_free_host': (C.c_int, [P(TgIdmap), i64, i64, vp, i64, vp]),
+    'tg_events_screen_workspace_bytes': (sz, [i64]),
+    'tg_events_screen': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, vp, vp, vp, sz, vp]),
+    'tg_events_repack': (C.c_int, [vp, vp, vp, i64, vp, vp, i64, vp]),
+    'tg_events_screen_host': (C.c_int, [P(TgIdmap), i64, vp, i64, vp, vp, vp]),
+    'tg_events_repack_host': (C.c_int, [vp, vp, vp, i64, vp, vp, i64]),
     'tg_edge_rows_workspace_bytes': (sz, [i64, i64]),
     'tg_edge_rows_plan': (C.c_int, [P(TgTcsr), i64, i64, vp, i64, vp, vp, vp, sz, vp]),
     'tg_edge_rows_apply': (C.c_int, [P(TgTcsr), vp, i64, i32, vp, i64, vp, vp, vp, sz, vp]),

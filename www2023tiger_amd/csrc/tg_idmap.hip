@@ -59,14 +59,10 @@
 
 #include "tg_tcsr.h"
 #include "tg_step.h"
+#include "tg_idmap.h"
 
 namespace tg {
 
-constexpr int IM_THREADS = TG_SCAN_BLOCK;  // block_excl_scan: 256
-constexpr int IM_ITEMS = 8;
-constexpr int IM_TILE = IM_THREADS * IM_ITEMS;  // positions per workgroup
-constexpr int IM_WORDS = IM_TILE / 64;          // flag words per tile
-constexpr int IM_WAVES = IM_THREADS / TG_WAVE;
 // Batches up to here run in one workgroup of one launch: one key per thread.  Measured (profiles/idmap_one_max_v1.json,
 // DESIGN 7.18): at 256 keys the one launch is the faster form; at 2 048 - eight keys per thread, each a chain of dependent
 // atomics - the four launches are.  (Diagnostic builds: make EXTRA=-DTG_IDMAP_ONE_MAX=N, 0 <= N <= 2048.)
@@ -75,33 +71,10 @@ constexpr int IM_WAVES = IM_THREADS / TG_WAVE;
 #endif
 constexpr int IM_ONE_MAX = TG_IDMAP_ONE_MAX;
 static_assert(IM_ONE_MAX >= 0 && IM_ONE_MAX <= IM_TILE, "the one-workgroup form covers one tile");
-constexpr int64_t IM_EMPTY = TG_IDMAP_EMPTY;
 constexpr int32_t IM_PENDING = INT32_MIN;  // slot_id of a slot claimed in this call: IM_PENDING + smallest position
 // wpos[i] of a position that waits for no rank: done, or why it failed
 constexpr int32_t IM_DONE = -1, IM_BAD_PROBE = -2, IM_BAD_TABLE = -3;
 
-__host__ __device__ __forceinline__ uint64_t idmap_mix(int64_t key) {
-  uint64_t z = (uint64_t)key + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// table words other workgroups change while this kernel runs: read past the vector L1
-__device__ __forceinline__ int64_t im_ld(const int64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int32_t im_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the slot that holds `key`, or -1 (an empty slot comes first: the map does not hold it), or -2 (capacity slots probed)
-__device__ __forceinline__ int64_t im_find(const tg_idmap& m, int64_t key) {
-  const uint64_t mask = (uint64_t)m.capacity - 1;
-  uint64_t s = idmap_mix(key) & mask;
-  for (int64_t j = 0; j < m.capacity; ++j, s = (s + 1) & mask) {
-    const int64_t k = im_ld(m.slot_key + s);
-    if (k == key) return (int64_t)s;
-    if (k == IM_EMPTY) return -1;
-  }
-  return -2;
-}
 // the slot that holds `key` once this returns - found, or claimed from the empty slots -, or -2 (capacity slots probed)
 __device__ __forceinline__ int64_t im_claim(const tg_idmap& m, int64_t key) {
   const uint64_t mask = (uint64_t)m.capacity - 1;
@@ -563,17 +536,6 @@ static int idmap_free_args(const tg_idmap* m, int64_t size, int64_t occupied, in
   const int64_t grown = size + std::max<int64_t>(0, n - n_free);
   if (grown > 0x7fffffffLL || grown > m->key_rows || 2 * (occupied + n) > m->capacity) return TG_EINVAL;
   return TG_OK;
-}
-
-// host twins' probe: the slot of `key`, or of the first empty slot (*found = false), or -1 after capacity slots
-static int64_t host_probe(const tg_idmap* m, int64_t key, bool* found) {
-  const uint64_t mask = (uint64_t)m->capacity - 1;
-  uint64_t s = idmap_mix(key) & mask;
-  for (int64_t j = 0; j < m->capacity; ++j, s = (s + 1) & mask) {
-    *found = m->slot_key[s] == key;
-    if (*found || m->slot_key[s] == IM_EMPTY) return (int64_t)s;
-  }
-  return -1;
 }
 
 }  // namespace tg

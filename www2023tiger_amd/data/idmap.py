@@ -39,7 +39,8 @@ class IdMap:
     and one for the padding id included: a removed slot keeps its key so that probe chains stay intact, and the table is
     rebuilt from key_of - purged of those slots, possibly at the SAME capacity - when slots_used + n would pass half of it.
     device 'cpu' runs the library's host twins over the same layout (tests, tools); there is no other fallback.
-    `compact` takes the free ids out and shrinks the tables to the live keys.  Not built: keys for eids."""
+    `compact` takes the free ids out and shrinks the tables to the live keys.  Keys for EVENTS (eids) are data/events.py:
+    EventKeys, over the same table layout and kernels."""
 
     def __init__(self, device, capacity: int = 1024, reserve: Optional[int] = None):
         self.device = torch.device(device)

@@ -1212,6 +1212,85 @@ def idmap_rebuild_free(tables, size: int, live: int, free_bits: Tensor, read_bac
     return int(out2[1].item()) if read_back else out2
 
 
+# ---- event keys: external int64 event keys -> edge-table rows (tg_events_* and their host twins) ---------------------------
+EVENTS_ERR_KEY = _lib.TG_EVENTS_ERR_KEY
+_EVENTS_CLASSES = _IDMAP_CLASSES + ((_lib.TG_EVENTS_ERR_KEY, 'KEY: INT64_MIN is the key of the padding row alone'),)
+
+
+def EVENTS_ERR_TEXT(word: int) -> str:
+    """The message of a non-zero tg_events_screen error word: the classes by name."""
+    return '; '.join(text for bit, text in _EVENTS_CLASSES if int(word) & bit)
+
+
+def _events_screen(tables, rows: int, keys: Tensor, host: bool):
+    m, dev = _idmap_struct('events_screen', tables, keys)
+    if (dev.type == 'cpu') != host:
+        raise ValueError(f'events_screen{"_host" if host else ""}: the tables live on {dev}')
+    n = keys.numel()
+    eids = torch.empty(n, dtype=torch.int32, device=dev)
+    keep = torch.empty(n, dtype=torch.int64, device=dev)
+    out2 = torch.empty(2, dtype=torch.int64, device=dev)
+    if host:
+        check(lib.tg_events_screen_host(C_.byref(m), rows, ptr(keys), n, ptr(eids), ptr(keep), ptr(out2)),
+              'tg_events_screen_host')
+    else:
+        with torch.cuda.device(dev):
+            nbytes = int(lib.tg_events_screen_workspace_bytes(n))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            check(lib.tg_events_screen(C_.byref(m), rows, ptr(keys), n, ptr(eids), ptr(keep), ptr(out2), ptr(ws), nbytes,
+                                       stream_ptr(dev)), 'tg_events_screen')
+    m_kept, err = out2.tolist()
+    return eids, keep[:max(0, min(int(m_kept), n))], int(err)
+
+
+def events_screen(tables, rows: int, keys: Tensor) -> Tuple[Tensor, Tensor, int]:
+    """tiger_hip.h: tg_events_screen -> (eids int32 [n]: the row each key has or would get, -1 where the error word says
+    why; keep int64 [m]: the positions of the first occurrences of the keys the map does not hold, ascending; error
+    word: EVENTS_ERR_TEXT).  The tables are only read; ONE read-back, of the two result words."""
+    return _events_screen(tables, rows, keys, False)
+
+
+def events_screen_host(tables, rows: int, keys: Tensor) -> Tuple[Tensor, Tensor, int]:
+    """tiger_hip.h: tg_events_screen_host: events_screen over CPU tensors, bit for bit"""
+    return _events_screen(tables, rows, keys, True)
+
+
+def _events_repack(key_of_old, keyless_old, remap, rows_before, key_of_new, keyless_new, rows_new, host: bool):
+    what = 'events_repack_host' if host else 'events_repack'
+    dev = key_of_old.device
+    rows_before, rows_new = int(rows_before), int(rows_new)
+    for t, dt, least, name in ((key_of_old, torch.int64, rows_before, 'key_of_old'),
+                               (keyless_old, torch.int64, (rows_before + 63) // 64, 'keyless_old'),
+                               (remap, torch.int32, rows_before, 'remap'), (key_of_new, torch.int64, rows_new, 'key_of_new'),
+                               (keyless_new, torch.int64, (rows_new + 63) // 64, 'keyless_new')):
+        if not (torch.is_tensor(t) and t.dtype == dt and t.dim() == 1 and t.is_contiguous() and t.device == dev
+                and t.numel() >= least):
+            raise ValueError(f'{what}: {name} must be a contiguous 1-d tensor of {dt} with at least {least} entries on {dev}')
+    if (dev.type == 'cpu') != host:
+        raise ValueError(f'{what}: the tables live on {dev}')
+    if host:
+        check(lib.tg_events_repack_host(ptr(key_of_old), ptr(keyless_old), ptr(remap), rows_before, ptr(key_of_new),
+                                        ptr(keyless_new), rows_new), 'tg_events_repack_host')
+    else:
+        with torch.cuda.device(dev):
+            check(lib.tg_events_repack(ptr(key_of_old), ptr(keyless_old), ptr(remap), rows_before, ptr(key_of_new),
+                                       ptr(keyless_new), rows_new, stream_ptr(dev)), 'tg_events_repack')
+
+
+def events_repack(key_of_old: Tensor, keyless_old: Tensor, remap: Tensor, rows_before: int, key_of_new: Tensor,
+                  keyless_new: Tensor, rows_new: int):
+    """tiger_hip.h: tg_events_repack: key_of_new[remap[r]] = key_of_old[r] and the keyless bit with it, for the rows a
+    release of edge rows kept (remap: EdgeRowsRelease.remap).  keyless_*: 64-bit words held as int64.  Nothing is read
+    back."""
+    _events_repack(key_of_old, keyless_old, remap, rows_before, key_of_new, keyless_new, rows_new, False)
+
+
+def events_repack_host(key_of_old: Tensor, keyless_old: Tensor, remap: Tensor, rows_before: int, key_of_new: Tensor,
+                       keyless_new: Tensor, rows_new: int):
+    """tiger_hip.h: tg_events_repack_host: events_repack over CPU tensors, bit for bit"""
+    _events_repack(key_of_old, keyless_old, remap, rows_before, key_of_new, keyless_new, rows_new, True)
+
+
 # ---- compacting the node id space (tg_node_compact_plan / tg_node_rows_compact / tg_bitmap_compact and their host twins) ---
 NODE_COMPACT_CLASSES = ('ID0', 'SPARE', 'ROW', 'NBR')
 _NODE_COMPACT_WHAT = ('node id 0 is the padding id and never leaves',

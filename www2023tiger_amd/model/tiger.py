@@ -17,7 +17,7 @@ Ways to run a batch:
 """
 import ctypes as C
 import operator
-from typing import Optional, Tuple, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import os
@@ -40,6 +40,15 @@ from .utils import select_latest_nids
 
 _TSFM = {'id': 0, 'linear': 1, 'mlp': 2}
 _UPD = {'gru': 0, 'merge': 1}
+
+
+class EventAdmission(NamedTuple):
+    """What `TIGE.observe_events` did with a batch.  eids int32 [n]: the edge row of every delivered event - a new row for
+    a kept one, the row of its first copy for a duplicate; keep int64 [n_kept]: the positions that were observed,
+    ascending (the first occurrences of the keys not seen before); n_kept = len(keep)."""
+    eids: Tensor
+    keep: Tensor
+    n_kept: int
 
 
 class _QueryGraph:
@@ -791,6 +800,18 @@ class TIGE(nn.Module):
         if getattr(self, '_row_of', None) is not None:
             raise RuntimeError(f'{what}: the model\'s state is physically partitioned (partition_state); only '
                                'www2023tiger_amd.dist.HipPartitionEngine may drive it')
+
+    events = None              # the attached EventKeys tracker (track_events / attach_events), or None
+    _events_admitting = False  # observe_events is inside its own call of observe / observe_late
+
+    def _refuse_tracked(self, what: str):
+        """With an event-key tracker attached (events.size == rows of the edge table, always) the calls that append or
+        replace edge rows behind its back are refused: the rows they add would have no key and the invariant would
+        break."""
+        if self.events is not None and not self._events_admitting:
+            raise RuntimeError(f'{what}: an event-key tracker is attached (model.events); feed the model through '
+                               'observe_events, or detach_events() first (load a state, then attach_events the restored '
+                               'tracker)')
 
     # ---- eager query rows (tiger_hip.h: tg_model.g_table) --------------------------------------------------------------
     def _gtab_wanted(self) -> bool:
@@ -2084,6 +2105,7 @@ class TIGE(nn.Module):
         one built on N1 nodes - bit for bit.  The child graph is computed first (it validates), then what `grow_nodes`
         refuses is refused: nothing has changed if the call raises.  The caller's part is that of `grow_nodes`."""
         self._refuse_partitioned('observe')
+        self._refuse_tracked('observe')
         if self.training:
             raise RuntimeError('observe streams the model in eval() mode')
         if num_node is None and nfeats is not None:
@@ -2136,6 +2158,7 @@ class TIGE(nn.Module):
         eid that is no row of the edge table after the append, arrays of unequal length).  `observe` keeps refusing a
         batch that starts before the latest event: the two do not overlap."""
         self._refuse_partitioned('observe_late')
+        self._refuse_tracked('observe_late')
         if self.training:
             raise RuntimeError('observe_late: late events are admitted in eval() mode (the streaming state of a served model)')
         if num_node is None and nfeats is not None:
@@ -2170,6 +2193,7 @@ class TIGE(nn.Module):
         a recycled one; nfeats may be a callable handed the admitted keys), and the batch is merged with num_node =
         max(idmap.size, n_nodes) -> the new graph.  Refusals and their order are those of `observe_keys`: what
         `observe_late` refuses about the batch is refused AFTER the assignment - the model is untouched, the keys stay."""
+        self._refuse_tracked('observe_late_keys')
         src_keys = self._device_keys('observe_late_keys', 'src_keys', src_keys).reshape(-1)
         dst_keys = self._device_keys('observe_late_keys', 'dst_keys', dst_keys).reshape(-1)
         if src_keys.numel() != dst_keys.numel():
@@ -2471,6 +2495,7 @@ class TIGE(nn.Module):
         may precede its first event; the next observe_keys admits its id with the batch it arrives in."""
         if 'num_node' in observe_kwargs:
             raise TypeError('observe_keys: num_node follows from the id map')
+        self._refuse_tracked('observe_keys')
         src_keys = self._device_keys('observe_keys', 'src_keys', src_keys).reshape(-1)
         dst_keys = self._device_keys('observe_keys', 'dst_keys', dst_keys).reshape(-1)
         if src_keys.numel() != dst_keys.numel():
@@ -2692,13 +2717,147 @@ class TIGE(nn.Module):
             self.last_release = None
             return None
         child = graph.renumbered(res.remap, res.eid_out)
+        # (an attached event-key tracker follows the rows: built beside the old one - it may raise -, swapped with the rest)
+        events = None if self.events is None else self.events._released_build(res)
         self.graph = child
         if self._journal is not None:  # (a trim or an erase in the same call hides the shared indptr from the setter)
             self._journal.mark_all('release_edge_rows packed the edge table and renumbered every edge id')
         fg.adopt_edge_rows(res)
+        if events is not None:
+            self.events._adopt(events)
         self.invalidate_struct()
         self.last_release = res
         return res
+
+    # ---- event keys: idempotent ingestion and retraction by external event id (data/events.py) -------------
+    def _events_refusals(self, what: str):
+        self._refuse_partitioned(what)
+        fg = self.raw_feat_getter
+        if fg.efeats is None:
+            raise NotImplementedError(f'{what}: the model has no edge table; event keys name its rows (NOT BUILT for models '
+                                      'without one)')
+        if not fg.pin_mem:
+            raise NotImplementedError(f'{what}: the edge table lives in pinned host memory (register_buffer=False)')
+        if self.training:
+            raise RuntimeError(f'{what}: events are tracked in eval() mode (the streaming state of a served model)')
+        if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{what}: building the key table reads an error word back; it cannot be captured into a graph')
+
+    def track_events(self, keys=None):
+        """Name events by external int64 keys from now on -> the EventKeys tracker, also kept as `model.events`
+        (data/events.py).  keys int64 [rows - 1]: the keys of the rows the edge table holds now (row 0 is the padding row);
+        None: those rows are keyless - never matched, never retractable by key.  While the tracker is attached:
+          * `observe_events` is idempotent and `retract_events` takes keys;
+          * `release_edge_rows`, and the release paths of `forget` / `erase`, carry the tracker along inside the same
+            all-or-nothing swap as graph and table (EventKeys.released);
+          * plain `observe` / `observe_keys` / `observe_late*`, `load_online` and `apply_online_delta` raise RuntimeError:
+            they would add or replace rows behind the tracker's back (detach, load, `attach_events` the restored tracker);
+          * `compact_nodes` is unaffected (it renumbers nodes, not rows).
+        THE LIMITS: the dedupe and tombstone horizon is the life of the edge row - after `forget(...,
+        release_edge_rows=True)` a very old redelivery is unknown again (`observe_events` then refuses it as going back in
+        time; late=True admits it).  The journal's deltas do not carry event keys: `events.state_dict()` is saved whole
+        (8 B per row) beside `online_state()`, as an IdMap is; a delta form is NOT BUILT.  Models without an edge table
+        are not supported.
+        Refused before anything changes: a model without an edge table (NotImplementedError), a table in pinned host
+        memory, a partitioned model, training mode, a stream capture in progress, and keys EventKeys refuses (another
+        count than rows - 1, a key that stands twice, INT64_MIN)."""
+        from ..data.events import EventKeys
+        self._events_refusals('track_events')
+        self.events = EventKeys(self.device, int(self.raw_feat_getter.efeats.shape[0]), keys)
+        return self.events
+
+    def attach_events(self, ev):
+        """Attach a restored tracker (EventKeys.from_state_dict) -> it, also kept as `model.events`.  Refused before
+        anything changes: what `track_events` refuses, a tracker whose size is not the edge table's row count, a tracker on
+        another device (ValueError)."""
+        self._events_refusals('attach_events')
+        rows = int(self.raw_feat_getter.efeats.shape[0])
+        if ev.size != rows:
+            raise ValueError(f'attach_events: the tracker covers {ev.size} rows, the edge table has {rows}')
+        if ev.device != self.device:
+            raise ValueError(f'attach_events: the tracker lives on {ev.device}, the model on {self.device}')
+        self.events = ev
+        return ev
+
+    def detach_events(self):
+        """Remove the tracker -> it (or None): the model is fed by plain `observe` again"""
+        ev, self.events = self.events, None
+        return ev
+
+    def observe_events(self, src, dst, ts, event_keys, *, efeats, idmap=None, late: bool = False, **observe_kwargs):
+        """`observe` for a stream that names its EVENTS by external int64 keys and may deliver them more than once ->
+        (step, EventAdmission(eids, keep, n_kept)).  In this order:
+          1. `events.screen(event_keys)`: keep = the first occurrences of the keys never seen (the map is only read);
+          2. src / dst / ts / efeats are gathered by keep;
+          3. the kept events are observed with eids = rows + arange(n_kept): `observe`; with idmap= `observe_keys` (src / dst
+             are then NODE keys - screened first, so a dropped duplicate assigns no node id); with late=True `observe_late`
+             / `observe_late_keys` (the step is then the new graph);
+          4. `events.commit(event_keys[keep])`.
+        A redelivered event - a copy inside the batch, a copy of an earlier batch, a whole batch sent twice - changes
+        nothing: the model ends bit-identical to one fed the clean stream through `observe`.  If step 3 raises, the tracker
+        is unchanged (the screen wrote nothing; the table may have grown in capacity, the mapping has not).  n_kept == 0:
+        nothing is observed and the step is None.  efeats [n, d_e] is required; the caller passes no eids.
+        observe_kwargs: those of the call of step 3 (neg and nfeats are per-event / per-call as there; neg is gathered by
+        keep).  THE LIMITS are those of `track_events`."""
+        what = 'observe_events'
+        ev = self.events
+        if ev is None:
+            raise RuntimeError(f'{what}: no event-key tracker is attached (track_events / attach_events)')
+        if 'eids' in observe_kwargs:
+            raise TypeError(f'{what}: eids follow from the tracker')
+        fg = self.raw_feat_getter
+        dev = self.device
+        event_keys = self._device_keys(what, 'event_keys', event_keys).reshape(-1)
+        n = event_keys.numel()
+        efeats = torch.as_tensor(efeats).to(dev)
+        if efeats.dim() != 2 or efeats.shape[0] != n or efeats.shape[1] != fg.efeats.shape[1]:
+            raise ValueError(f'{what}: efeats {tuple(efeats.shape)} for {n} events of width {fg.efeats.shape[1]}')
+        src, dst, ts = (torch.as_tensor(x).to(dev).reshape(-1) for x in (src, dst, ts))
+        if not (src.numel() == dst.numel() == ts.numel() == n):
+            raise ValueError(f'{what}: src, dst, ts and event_keys must have one entry per event')
+        rows = int(fg.efeats.shape[0])
+        if ev.size != rows:
+            raise RuntimeError(f'{what}: the tracker covers {ev.size} rows, the edge table has {rows}: rows were added or '
+                               'released behind its back')
+        eids, keep = ev.screen(event_keys)
+        m = int(keep.numel())
+        if m == 0:
+            return None, EventAdmission(eids, keep, 0)
+        ev.reserve(m)   # (before the batch is observed: commit cannot fail for want of room)
+        pick = lambda x: x.index_select(0, keep)
+        if observe_kwargs.get('neg') is not None:
+            observe_kwargs['neg'] = pick(torch.as_tensor(observe_kwargs['neg']).to(dev).reshape(-1))
+        new_eids = torch.arange(rows, rows + m, dtype=torch.int64, device=dev)
+        self._events_admitting = True
+        try:
+            if idmap is None:
+                call = self.observe_late if late else self.observe
+                step = call(pick(src), pick(dst), pick(ts), new_eids, efeats=pick(efeats), **observe_kwargs)
+            else:
+                call = self.observe_late_keys if late else self.observe_keys
+                step = call(idmap, pick(src), pick(dst), pick(ts), new_eids, efeats=pick(efeats), **observe_kwargs)
+        finally:
+            self._events_admitting = False
+        ev.commit(pick(event_keys))
+        return step, EventAdmission(eids, keep, m)
+
+    def retract_events(self, keys, *, release_edge_rows: bool = False, keep_from=None):
+        """`erase(eids=...)` behind event keys (a chargeback names a transaction id) -> (graph, eids): the new graph and the
+        rows (int64, in the order of `keys`) of the keys the tracker holds; a key it does not hold is ignored, and so is
+        INT64_MIN.  Without a release the key STAYS mapped to its row, which no entry names any more: a redelivered copy of
+        a retracted event stays dropped, like a tombstone.  release_edge_rows=True: the row leaves the table and the key
+        with it (`events.released`, inside the swap) - the event is unknown again.  `erase`'s limits and refusals carry
+        over; no key found: nothing changes and the graph is returned as it is."""
+        what = 'retract_events'
+        ev = self.events
+        if ev is None:
+            raise RuntimeError(f'{what}: no event-key tracker is attached (track_events / attach_events)')
+        keys = self._device_keys(what, 'keys', keys).reshape(-1)
+        found = ev.lookup(keys).long()
+        found = found[found > 0]
+        if found.numel() == 0:
+            return self.graph, found
+        return self.erase(eids=found, release_edge_rows=release_edge_rows, keep_from=keep_from), found
 
     # ---- saving and restoring an online model ----------------------------------------------
     ONLINE_FORMAT, ONLINE_VERSION = 'tiger-online-state', 1
@@ -2759,6 +2918,7 @@ class TIGE(nn.Module):
         from ..data.graph import Graph
         what = 'load_online'
         self._refuse_partitioned(what)
+        self._refuse_tracked(what)
         if self.training:
             raise RuntimeError(f'{what}: an online state is loaded in eval() mode (the streaming state of a served model)')
         fg, S = self.raw_feat_getter, self.msg_store
@@ -2897,6 +3057,7 @@ class TIGE(nn.Module):
         file: it is no longer the delta's predecessor)."""
         what = 'apply_online_delta'
         self._refuse_partitioned(what)
+        self._refuse_tracked(what)
         if self.training:
             raise RuntimeError(f'{what}: a delta is applied in eval() mode (the streaming state of a served model)')
         fg, S, J = self.raw_feat_getter, self.msg_store, self._journal

@@ -94,6 +94,12 @@ to every row the walk leaves short, under the walk's own rules (`hip_ops.fill_ca
 fill=dict(T=..., window=..., among=destinations))`), so a source without history gets the popular items instead of an
 empty list.  The line printed reads recall@C coverage_walk -> coverage and adds `filled`, the filled share of all
 candidates.
+--similar S [--metric cos|ip] retrieves in embedding space before it ranks: per batch one snapshot of all destination
+nodes at the batch's earliest event time; every event's seed is its source's latest neighbour before the event, its
+candidates are the seed's S nearest snapshot rows by cosine or inner product (`TIGE.recommend_similar`: `hip_ops.knn_rows`,
+S <= 64), ranked by the score head on the snapshot's rows (`eval_recommendation(similar=dict(S=..., catalogue=...,
+metric=...))`).  The line printed adds recall@S and `seeded`, the share of events whose seed has a row.  Embedding
+nearness is not what the score head was trained on; what this generator does to hit rate / NDCG is not measured.
 
 Only `run()`, `run_online()` and `run_cold()` matter; the few flags exist to make the file runnable.
 """
@@ -114,7 +120,8 @@ from www2023tiger_amd.init_utils import init_data, init_model  # noqa: E402
 
 def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0, bs=200, dim=None, n_neighbors=10, n_heads=2,
         hit_type='bin', restarter_type='seq', hist_len=40, msg_src='left', upd_src='right', strategy='recent_edges',
-        device='cuda:0', snapshot=False, walk=None, fanout=(10, 10, 10), fill=None, fill_window=None):
+        device='cuda:0', snapshot=False, walk=None, fanout=(10, 10, 10), fill=None, fill_window=None, similar=None,
+        metric='cos'):
     """-> (ids [n_test, k], scores [n_test, k], the eval_recommendation dict).  The model settings must be those the
     checkpoint was trained with (examples/link_prediction.py defaults here).  snapshot: one catalogue snapshot per batch
     at the batch's earliest event time (catalogue_at='batch') instead of the exact per-pair protocol.  walk=C: per-event
@@ -122,9 +129,13 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     the catalogue of all destinations; the dict's coverage is then the generator's recall@C.  walk with snapshot: the
     walk's candidates ranked on the per-batch snapshot of all destinations; the dict gains in_catalogue.  fill=T (with
     walk): rows back-filled from the T most active destinations of the fill_window seconds (None: everything) before the
-    batch's earliest event time; the dict gains coverage_walk and filled."""
+    batch's earliest event time; the dict gains coverage_walk and filled.  similar=S: per-event candidates are the S
+    nearest rows (metric 'cos' | 'ip') of a per-batch snapshot of all destinations to the source's latest neighbour
+    (TIGE.recommend_similar); the dict's coverage is the generator's recall@S and it gains seeded and candidates."""
     if fill is not None and walk is None:
         raise ValueError('fill back-fills walk candidates: give walk=C as well')
+    if similar is not None and (walk is not None or snapshot or exclude_seen):
+        raise ValueError('similar is a candidate generator of its own: it takes neither walk, snapshot nor exclude_seen')
     fanout = tuple(int(f) for f in fanout)
     wk = dict(fanout=fanout, take=tuple(l == len(fanout) - 1 or (l == 0 and len(fanout) == 3) for l in range(len(fanout))))
     device = torch.device(device)
@@ -149,7 +160,10 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
         for src, dst, neg, ts, eids, _, cg in test_dl:
             src, dst, neg, eids = (x.long().to(device) for x in (src, dst, neg, eids))
             cg.to(device)
-            if walk is not None:
+            if similar is not None:
+                snap = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph)
+                i, s, _, _ = model.recommend_similar(src, cg.ts64, snap, k, S=int(similar), metric=metric, graph=full_graph)
+            elif walk is not None:
                 snap = model.embed_catalogue(catalogue, float(cg.ts64.min()), graph=full_graph) if snapshot else None
                 i, s, _, _ = model.recommend_walk(src, cg.ts64, k, C=walk, graph=full_graph, exclude_seen=exclude_seen,
                                                   snapshot=snap, fill=fl, **wk)
@@ -163,7 +177,9 @@ def run(data, root, ckpt_path, *, k=10, exclude_seen=False, out_dir='.', seed=0,
     np.save(os.path.join(out_dir, 'ids.npy'), ids)
     np.save(os.path.join(out_dir, 'scores.npy'), scores)
     model.load_memory_state(start)  # the same pass once more, folded into the metrics
-    if walk is not None:
+    if similar is not None:
+        out = eval_recommendation(model, test_dl, device, similar=dict(S=int(similar), catalogue=catalogue, metric=metric), k=k)
+    elif walk is not None:
         out = eval_recommendation(model, test_dl, device, walk=dict(wk, C=walk, **(dict(catalogue=catalogue) if snapshot else {}),
                                                                     **(dict(fill=fl) if fl is not None else {})),
                                   k=k, exclude_seen=exclude_seen)
@@ -753,6 +769,9 @@ if __name__ == '__main__':
                     'destination nodes before the batch (hip_ops.trending, hip_ops.fill_candidates)')
     ap.add_argument('--fill_window', type=float, default=None, metavar='SECONDS', help='--fill: count activity in this many '
                     'seconds before the batch\'s earliest event time (default: everything before it)')
+    ap.add_argument('--similar', type=int, default=None, metavar='S', help='retrieve the S nearest snapshot rows of each '
+                    "source's latest neighbour in embedding space (TIGE.recommend_similar, S <= 64); prints recall@S")
+    ap.add_argument('--metric', default='cos', choices=['cos', 'ip'], help='--similar: cosine or inner product')
     a = ap.parse_args()
     if a.cold:
         m, restarted = run_cold(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, seed=a.seed, bs=a.bs,
@@ -785,8 +804,11 @@ if __name__ == '__main__':
         sys.exit(0)
     ids, _, m = run(a.data, a.root, a.ckpt, k=a.k, exclude_seen=a.exclude_seen, out_dir=a.out_dir, seed=a.seed, bs=a.bs,
                     restarter_type=a.restarter_type, snapshot=a.snapshot, walk=a.walk, fanout=a.fanout.split(','),
-                    fill=a.fill, fill_window=a.fill_window)
-    print('protocol: ' + (f'{a.walk} walk candidates per event (fanout {a.fanout}), ranked on one catalogue snapshot per batch '
+                    fill=a.fill, fill_window=a.fill_window, similar=a.similar, metric=a.metric)
+    print('protocol: ' + (f'the {a.similar} nearest snapshot rows ({a.metric}) of the source\'s latest neighbour, ranked on one '
+                          "catalogue snapshot per batch at the batch's earliest event time"
+                          if a.similar is not None else
+                          f'{a.walk} walk candidates per event (fanout {a.fanout}), ranked on one catalogue snapshot per batch '
                           "at the batch's earliest event time"
                           if a.walk is not None and a.snapshot else
                           f'{a.walk} walk candidates per event (fanout {a.fanout}), each pair embedded at the query\'s time'
@@ -794,6 +816,8 @@ if __name__ == '__main__':
                           "one catalogue snapshot per batch at the batch's earliest event time (catalogue_at='batch')"
                           if a.snapshot else 'exact - every (query, item) pair embedded at the query\'s time'))
     cov = f"recall@{a.walk} {m['coverage']:.4f}" if a.walk is not None else f"coverage {m['coverage']:.4f}"
+    if a.similar is not None:
+        cov = f"recall@{a.similar} {m['coverage']:.4f}  seeded {m['seeded']:.4f}"
     if 'coverage_walk' in m:
         cov = f"recall@{a.walk} {m['coverage_walk']:.4f} -> {m['coverage']:.4f}  filled {m['filled']:.4f}"
     if 'in_catalogue' in m:

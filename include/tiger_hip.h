@@ -1543,7 +1543,42 @@ int tg_topk_rows_host(int64_t B, int64_t C, int32_t k, const float* scores_host,
                       int64_t* out_ids_host, float* out_scores_host, int32_t* out_cols_host, int32_t* n_valid_host,
                       int64_t* n_nonfinite_host);
 
-/* Seen-item filter.  col_of: int32 [g->num_node], the column of a node id in a shared catalogue of C items, -1 when the
+/* Embedding nearest neighbours: the k best catalogue rows c [C, d] (row stride ldc floats) of every query row q [Q, d]
+ * (row stride ldq) by inner product, without the [Q, C] matrix ever being written.
+ * Score (the bits are part of the contract): s = 0.0f; for kk = 0 .. d-1: s = fmaf(q[i, kk], c[j, kk], s) - one chain per
+ * pair, which is what v_mfma_f32_32x32x2_f32 computes from accumulator 0 with k ascending - then, when given,
+ * s = s * q_scale[i], then s = s * c_scale[j]: two separately rounded float32 products in that order.  No norms and no
+ * transcendental function: cosine is the caller passing reciprocal norms.  A pair's score does not depend on its
+ * position, on n_split or on Q.
+ * Selection: exactly tg_topk_rows on that matrix with cand_shared = 1, the id of column j = ids[j] (ids NULL: j + 1) and
+ * the mask row col_mask & (id of column j != exclude[i]).  Left out: id 0, columns with col_mask[j] == 0, every column
+ * that carries row i's excluded id; a remaining non-finite score is counted into *n_nonfinite (+=) and left out.
+ * n_valid, the order (higher score first, equal scores - -0.0 == +0.0 - by ascending column), the padding (id 0, score
+ * -inf, column -1) and 1 <= k <= TG_TOPK_MAX_K are tg_topk_rows's.  out_scores holds the score's own bits.
+ * n_split: catalogue splits per query tile, one workgroup per (query tile, split); 0: the library chooses.  The result
+ * is bit-identical for every n_split, values above the number of catalogue tiles included.  A workgroup holds
+ * TG_KNN_Q_TILE query rows (half as many when d > 284: the tile must fit the LDS) against catalogue tiles of
+ * TG_KNN_C_TILE columns.  ws: tg_knn_rows_workspace_bytes(Q, C, k, n_split) bytes, 8-byte aligned: the best k keys and two
+ * counts per (row, split), no term in Q * C; a short one returns TG_EWORKSPACE before anything is written.
+ * Before any launch - TG_EINVAL: a negative size, C >= 2^31, ldq < d or ldc < d, k out of range, n_split < 0, a NULL
+ * q / c (with Q, C > 0) or output (with Q > 0), more than 2^31 - 1 workgroups; TG_EUNSUPPORTED: d == 0, d % 4 != 0 or
+ * d > 512.  Q == 0 is TG_OK with nothing launched; C == 0 is TG_OK and every position is padding.  Rows of q and c that
+ * do not start on 16-byte boundaries take a scalar-load path. */
+#define TG_KNN_Q_TILE 128
+#define TG_KNN_C_TILE 64
+size_t tg_knn_rows_workspace_bytes(int64_t Q, int64_t C, int32_t k, int32_t n_split);
+int tg_knn_rows(int64_t Q, int64_t C, int32_t d, int32_t k, const float* q, int64_t ldq, const float* c, int64_t ldc,
+                const int64_t* ids, const float* q_scale, const float* c_scale, const int64_t* exclude,
+                const uint8_t* col_mask, int32_t n_split, int64_t* out_ids, float* out_scores, int32_t* out_cols,
+                int32_t* n_valid, int64_t* n_nonfinite, void* ws, size_t ws_bytes, void* stream);
+/* The same on the host (every pointer a HOST pointer; n_split is validated and otherwise unused): plain fmaf loops.
+ * scores_out_host: float32 [Q, C] or NULL - the full score matrix, for tests. */
+int tg_knn_rows_host(int64_t Q, int64_t C, int32_t d, int32_t k, const float* q, int64_t ldq, const float* c,
+                     int64_t ldc, const int64_t* ids, const float* q_scale, const float* c_scale, const int64_t* exclude,
+                     const uint8_t* col_mask, int32_t n_split, int64_t* out_ids, float* out_scores, int32_t* out_cols,
+                     int32_t* n_valid, int64_t* n_nonfinite, float* scores_out_host);
+
+/* Seen-item filter. col_of: int32 [g->num_node], the column of a node id in a shared catalogue of C items, -1 when the
  * node is not in it.  For every event i, mask[i, col_of[nbr]] (uint8 [B, C]) is cleared for each T-CSR entry of src[i]
  * whose time is < ts[i] - strict float64, the sampler's cut; both edge directions count, as the T-CSR stores them.  The
  * call ONLY CLEARS bytes: the caller pre-fills mask with ones, or with its own mask.  A source with no entry before

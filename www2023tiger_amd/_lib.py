@@ -19,6 +19,7 @@ TG_TRAJ_LAST, TG_TRAJ_MAX, TG_TRAJ_SUM = 0, 1, 2  # tg_trajectory_accumulate mod
 TG_TRAJ_ERR_BAD_ID = 1
 TG_RANK_MAX_K = 8  # tg_rank_stats: cut-offs per call
 TG_TOPK_MAX_K = 64  # tg_topk_rows: positions per row
+TG_KNN_Q_TILE, TG_KNN_C_TILE = 128, 64  # tg_knn_rows: query rows of a workgroup, catalogue columns of a tile
 TG_FORM_FC2_DEFERRED = 16  # tiger_hip.h: bit of tg_stream_step_form
 TG_INVOLVED_MAX_K = 64  # tg_involved_list: sampler slots per query
 TG_WALK_MAX_FANOUT, TG_WALK_MAX_FRONTIER, TG_WALK_MAX_ENDPOINTS = 64, 1024, 2048  # tg_walk_candidates: the caps
@@ -384,6 +385,9 @@ SIGNATURES = {
     'tg_topk_rows_workspace_bytes': (sz, [i64, i64, i32, i32]),
     'tg_topk_rows': (C.c_int, [i64, i64, i32, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'tg_topk_rows_host': (C.c_int, [i64, i64, i32, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    'tg_knn_rows_workspace_bytes': (sz, [i64, i64, i32, i32]),
+    'tg_knn_rows': (C.c_int, [i64, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'tg_knn_rows_host': (C.c_int, [i64, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     'tg_seen_mask': (C.c_int, [P(TgTcsr), i64, vp, vp, i64, vp, vp, vp]),
     'tg_seen_mask_host': (C.c_int, [P(TgTcsr), i64, vp, vp, i64, vp, vp]),
     'tg_involved_list_workspace_bytes': (sz, [i64, i64, i32, i32]),

@@ -23,18 +23,13 @@
 #include <vector>
 
 #include "tg_sample.h"
+#include "tg_topk_keys.h"
 
 namespace tg {
 
 constexpr int TK_U = 4;    // 64-column chunks in flight per step
 constexpr int TK_WPB = 4;  // wavefronts of a workgroup
 
-__host__ __device__ __forceinline__ bool topk_finite(uint32_t u) { return (u & 0x7f800000u) != 0x7f800000u; }
-__host__ __device__ __forceinline__ uint64_t topk_key(uint32_t u, uint32_t col) {
-  if ((u << 1) == 0) u = 0;  // -0.0 ties +0.0
-  const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)o << 32) | (uint64_t)(uint32_t)~col;
-}
 __host__ __device__ __forceinline__ bool topk_left_in(const int64_t* cand, const uint8_t* mask, int64_t j) {
   return cand[j] != 0 && (!mask || mask[j]);
 }
@@ -53,27 +48,6 @@ struct TopkArgs {
   uint64_t* ws_keys;  // [B, n_seg, k]
   int32_t* ws_cnt;    // [B, n_seg, 2]: columns left in, non-finite scores met
 };
-
-__device__ __forceinline__ uint64_t lane_bcast(uint64_t v, int src) {
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src), hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// best: lane p holds the p-th largest key met so far (0: none).  Inserts the lanes' keys that beat the one at lane kth.
-__device__ __forceinline__ void topk_insert(uint64_t& best, uint64_t key, int kth, int lane) {
-  uint64_t thr = lane_bcast(best, kth);
-  unsigned long long todo = __ballot(key > thr);
-  while (todo) {  // wave-uniform
-    const int src = __builtin_amdgcn_readfirstlane(__ffsll(todo) - 1);
-    todo &= todo - 1;
-    const uint64_t x = lane_bcast(key, src);
-    if (x > thr) {  // the threshold has risen since the ballot
-      const uint64_t up = __shfl_up(best, 1);
-      if (best < x) best = (lane == 0 || up > x) ? x : up;
-      thr = lane_bcast(best, kth);
-    }
-  }
-}
 
 __device__ __forceinline__ void topk_finish(const TopkArgs& a, int64_t row, uint64_t best, int nv, int bad, int lane) {
   if (lane < a.k) {

@@ -646,7 +646,8 @@ def eval_edge_ranking(model, dl, device: torch.device, candidates, *, ks=(1, 3, 
     return out
 
 
-def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk: Optional[dict] = None, k: int = 10,
+def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk: Optional[dict] = None,
+                        similar: Optional[dict] = None, k: int = 10,
                         exclude_seen: bool = False, chunk_queries: int = 65536, restart_mode: bool = False,
                         return_positions: bool = False, lazy_restarts: bool = False, uptodate_nodes: Optional[set] = None,
                         catalogue_at: Optional[str] = None) -> dict:
@@ -689,8 +690,17 @@ def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk
     ranked.  coverage is then the recall of the FILLED rows; `coverage_walk`, the recall before filling, and `filled`, the
     filled candidates divided by all valid candidates, are added.  Its effect on hit rate / NDCG on trained weights has
     not been measured.
+    similar (dict(S=..., catalogue=int64 [C], metric='cos' | 'ip'); instead of a catalogue or a walk): retrieve in
+    embedding space, then rank - per batch ONE snapshot of similar['catalogue'] at the batch's earliest event time on the
+    state before the batch (the catalogue_at='batch' rule), every event's seed by the default rule of
+    TIGE.recommend_similar at the event's own time (the source's latest neighbour before it), its S nearest snapshot rows
+    (tg_knn_rows) and `recommend_subset` on them.  coverage is the generator's recall@S; `seeded`, the share of events
+    whose seed has a row in the snapshot, and `candidates`, the mean number of candidates per event, are added.  An
+    APPROXIMATION in the same sense as catalogue_at='batch'; embedding nearness is not what the score head was trained on
+    and its effect on hit rate / NDCG on trained weights has not been measured.
     Refused: restart_mode=True (use lazy_restarts=True), a catalogue_at other than None / 'batch', walk together with a
-    catalogue or with catalogue_at, neither a catalogue nor a walk, and whatever TIGE.recommend refuses."""
+    catalogue or with catalogue_at, similar together with walk, a catalogue, catalogue_at, exclude_seen or lazy_restarts,
+    none of a catalogue, a walk and similar, and whatever TIGE.recommend refuses."""
     from . import hip_ops
     if restart_mode:
         raise NotImplementedError('eval_recommendation: restart_mode=True is not built (the lazy restarts of '
@@ -700,6 +710,14 @@ def eval_recommendation(model, dl, device: torch.device, catalogue=None, *, walk
         raise ValueError(f"eval_recommendation: catalogue_at is None (exact) or 'batch', not {catalogue_at!r}")
     if walk is not None and (catalogue is not None or catalogue_at is not None):
         raise ValueError('eval_recommendation: walk generates per-event candidates; it takes neither a catalogue nor catalogue_at')
+    if similar is not None:
+        if walk is not None:
+            raise ValueError('eval_recommendation: walk and similar are two candidate generators; give one of them')
+        if catalogue is not None or catalogue_at is not None:
+            raise ValueError("eval_recommendation: similar takes its catalogue as similar['catalogue'], and neither a "
+                             'catalogue nor catalogue_at beside it')
+        return _eval_recommendation_similar(model, dl, device, dict(similar), k, exclude_seen, chunk_queries, return_positions,
+                                            lazy_restarts)
     if walk is None and catalogue is None:
         raise ValueError('eval_recommendation: give a shared catalogue, or walk=dict(C=..., ...) for per-event walk candidates')
     if walk is not None:
@@ -863,6 +881,71 @@ def _eval_recommendation_walk(model, dl, device, walk: dict, k: int, exclude_see
         n_walked, n_filled, n_all = filled.cpu().tolist()
         out['coverage_walk'] = n_walked / n if n else nan
         out['filled'] = n_filled / n_all if n_all else nan
+    if return_positions:
+        out['positions'] = torch.cat(positions) if positions else torch.zeros(0, dtype=torch.int64, device=device)
+    return out
+
+
+def _eval_recommendation_similar(model, dl, device, similar: dict, k: int, exclude_seen: bool, chunk_queries: int,
+                                 return_positions: bool, lazy_restarts: bool) -> dict:
+    """eval_recommendation(similar=...): the same loop and folds with the embedding neighbours of every event's seed"""
+    from . import hip_ops
+    from ._lib import TG_TOPK_MAX_K
+    unknown = set(similar) - {'S', 'catalogue', 'metric'}
+    if unknown or 'S' not in similar or 'catalogue' not in similar:
+        raise ValueError(f"eval_recommendation: similar is dict(S=..., catalogue=..., metric='cos' | 'ip'); got {sorted(similar)}")
+    S, metric = int(similar['S']), similar.get('metric', 'cos')
+    if not 1 <= S <= TG_TOPK_MAX_K:
+        raise ValueError(f"eval_recommendation: 1 <= similar['S'] <= {TG_TOPK_MAX_K} (TG_TOPK_MAX_K)")
+    if metric not in ('cos', 'ip'):
+        raise ValueError(f"eval_recommendation: similar['metric'] is 'cos' or 'ip', got {metric!r}")
+    if exclude_seen or lazy_restarts:
+        raise NotImplementedError('eval_recommendation: similar is built without exclude_seen and without lazy_restarts')
+    model._refuse_partitioned('eval_recommendation')
+    model.eval()
+    k = int(k)
+    cat = torch.as_tensor(similar['catalogue']).long().to(device)
+    if cat.dim() != 1 or cat.numel() == 0:
+        raise ValueError("eval_recommendation: similar['catalogue'] is int64 [C], C >= 1, shared by all events")
+    hip_ops.catalogue_index(cat, model.n_nodes)  # no id twice, every id a node: refused before the first batch
+    graph = getattr(getattr(dl, 'collate_fn', None), 'graph', None)
+    acc = torch.zeros(4, dtype=torch.float64, device=device)  # hits, sum of gains, sum of reciprocal places, covered
+    gen = torch.zeros(2, dtype=torch.float64, device=device)  # events whose seed has a row, candidates generated
+    place = torch.arange(k, dtype=torch.int64, device=device)
+    positions, n = [], 0
+    with torch.no_grad():
+        for src_ids, dst_ids, neg_dst_ids, ts, eids, _, comp_graph in BackgroundThreadGenerator(dl):
+            src_ids, dst_ids, neg_dst_ids = (x.long().to(device) for x in (src_ids, dst_ids, neg_dst_ids))
+            ts, eids = ts.float().to(device), eids.long().to(device)
+            comp_graph.to(device)
+            ts64 = getattr(comp_graph, 'ts64', None)
+            t = (ts if ts64 is None else ts64).to(device)
+            g = graph if graph is not None else getattr(comp_graph, 'graph', None)
+            g = model.graph if g is None else g
+            if len(src_ids):
+                snap = model.embed_catalogue(cat, float(t.double().min()), graph=g)
+                ids, _, _, rows = model.recommend_similar(src_ids, t, snap, k, S=S, metric=metric, graph=g,
+                                                          chunk_queries=chunk_queries)
+                cand = rows['ids']
+                gen += torch.stack([(snap.col_of[rows['seeds']] >= 0).logical_and(rows['seeds'] != 0).sum().double(),
+                                    (cand != 0).sum().double()])
+                hit = (ids == dst_ids[:, None]) & (ids != 0)
+                pos = torch.where(hit.any(1), torch.where(hit, place, k).amin(1), -1)
+                listed = pos >= 0
+                p64 = pos.clamp(min=0).double()
+                covered = ((cand == dst_ids[:, None]) & (cand != 0)).any(1)         # the generator's recall@S
+                acc += torch.stack([listed.sum().double(), (listed / torch.log2(p64 + 2.0)).sum(),
+                                    (listed / (p64 + 1.0)).sum(), covered.sum().double()])
+                if return_positions:
+                    positions.append(pos)
+            model.contrast_learning(src_ids, dst_ids, neg_dst_ids, ts, eids, comp_graph)
+            n += len(src_ids)
+    model._poll_train_errors()
+    a = acc.cpu().tolist()
+    nan = float('nan')
+    n_seeded, n_gen = gen.cpu().tolist()
+    out = dict(hit_rate=a[0] / n if n else nan, ndcg=a[1] / n if n else nan, mrr_at_k=a[2] / n if n else nan, n_events=n,
+               coverage=a[3] / n if n else nan, seeded=n_seeded / n if n else nan, candidates=n_gen / n if n else nan)
     if return_positions:
         out['positions'] = torch.cat(positions) if positions else torch.zeros(0, dtype=torch.int64, device=device)
     return out

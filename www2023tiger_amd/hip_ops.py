@@ -274,6 +274,89 @@ def topk_rows(scores: Tensor, cand_ids: Tensor, k: int, *, mask: Optional[Tensor
     return out
 
 
+def _rows_f32(t: Tensor, what: str) -> Tuple[Tensor, int]:
+    """float32 [n, d] with unit column stride -> (tensor, row stride in floats); a view with a larger row stride is kept"""
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f'knn_rows: {what} is float32 [n, d]')
+    n, d = t.shape
+    if n * d and t.stride(1) != 1:
+        t = t.contiguous()
+    ld = t.stride(0) if n > 1 and d > 0 else d
+    if ld < d:
+        t, ld = t.contiguous(), d
+    return t, ld
+
+
+def knn_rows(q: Tensor, c: Tensor, k: int, *, ids: Optional[Tensor] = None, q_scale: Optional[Tensor] = None,
+             c_scale: Optional[Tensor] = None, exclude: Optional[Tensor] = None, col_mask: Optional[Tensor] = None,
+             n_split: int = 0, acc=None, _scores_out: Optional[Tensor] = None) -> dict:
+    """The k nearest rows of c [C, d] for every row of q [Q, d] by inner product (tiger_hip.h: tg_knn_rows); the [Q, C]
+    score matrix is never formed.  Score: the float32 fmaf chain over d, k ascending, then `* q_scale[i]`, then
+    `* c_scale[j]` when given (cosine: pass reciprocal norms).  ids: int64 [C], the id of column j (None: j + 1); exclude:
+    int64 [Q], an id left out of row i; col_mask: bool [C], false = left out for every row.  Id 0 and non-finite scores
+    (counted) are left out as in topk_rows, whose order and padding these are.
+    -> dict(ids int64 [Q, k], scores float32 [Q, k], cols int32 [Q, k]; n_valid int32 [Q]; n_nonfinite int64 [1], the
+    accumulator `acc` when given).  n_split: catalogue splits per query tile (0: the library chooses); the result does not
+    depend on it.  q and c may be views with a row stride above d.  Device tensors take the device entry, host tensors the
+    host twin (`_scores_out`: float32 [Q, C] host tensor that receives the twin's full matrix, for tests).  ValueError for
+    what the C entry refuses and for tensors on different devices."""
+    dev = q.device
+    q, ldq = _rows_f32(q, 'q')
+    c, ldc = _rows_f32(c, 'c')
+    (Q, d), C = q.shape, c.shape[0]
+    if c.shape[1] != d:
+        raise ValueError(f'knn_rows: q {tuple(q.shape)}, c {tuple(c.shape)}')
+    if d == 0 or d % 4 or d > 512:
+        raise ValueError('knn_rows: d is a positive multiple of 4, at most 512')
+    k, n_split = int(k), int(n_split)
+    if not 1 <= k <= _lib.TG_TOPK_MAX_K:
+        raise ValueError(f'knn_rows: 1 <= k <= {_lib.TG_TOPK_MAX_K}')
+    if n_split < 0:
+        raise ValueError('knn_rows: n_split is 0 (chosen by the library) or positive')
+    if C >= 1 << 31:
+        raise ValueError('knn_rows: C < 2^31')
+
+    def vec(t, n, dtype, what):
+        if t is None:
+            return None
+        if t.device != dev:
+            raise ValueError(f'knn_rows: {what} on {t.device}, q on {dev}')
+        if t.dtype == torch.bool and dtype == torch.uint8:
+            t = t.to(torch.uint8)
+        if t.dtype != dtype or t.shape != (n,):
+            raise ValueError(f'knn_rows: {what} is {dtype} [{n}], got {t.dtype} {tuple(t.shape)}')
+        return t.contiguous()
+
+    if c.device != dev:
+        raise ValueError(f'knn_rows: c on {c.device}, q on {dev}')
+    ids = vec(ids, C, torch.int64, 'ids')
+    q_scale = vec(q_scale, Q, torch.float32, 'q_scale')
+    c_scale = vec(c_scale, C, torch.float32, 'c_scale')
+    exclude = vec(exclude, Q, torch.int64, 'exclude')
+    col_mask = vec(col_mask, C, torch.uint8, 'col_mask')
+    if acc is None:
+        acc = torch.zeros(1, dtype=torch.int64, device=dev)
+    elif acc.device != dev or acc.dtype != torch.int64:
+        raise ValueError('knn_rows: acc is an int64 tensor on the device of q')
+    out = dict(ids=torch.empty(Q, k, dtype=torch.int64, device=dev), scores=torch.empty(Q, k, dtype=torch.float32, device=dev),
+               cols=torch.empty(Q, k, dtype=torch.int32, device=dev), n_valid=torch.empty(Q, dtype=torch.int32, device=dev),
+               n_nonfinite=acc)
+    args = (Q, C, d, k, ptr(q), ldq, ptr(c), ldc, ptr(ids), ptr(q_scale), ptr(c_scale), ptr(exclude), ptr(col_mask), n_split,
+            ptr(out['ids']), ptr(out['scores']), ptr(out['cols']), ptr(out['n_valid']), ptr(acc))
+    if dev.type == 'cpu':
+        if _scores_out is not None and (_scores_out.dtype != torch.float32 or _scores_out.shape != (Q, C)
+                                        or not _scores_out.is_contiguous() or _scores_out.device != dev):
+            raise ValueError('knn_rows: _scores_out is a contiguous float32 [Q, C] host tensor')
+        check(lib.tg_knn_rows_host(*args, ptr(_scores_out)), 'tg_knn_rows_host')
+    else:
+        if _scores_out is not None:
+            raise ValueError('knn_rows: the device entry never forms the score matrix')
+        nbytes = int(lib.tg_knn_rows_workspace_bytes(Q, C, k, n_split))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.tg_knn_rows(*args, ptr(ws), ws.numel(), stream_ptr(dev)), 'tg_knn_rows')
+    return out
+
+
 def catalogue_index(cand: Tensor, n_nodes: int) -> Tensor:
     """int32 [n_nodes] on cand's device: the column of every node id in the shared catalogue cand [C], -1 for a node that
     is not in it (the `col_of` of seen_mask).  ValueError for an id outside [0, n_nodes) or listed twice."""

@@ -83,6 +83,7 @@ class CatalogueSnapshot:
         self._P = None
         self._P_stamp = None
         self._col_of = None
+        self._inv_norm = None
         self.t_row = None
         self.change_epoch = None
 
@@ -99,6 +100,17 @@ class CatalogueSnapshot:
         if grown > 0:  # the model admitted node ids since (TIGE.grow_nodes): none of them is in the snapshot
             self._col_of = torch.cat([self._col_of, self._col_of.new_full((grown,), -1)])
         return self._col_of
+
+    @property
+    def inv_norm(self) -> Tensor:
+        """float32 [C]: 1 / ||h[j]||, the norm taken in float64 and the reciprocal rounded once; 0 for a zero or non-finite
+        norm.  Built on first use (TIGE.similar_items with metric='cos' passes it to tg_knn_rows on both sides) and kept:
+        h is read-only.  A refreshed snapshot is a new object and computes its own."""
+        if self._inv_norm is None:
+            n = self.h.double().pow(2).sum(1).sqrt()
+            ok = torch.isfinite(n) & (n > 0)
+            self._inv_norm = torch.where(ok, 1.0 / torch.where(ok, n, torch.ones_like(n)), torch.zeros_like(n)).float()
+        return self._inv_norm
 
     def __len__(self):
         return int(self.ids.numel())
@@ -1795,6 +1807,127 @@ class TIGE(nn.Module):
                                                          chunk_queries=chunk_queries)
             found = (snapshot.col_of[cand['ids']] >= 0) & (cand['ids'] != 0)
             cand['n_in_catalogue'] = found.sum(1).to(torch.int32)
+        return ids, scores, n_valid, cand
+
+    # ---- embedding nearest neighbours on a catalogue snapshot ----------------------------------------------
+    def _similar_refusals(self, what: str, snapshot, graph, stale_ok: bool, metric: str):
+        self._refuse_partitioned(what)
+        if not isinstance(snapshot, CatalogueSnapshot):
+            raise ValueError(f'{what}: snapshot is a CatalogueSnapshot of embed_catalogue')
+        if metric not in ('cos', 'ip'):
+            raise ValueError(f"{what}: metric is 'cos' or 'ip', got {metric!r}")
+        self._check_snapshot(snapshot, self.graph if graph is None else graph, stale_ok)
+
+    def _similar(self, what: str, items: Tensor, snapshot: CatalogueSnapshot, k: int, metric: str, exclude_self: bool,
+                 mask: Optional[Tensor], found: Optional[Tensor] = None) -> dict:
+        """tg_knn_rows of the snapshot rows of `items` against all rows -> the dict of hip_ops.knn_rows.  found (bool [B]):
+        the items that have a row; the others get an empty list (n_valid 0, padding) instead of being refused"""
+        dev = self.device
+        col = snapshot.col_of[items].long()
+        if found is not None:
+            col = torch.where(found, col, torch.zeros_like(col))
+        q = snapshot.h[col]
+        cos = metric == 'cos'
+        inv = snapshot.inv_norm if cos else None
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(dev)
+            if mask.dtype != torch.bool or mask.shape != (len(snapshot),):
+                raise ValueError(f'{what}: mask is bool [C = {len(snapshot)}], got {mask.dtype} {tuple(mask.shape)}')
+        out = hip_ops.knn_rows(q, snapshot.h, k, ids=snapshot.ids, q_scale=inv[col] if cos else None, c_scale=inv,
+                               exclude=items if exclude_self else None, col_mask=mask)
+        if found is not None and items.numel():
+            lost = ~found
+            out['ids'][lost] = 0
+            out['scores'][lost] = float('-inf')
+            out['cols'][lost] = -1
+            out['n_valid'][lost] = 0
+        return out
+
+    @torch.no_grad()
+    def similar_items(self, items: Tensor, snapshot: CatalogueSnapshot, k: int, *, metric: str = 'cos',
+                      exclude_self: bool = True, mask: Optional[Tensor] = None, stale_ok: bool = False):
+        """The k nearest catalogue items of every item in embedding space, both "as of the snapshot": the query rows are
+        snapshot.h[snapshot.col_of[items]], the catalogue is snapshot.h, and tg_knn_rows selects on the MFMA accumulators -
+        the [B, C] matrix is never formed -> (ids int64 [B, k], scores float32 [B, k], n_valid int32 [B]).  metric 'ip': the
+        float32 inner product (the fmaf chain of tiger_hip.h); 'cos': that times snapshot.inv_norm of the item, then of the
+        neighbour (a zero row scores 0 against everything).  exclude_self leaves the item itself out of its own list; mask:
+        bool [C] over the snapshot's rows, false = left out for every item.  Padding id 0 rows of the snapshot and
+        non-finite scores are left out; order and padding are those of recommend (tg_topk_rows).  Reads nothing but the
+        snapshot, writes nothing.  Refused before anything runs: what recommend on a snapshot refuses (another model's or
+        device's snapshot, a stale one - RuntimeError - unless stale_ok; a partitioned model); an item that is the
+        padding id 0, outside [0, n_nodes) or not in the snapshot, naming the first offender; k outside
+        [1, TG_TOPK_MAX_K]; a memory_dim that tg_knn_rows does not take (a multiple of 4, at most 512)."""
+        self._similar_refusals('similar_items', snapshot, None, stale_ok, metric)
+        items = torch.as_tensor(items).to(self.device).long().contiguous().reshape(-1)
+        if not 1 <= int(k) <= TG_TOPK_MAX_K:
+            raise ValueError(f'similar_items: 1 <= k <= {TG_TOPK_MAX_K}')
+        if items.numel():
+            bad = (items <= 0) | (items >= snapshot.col_of.numel())
+            bad = bad | (snapshot.col_of[torch.where(bad, torch.zeros_like(items), items)] < 0)
+            if bool(bad.any()):
+                at = int(bad.int().argmax())
+                raise ValueError(f'similar_items: item {int(items[at])} (position {at}) is the padding id 0, outside '
+                                 f'[0, {self.n_nodes}) or not in the snapshot')
+        out = self._similar('similar_items', items, snapshot, int(k), metric, exclude_self, mask)
+        return out['ids'], out['scores'], out['n_valid']
+
+    def similar_items_keys(self, idmap, item_keys, snapshot: CatalogueSnapshot, k: int, **kw):
+        """`similar_items` behind external keys -> (keys int64 [B, k], scores, n_valid); keys = idmap.keys_of(ids), so
+        positions past n_valid[i] hold INT64_MIN, as in recommend_keys.  A key the map (or the model) does not know raises
+        ValueError saying how many."""
+        item_keys = self._device_keys('similar_items_keys', 'item_keys', item_keys).reshape(-1)
+        if idmap.device != self.device:
+            raise ValueError(f'similar_items_keys: the id map lives on {idmap.device}, the model on {self.device}')
+        ids = idmap.lookup(item_keys)
+        unknown = int(((ids < 0) | (ids >= self.n_nodes)).sum())
+        if unknown:
+            raise ValueError(f'similar_items_keys: {unknown} of the {ids.numel()} items are keys the model has never seen')
+        out, scores, n_valid = self.similar_items(ids.long(), snapshot, k, **kw)
+        return idmap.keys_of(out, check=False), scores, n_valid
+
+    def recommend_similar(self, src_ids: Tensor, ts: Tensor, snapshot: CatalogueSnapshot, k: int, *, S: int = 64,
+                          seeds: Optional[Tensor] = None, metric: str = 'cos', graph=None, **recommend_subset_kwargs):
+        """Retrieve in embedding space, rank with the score head: every query's candidates are the S nearest snapshot rows
+        of its SEED item (`similar_items` without the seed itself), and `recommend_subset(src_ids, ts, snapshot, k,
+        cand['ids'])` lists the k best of them -> (ids int64 [B, k], scores float32 [B, k], n_valid int32 [B], cand =
+        dict(ids int64 [B, S], scores, cols, n_valid, seeds)).  seeds: int64 [B], 0 = none; None: each source's latest
+        neighbour strictly before its time, `hip_ops.walk_candidates(graph, src, ts, 1, fanout=(1,), take=(True,))`.  A
+        query whose seed is 0 or not in the snapshot has no candidates: n_valid == 0.  S <= TG_TOPK_MAX_K (tg_knn_rows
+        selects at most that many; a larger S is refused, not looped).
+        The approximation is recommend_subset's: items as of the snapshot - seed and neighbours are the snapshot's rows,
+        never a query's future.  Inner-product or cosine nearness of embeddings is NOT what the score head was trained on:
+        the generator proposes, the score head disposes, and the effect of this generator on hit rate / NDCG with trained
+        weights has not been measured.  Whatever recommend_subset refuses is refused before the retrieval runs."""
+        graph, _ = self._pair_refusals('recommend_similar', graph, int(recommend_subset_kwargs.get('chunk_queries', 65536)),
+                                       recommend_subset_kwargs.get('uptodate'))
+        if not 1 <= int(S) <= TG_TOPK_MAX_K:
+            raise ValueError(f'recommend_similar: 1 <= S <= {TG_TOPK_MAX_K} (TG_TOPK_MAX_K, the most positions tg_knn_rows '
+                             'selects per row)')
+        if not 1 <= int(k) <= TG_TOPK_MAX_K:
+            raise ValueError(f'recommend_similar: 1 <= k <= {TG_TOPK_MAX_K}')
+        self._similar_refusals('recommend_similar', snapshot, graph, bool(recommend_subset_kwargs.get('stale_ok', False)), metric)
+        self._shared_refusals('recommend_similar')
+        dev = self.device
+        src_ids = src_ids.to(dev).long().contiguous().reshape(-1)
+        ts64 = ts.to(dev).double().contiguous().reshape(-1)
+        B = src_ids.numel()
+        if ts64.numel() != B:
+            raise ValueError(f'recommend_similar: {B} queries, ts {tuple(ts.shape)}')
+        if seeds is None:
+            seeds = hip_ops.walk_candidates(graph, src_ids, ts64, 1, fanout=(1,), take=(True,))['ids'].reshape(-1)
+        else:
+            seeds = torch.as_tensor(seeds).to(dev).long().contiguous().reshape(-1)
+            if seeds.numel() != B:
+                raise ValueError(f'recommend_similar: {B} queries, seeds {tuple(seeds.shape)}')
+            if B:
+                self._check_ids(seeds, 'recommend_similar: a seed outside [0, n_nodes)')
+        with torch.no_grad():
+            col_of = snapshot.col_of
+            found = (seeds > 0) & (col_of[seeds.clamp(0, col_of.numel() - 1)] >= 0) if B else seeds.bool()
+            cand = self._similar('recommend_similar', seeds, snapshot, int(S), metric, True, None, found)
+        cand['seeds'] = seeds
+        ids, scores, n_valid = self.recommend_subset(src_ids, ts64, snapshot, k, cand['ids'], graph=graph,
+                                                     **recommend_subset_kwargs)
         return ids, scores, n_valid, cand
 
     # ---- fused path ---------------------------------------------------------------------
